@@ -12,9 +12,12 @@ step    : one PBNet.forward over one scene per rank (1 rotated copy).  N > 1: ev
           (identical per-GPU work), no data-path collective (scenes are independent at inference) -> weak scaling; the
           process group (RCCL) only carries the barrier and the max-over-ranks of the elapsed time.  The process group is
           initialised at N = 1 too (one all-reduce + barrier) so that the RCCL path is known to work on the box.
-timing  : W warm-up steps, then `--repeats` timed blocks of EXACTLY K steps, each bracketed by barrier +
-          torch.cuda.synchronize() on both sides and reduced with MAX over ranks.  `value` / `ms_per_step` come from the
-          MEDIAN block; p10 / p90 over the blocks are reported beside it.
+timing  : W warm-up steps, then ONE timed block of EXACTLY K steps, bracketed by barrier + torch.cuda.synchronize() on
+          both sides and reduced with MAX over ranks: `value` / `ms_per_step` come from that block.  `--repeats` /
+          `--min-seconds` ask for more blocks of K steps (defaults 5 / 2 s under `--full`): the MEDIAN block is then
+          reported, p10 / p90 over the blocks beside it.
+outputs : `--dump-outputs DIR` writes what the last timed step returned to its caller, one DIR/<name>.npy per array
+          (float32 / float64, at most 64 MB in all): the inputs are seeded, so two builds compare output for output.
 in flight: the K steps of a rank are taken round-robin by `--inflight` host threads (default 4), each on its own HIP
           stream: most launches of the path are far too small for 256 CUs, so kernels of independent scenes overlap
           on the device and one scene's host read-backs hide behind another's kernels.  Results are bit-identical to
@@ -22,7 +25,9 @@ in flight: the K steps of a rank are taken round-robin by `--inflight` host thre
           inverse rate); the latency of a scene alone on the GPU is config.one_scene_in_flight_ms_per_scene, and
           `--inflight 1` runs the reference's one-scene-at-a-time loop.
 
-Also on the JSON line:
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the outputs, the JSON line.  With `--full`
+the line also carries the RCCL self-check (config.rccl.selfcheck), the figures below and the side legs (fp32,
+graph_f16, planned, batched3, served, c4, train_step):
   roofline     -- the dominant kernel family (k_spconv*, csrc/spconv.hip): algorithmic bytes of every launch
                   ((V_in*C_in + V_out*C_out)*b + K*C_in*C_out*b + 8*P, true channel counts, no residual term) divided by
                   that launch's duration, measured with HIP events on the launching stream in an instrumented pass over
@@ -468,6 +473,7 @@ class Runner(object):
         self.model, self.b, self.t, self.inflight, self.device, self.mode = model, b, t, inflight, device, mode
         self.streams = inflight_streams(device, inflight) if inflight > 1 else [None]
         self.last = [None] * len(self.streams)
+        self.final = None            # what the last step of the last `run` returned
         self.pfs = None
         if mode != "size-exact":
             from pbnet_amd import planned
@@ -497,6 +503,7 @@ class Runner(object):
                 self.last[0] = self.step(0)
             if self.streams[0] is not None:
                 torch.cuda.synchronize()
+            self.final = self.last[0]
             return
         errors = []
 
@@ -516,15 +523,16 @@ class Runner(object):
             th.join()
         if errors:
             raise errors[0]
+        self.final = self.last[(n - 1) % m] if n > 0 else None     # step n - 1 is the one worker (n - 1) % m took last
 
     def result(self):
         return next(r for r in self.last if r is not None)
 
 
-def init_process_group(world, rank, device):
+def init_process_group(world, rank, device, selfcheck=True):
     """RCCL process group (backend "nccl" is RCCL on ROCm), also at world size 1: init + one all-reduce + barrier, so the
-    multi-GPU code path has run on this box before an 8-GPU node ever sees it.  At N = 1 a failure is reported on the JSON
-    line instead of failing the run (the single-GPU metric does not need the group)."""
+    multi-GPU code path has run on this box before an 8-GPU node ever sees it; `selfcheck` adds rccl_selfcheck.  At N = 1 a
+    failure is reported on the JSON line instead of failing the run (the single-GPU metric does not need the group)."""
     import torch.distributed as dist
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     if world == 1 and "MASTER_PORT" not in os.environ:
@@ -542,7 +550,7 @@ def init_process_group(world, rank, device):
         want = world * (world + 1) / 2
         if float(probe[0]) != want:
             raise RuntimeError("all-reduce returned %r, expected %r" % (float(probe[0]), want))
-        check = rccl_selfcheck(dist, world, rank, device)
+        check = rccl_selfcheck(dist, world, rank, device) if selfcheck else None
         return dist, {"status": "ok (backend nccl = RCCL, world %d: init, all-reduce, barrier)" % world, "selfcheck": check}
     except Exception as e:  # noqa: BLE001
         if world > 1:
@@ -676,20 +684,63 @@ def dry_run(args):
                           "roofline": None}), flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(ret, out_dir):
+    """`--dump-outputs DIR`: the arrays one step handed its caller (PBNet.forward's dict; tuple members as <key>_<i>), one
+    DIR/<name>.npy each -- floating tensors as float32 (float64 stays float64), integer and bool tensors as float64 (exact below
+    2^53).  The files stay within 64 MB: if the arrays are larger together, one above its even share of that is cut to a sample of
+    its rows drawn with a fixed seed, and the rows taken are written beside it as <name>.sample_rows.npy.  Returns {name: shape
+    written}."""
+    arrays = []
+    for key in sorted(ret):
+        v = ret[key]
+        for j, x in (enumerate(v) if isinstance(v, (tuple, list)) else [(None, v)]):
+            if not torch.is_tensor(x):
+                continue
+            a = x.detach()
+            a = a.double() if (a.dtype == torch.float64 or not a.is_floating_point()) else a.float()
+            arrays.append((key if j is None else "%s_%d" % (key, j), a.cpu().numpy()))
+    os.makedirs(out_dir, exist_ok=True)
+    fits = sum(a.nbytes for _, a in arrays) <= DUMP_LIMIT_BYTES
+    share = DUMP_LIMIT_BYTES // max(1, 2 * len(arrays))         # room for a sample and its row indices
+    written = {}
+    for name, a in arrays:
+        if not fits and a.nbytes > share and a.ndim > 0 and a.shape[0] > 1:
+            row_bytes = max(1, a.nbytes // a.shape[0])
+            k = max(1, min(a.shape[0], share // row_bytes))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=k, replace=False))
+            np.save(os.path.join(out_dir, name + ".sample_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        written[name] = list(a.shape)
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=6)
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps at least; the median block is reported")
-    ap.add_argument("--min-seconds", type=float, default=2.0,
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed blocks of --steps steps at least; the median block is reported (default 1; 5 with --full)")
+    ap.add_argument("--min-seconds", type=float, default=None,
                     help="keep adding timed blocks (EXACTLY --steps steps each) until this much timed wall has accumulated "
-                         "(VERDICT round 4: 5 blocks of 0.06 s carried 5-10 %% of noise); at most --max-blocks blocks")
+                         "(VERDICT round 4: 5 blocks of 0.06 s carried 5-10 %% of noise); at most --max-blocks blocks "
+                         "(default 0; 2 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: RCCL self-check, roofline probes, stage breakdown, TTA and "
+                         "configuration legs, serving grid, training step, CPU baseline, repeated timed blocks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all)")
     ap.add_argument("--max-blocks", type=int, default=64)
     ap.add_argument("--copies", type=int, default=1, help="rotated copies per scene (reference eval uses 3: TTA)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the stage breakdown, the TTA leg and the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the stage breakdown, the TTA leg, the side legs and the CPU baseline")
     ap.add_argument("--switch-interval", type=float, default=float(os.environ.get("PBN_BENCH_SWITCH", "0") or 0),
                     help="sys.setswitchinterval for the in-flight host threads (0 = Python's default 5 ms)")
     ap.add_argument("--inflight", type=int, default=4,
@@ -703,6 +754,10 @@ def main():
                     help="no GPU: rendezvous over gloo, a stand-in step, the same barriers / MAX-over-ranks timing / JSON line "
                          "(tests/test_launch_cpu.py proves the N-rank plumbing before an 8-GPU node runs it)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.min_seconds is None:
+        args.min_seconds = 2.0 if args.full else 0.0
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args)          # `python bench.py --gpus N` by itself: one child per rank, started BEFORE any GPU call
     if args.dry_run:
@@ -725,7 +780,9 @@ def main():
     assert world == args.gpus, "WORLD_SIZE %d does not match --gpus %d (launch with torch.distributed.run --nproc-per-node %d, or run `python bench.py --gpus %d` by itself: it starts its ranks)" % (world, args.gpus, args.gpus, args.gpus)
     phases["import_torch"] = round(time.perf_counter() - T_START, 2)
     t_phase[0] = time.perf_counter()
-    dist, rccl_status = init_process_group(world, rank, device)
+    # opened at world size 1 too, also in a plain run: measured, the in-flight rate of a plain run without it is ~15 % lower
+    # (~280 against ~340 scenes/s, alternating runs on one MI355X); the 64 MB self-check of RCCL runs under --full only
+    dist, rccl_status = init_process_group(world, rank, device, selfcheck=args.full)
     phase("rccl_init")
 
     dtype = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}[args.dtype]
@@ -780,12 +837,16 @@ def main():
     phase("warmup_and_timed_blocks")
     elapsed = float(np.median(blocks))
     rate = lambda e: world * args.steps / e
-    ret = runner.result()
+    ret = runner.final                      # the last timed step's result (the probes below run the runner again)
     n_prop = int(ret["proposals"][1].shape[0] - 1)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(ret, args.dump_outputs)
+        phase("dump_outputs")
 
     roof = cpu = single_ms = stages = grouping = tta = None
     legs = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         n_probe = max(2, min(args.steps, 5)) * args.inflight
 
         def probe_leg(run, n):
@@ -990,7 +1051,7 @@ def main():
             "dtype": args.dtype,
             "data": "synthetic room scene (pbnet_amd/synth.py), random-init weights (seed 22), teacher-forced "
                     "semantic/offset head outputs",
-            "gpu_active": gpu_active(args),
+            "gpu_active": gpu_active(args) if args.full else None,
             "timed_blocks": {"n": len(blocks), "steps_per_block": args.steps, "timed_seconds": round(float(sum(blocks)), 3),
                              "cv": round(float(np.std(blocks) / np.mean(blocks)), 4),
                              "statistic": "median", "value_p10": round(rate(float(np.percentile(blocks, 90))), 3),
@@ -1015,6 +1076,8 @@ def main():
         }
         if per_rank is not None:
             line["per_rank"] = per_rank
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if stages is not None:
             line["stages_ms"] = stages
             line["grouping"] = grouping

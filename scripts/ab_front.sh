@@ -1,6 +1,6 @@
 #!/bin/bash
 # the device front of the size-exact forward on / off by scene size: 1 and 3 copies of the configs[1] scene, the configs[3] scene
-one() { python bench.py "$@" 2>/dev/null | python -c "
+one() { python bench.py --full "$@" 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

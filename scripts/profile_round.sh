@@ -1,6 +1,6 @@
 #!/bin/bash
 # Everything profiles/ holds for one milestone, from one box:  bash scripts/profile_round.sh r02_a
-#   <tag>_bench.json                   the default bench.py line
+#   <tag>_bench.json                   the full bench.py line (--full)
 #   <tag>_bench_kernel_stats.csv       rocprofv3 --kernel-trace --stats of the same command (no CPU baseline)
 #   <tag>_inflight1_kernel_stats.csv   the same with one scene in flight
 #   <tag>_{bench,inflight1,planned,graph}_concurrency.json   union of kernel intervals / wall of those traces (+ --forward-mode planned / graph)
@@ -16,7 +16,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $R
 O=$R/gpurun_out/$TAG
 mkdir -p $O
-timeout 600 python bench.py 2> $O/bench.err | grep "^{" > $O/${TAG}_bench.json; tail -1 $O/${TAG}_bench.json | cut -c1-200
+timeout 600 python bench.py --full 2> $O/bench.err | grep "^{" > $O/${TAG}_bench.json; tail -1 $O/${TAG}_bench.json | cut -c1-200
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python bench.py --no-extras --min-seconds 3 > $O/kt.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt1 -- python bench.py --no-extras --inflight 1 --min-seconds 3 > $O/kt1.log 2>&1
 PBN_TRACE_JSON=$O/${TAG}_bench_concurrency.json python scripts/analyze_trace.py $(find $O/kt -name "*kernel_trace.csv" | head -1) > $O/${TAG}_bench_concurrency.txt 2>&1; head -3 $O/${TAG}_bench_concurrency.txt

@@ -11,7 +11,7 @@ python -m pytest tests/test_train_gpu.py -m gpu -q -x -s > $O/test_train.log 2>&
 for fam in ${FAMS:-0 2 1}; do
   PBN_CONV_FAMILY=$fam python scripts/probe_ops.py > $O/probe_ops_fam$fam.log 2>&1
   grep "total" $O/probe_ops_fam$fam.log | tr '\n' ' '; echo " <- family $fam"
-  PBN_CONV_FAMILY=$fam python bench.py --no-extras --steps 40 --repeats 3 > $O/bench_fam$fam.json 2>$O/bench_fam$fam.err
+  PBN_CONV_FAMILY=$fam python bench.py --full --no-extras --steps 40 --repeats 3 > $O/bench_fam$fam.json 2>$O/bench_fam$fam.err
   python - <<PY
 import json
 d=json.loads(open("$O/bench_fam$fam.json").read().strip().splitlines()[-1])

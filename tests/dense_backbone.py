@@ -14,6 +14,11 @@ MinkowskiEngine is the sparse generalisation of exactly these dense operators):
   1x1                   F.conv3d(kernel 1)
   BatchNorm             F.batch_norm over the ACTIVE sites (train) or with running statistics (eval)
 
+conv3d / conv_transpose3d below state F.conv3d / F.conv_transpose3d as one channel product per kernel tap on strided views of
+the grid.  torch's CPU convolution picks a host-specific oneDNN kernel; on one host the comparison with the oracle failed by
+0.5 exactly on the layers with 24-34 input and 32 output channels, so the statement uses plain tensor products, which
+compute the same on every host.
+
 Follows /root/reference/network/Mink.py:291-354 (forward wiring), :75-107 (_make_layer), :218-288 (constructors).
 Coordinates must be shifted so that every coordinate is >= 0 and the shift is a multiple of 16 (stride alignment)."""
 import numpy as np
@@ -33,6 +38,35 @@ def _w3t(kernel, K):
     """[K^3, Ci, Co] -> conv_transpose3d weight [Ci, Co, X, Y, Z]."""
     ci, co = kernel.shape[1], kernel.shape[2]
     return kernel.view(K, K, K, ci, co).permute(3, 4, 2, 1, 0).contiguous()
+
+
+def conv3d(x, weight, stride=1, padding=0):
+    """F.conv3d(x, weight, stride=stride, padding=padding): weight [Co, Ci, X, Y, Z], cross-correlation."""
+    co, ci, kx, ky, kz = weight.shape
+    if padding:
+        x = F.pad(x, (padding,) * 6)
+    B, _, X, Y, Z = x.shape
+    ox, oy, oz = (X - kx) // stride + 1, (Y - ky) // stride + 1, (Z - kz) // stride + 1
+    out = x.new_zeros(B, co, ox, oy, oz)
+    for i in range(kx):
+        for j in range(ky):
+            for k in range(kz):
+                v = x[:, :, i:i + stride * (ox - 1) + 1:stride, j:j + stride * (oy - 1) + 1:stride, k:k + stride * (oz - 1) + 1:stride]
+                out += torch.einsum("bcxyz,dc->bdxyz", v, weight[:, :, i, j, k])
+    return out
+
+
+def conv_transpose3d(x, weight, stride=1):
+    """F.conv_transpose3d(x, weight, stride=stride): weight [Ci, Co, X, Y, Z]."""
+    ci, co, kx, ky, kz = weight.shape
+    B, _, X, Y, Z = x.shape
+    out = x.new_zeros(B, co, (X - 1) * stride + kx, (Y - 1) * stride + ky, (Z - 1) * stride + kz)
+    for i in range(kx):
+        for j in range(ky):
+            for k in range(kz):
+                out[:, :, i:i + stride * (X - 1) + 1:stride, j:j + stride * (Y - 1) + 1:stride, k:k + stride * (Z - 1) + 1:stride] += \
+                    torch.einsum("bcxyz,cd->bdxyz", x, weight[:, :, i, j, k])
+    return out
 
 
 class DenseScene(object):
@@ -82,8 +116,8 @@ def bn_dense(x, mask, sd, prefix, training, eps=1e-5):
 
 def conv_same(x, kernel, K):
     if kernel.dim() == 2:
-        return F.conv3d(x, kernel.t().contiguous().view(kernel.shape[1], kernel.shape[0], 1, 1, 1))
-    return F.conv3d(x, _w3(kernel, K), padding=K // 2)
+        return conv3d(x, kernel.t().contiguous().view(kernel.shape[1], kernel.shape[0], 1, 1, 1))
+    return conv3d(x, _w3(kernel, K), padding=K // 2)
 
 
 def basic_block_dense(x, mask, sd, prefix, training):
@@ -112,11 +146,11 @@ def minkunet_dense(sd, arch, feats, coords, extent, training=False, taps=None):
         return x
 
     def down(x, cname, bname, s):
-        out = F.conv3d(x, _w3(sd[cname + ".kernel"], 2), stride=2) * M[2 * s]
+        out = conv3d(x, _w3(sd[cname + ".kernel"], 2), stride=2) * M[2 * s]
         return torch.relu(bn_dense(out, M[2 * s], sd, bname, training))
 
     def up(x, cname, bname, s):
-        out = F.conv_transpose3d(x, _w3t(sd[cname + ".kernel"], 2), stride=2) * M[s // 2]
+        out = conv_transpose3d(x, _w3t(sd[cname + ".kernel"], 2), stride=2) * M[s // 2]
         return torch.relu(bn_dense(out, M[s // 2], sd, bname, training))
 
     x = sc.scatter(feats.detach().cpu().float())

@@ -1,5 +1,5 @@
 """CPU tier: oracle/sparse_ref.py against the independent DENSE statement of the backbone (tests/dense_backbone.py:
-F.conv3d / F.conv_transpose3d / batch_norm on a densified grid, no coordinate or kernel maps).  Narrows the
+conv3d / conv_transpose3d / batch_norm on a densified grid, no coordinate or kernel maps).  Narrows the
 "parity unpinned" gap of the MinkowskiEngine boundary: the oracle's conventions C1-C5, C7, C8 (offset order, weight
 layout, even kernels not centred, transposed map, BN on active rows) agree with the dense operators MinkowskiEngine
 generalises.  Layers of /root/reference/network/Mink.py:221-288, wiring :291-354."""
@@ -71,14 +71,14 @@ def test_strided_down_and_transposed_up_all_levels():
         assert int(sc.mask[2 * s].sum()) == len(coarse), "strided coordinate set == max-pooled occupancy"
         # down: oracle rows vs dense conv3d(stride 2) sampled at the oracle's coarse coordinates
         got = R.conv(x, w, cm.get_map(s, 2 * s, 2), len(coarse))
-        dn = torch.nn.functional.conv3d(grid, D._w3(w, 2), stride=2)
+        dn = D.conv3d(grid, D._w3(w, 2), stride=2)
         cc = coarse.astype(np.int64).copy()
         cc[:, 1:] += shift[None, :]
         _close(got, sc.rows_at(dn, cc, 2 * s), "k2s2 down @%d" % s)
         # up: the coarse features back onto the fine set
         wt = torch.randn(8, 8, 8, generator=g) / 8
         got_up = R.conv_transpose(got, wt, cm.get_map(s, 2 * s, 2), len(fine))
-        upg = torch.nn.functional.conv_transpose3d(dn * sc.mask[2 * s], D._w3t(wt, 2), stride=2)
+        upg = D.conv_transpose3d(dn * sc.mask[2 * s], D._w3t(wt, 2), stride=2)
         fc = fine.astype(np.int64).copy()
         fc[:, 1:] += shift[None, :]
         _close(got_up, sc.rows_at(upg, fc, s), "k2s2 transposed up @%d" % (2 * s))

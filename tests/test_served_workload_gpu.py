@@ -4,6 +4,8 @@ forwards.  In fp32 the merged forward equals the single ones (tests/test_batched
 kernel family / tile shape than the same level of a single scene, so the 16-bit contract of tests/test_bench_workload_gpu.py
 applies: the same semantic predictions, the same NUMBER of proposals per scene, proposal membership differing on at most
 BF16_MEMBERSHIP_BOUND of the rows, scores within BF16_SCORE_TOL; and the merged run is bit-identical run to run."""
+import threading
+
 import numpy as np
 import pytest
 import torch
@@ -17,6 +19,22 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 BF16_MEMBERSHIP_BOUND = 1e-3      # fraction of a scene's proposal rows (tests/test_bench_workload_gpu.py)
 BF16_SCORE_TOL = 3e-3
+
+
+class _GatedServer(SceneServer):
+    """A SceneServer whose workers take nothing from the queue until `open()`: the scenes submitted before are all WAITING when
+    the worker looks, so the merge does not depend on whether the worker thread wakes between two `submit` calls."""
+
+    def __init__(self, *a, **kw):
+        self._gate = threading.Event()
+        super().__init__(*a, **kw)
+
+    def open(self):
+        self._gate.set()
+
+    def _take(self):
+        self._gate.wait()
+        return super()._take()
 
 
 def _sets(res):
@@ -41,8 +59,9 @@ def test_four_bench_scenes_through_the_serving_front_bf16():
             singles.append(model(sc["feat_voxel"], sc["xyz_voxel"], sc["xyz_original"], sc["v2p_index"], None, 1, "test", teacher=t, n_batch=1))
     runs = []
     for _ in range(2):
-        srv = SceneServer(model, max_batch=4, forwards_in_flight=1)
+        srv = _GatedServer(model, max_batch=4, forwards_in_flight=1)
         futs = [srv.submit(sc, t) for sc, t, _ in scenes]
+        srv.open()
         runs.append([f.result(timeout=600) for f in futs])
         assert srv.forwards == 1 and srv.scenes == 4, "the four waiting scenes were merged into one forward"
         srv.close()
