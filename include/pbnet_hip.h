@@ -631,6 +631,55 @@ int pbn_unet_train_backward(const pbn_train_op* ops, int n_ops, const pbn_unet_b
                             float* param_grads, void* dinput, int ld_dinput, int dtype, void* splitk_ws, size_t splitk_bytes,
                             void* bn_ws, size_t bn_ws_bytes, void* wgrad_ws, size_t wgrad_ws_bytes, pbn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Batch construction (csrc/augment.hip): trainMerge / valMerge of datasets/scannetv2/dataset_preprocess.py:178-385.
+ * Rows of a batch form one range; a unit (one dataAugment call) and a scene (primary + mix-up partner) are contiguous
+ * row segments given by int32 offsets [n+1].  ext = double[n,6] (min xyz, max xyz).  workspace: pbn_aug_workspace_bytes
+ * (n_units or n_scenes).  max_*_rows sizes the grid only.
+ * ------------------------------------------------------------------------------------------------------------ */
+int pbn_aug_chunks(int n_rows);
+size_t pbn_aug_workspace_bytes(int n_segments);
+/* out = ((pre_min ? f32(x - f32 min) : x) @ mats[u]) - its min, times scale[u] where has_scale[u]; ext = extent of out. */
+int pbn_aug_affine(const float* xyz, const int32_t* unit_off, int n_units, int max_unit_rows, const int32_t* pre_min,
+                   const double* mats, const double* scale, const int32_t* has_scale, double* out, double* ext,
+                   void* workspace, pbn_stream_t stream);
+/* One elastic pass (gran, mag) on the units of desc int32[n_el,5] = (unit, b0, b1, b2, first float of its 3 grids):
+ * 6 box-blur passes of the float32 grids in noise (tmp: the same size; both are overwritten), then
+ * x += RegularGridInterpolator(g)(x) * mag; ext = extent per unit after the pass. */
+int pbn_aug_elastic(double* xyz, const int32_t* unit_off, int n_units, int max_unit_rows, const int32_t* desc, int n_el,
+                    int total_cells, float* noise, float* tmp, int gran, double mag, double* ext, void* workspace,
+                    pbn_stream_t stream);
+/* x -= ext min for the units with flags[u] != 0. */
+int pbn_aug_sub_min(double* xyz, const int32_t* unit_off, int n_units, int max_unit_rows, const int32_t* flags,
+                    const double* ext, pbn_stream_t stream);
+/* The crop loop of trainMerge (5 tries of crop(), each up to 17 shrink levels) for scenes with mode 0 (mode 1: keep every
+ * point).  triples double[n_scenes,85,3] consumed in order (n_triples valid per scene), levels double[17,3] the full_scale
+ * of each shrink.  One launch pair per try; state int32[n_scenes,8] (done, next triple, triples used, last try's start,
+ * its level, success, error, tries); counts int32[5,n_scenes,17].  ext_pre = extent before, ext_post = after the
+ * offset, over all points. */
+int pbn_aug_crop(const double* xyz, const int32_t* scene_off, int n_scenes, int max_scene_rows, const int32_t* mode,
+                 const double* triples, const int32_t* n_triples, const double* levels, int max_crop_p, int min_crop_p,
+                 int32_t* counts, int32_t* state, double* ext_pre, double* ext_post, void* workspace, pbn_stream_t stream);
+/* Mask + compaction in input order (xyz - ext_post min, f32(rgb + shift[unit]) | nl, sem) and the instance relabelling
+ * loop; labels of unit u are shifted by ins_shift[u] (-100 stays).  label_map / present: int32[n_labels]
+ * (label_off[n_scenes+1]), scene_i32: int32[2*n_scenes], scan: int32[pbn_aug_chunks(n_rows)+1].
+ * scene_info int32[n_scenes,4] = (rows kept, instance_num, first output row, 0). */
+int pbn_aug_compact(const double* xyz, const float* rgb, const float* nl, const int64_t* sem, const int32_t* ins,
+                    const double* shift, const int32_t* ins_shift, const int32_t* unit_off, int n_units,
+                    const int32_t* scene_off, int n_scenes, const int32_t* mode, const double* triples, const double* levels,
+                    const int32_t* state, const double* ext_pre, const double* ext_post, const int32_t* label_off,
+                    int32_t* label_map, int32_t* present, int32_t* scene_i32, int32_t* scan, double* xyz_out,
+                    float* feat_out, int64_t* sem_out, int32_t* label_out, int32_t* scene_info, int n_rows, int n_labels,
+                    pbn_stream_t stream);
+/* getInstanceInfo: per instance mean / min / max (float64, fixed-order reduction) and point count; inst_info f32[n,9]
+ * (-100 outside an instance), ins = label + inst_off[scene] (-100 stays).  out_start / inst_start: [n_scenes+1]. */
+int pbn_aug_instances(const double* xyz, const int32_t* label, const int32_t* out_start, int n_scenes,
+                      const int32_t* inst_start, const int32_t* inst_off, int n_inst, int n_rows, int32_t* pointnum,
+                      float* stats, float* inst_info, int64_t* ins, pbn_stream_t stream);
+/* coords int32[n,4] = (scene, floor(xyz / voxel_size)) of the float64 coordinates; xyz_f32 = float32(xyz). */
+int pbn_aug_quantize(const double* xyz, const int32_t* out_start, int n_scenes, int n_rows, double voxel_size,
+                     int32_t* coords, float* xyz_f32, pbn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

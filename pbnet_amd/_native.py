@@ -191,6 +191,20 @@ SIGNATURES = {
                                        ctypes.POINTER(c_i32), c_vp, c_int, ctypes.POINTER(ctypes.c_void_p), c_vp,
                                        ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), c_vp, c_size,
                                        c_int, c_vp, c_size, c_vp, ctypes.POINTER(ctypes.c_float)]),
+    "pbn_aug_chunks": (c_int, [c_int]),
+    "pbn_aug_workspace_bytes": (c_size, [c_int]),
+    "pbn_aug_affine": (c_int, [c_f32p, c_i32p, c_int, c_int, c_i32p, c_vp, c_vp, c_i32p, c_vp, c_vp, c_vp, c_vp]),
+    "pbn_aug_elastic": (c_int, [c_vp, c_i32p, c_int, c_int, c_i32p, c_int, c_int, c_f32p, c_f32p, c_int, ctypes.c_double, c_vp,
+                                c_vp, c_vp]),
+    "pbn_aug_sub_min": (c_int, [c_vp, c_i32p, c_int, c_int, c_i32p, c_vp, c_vp]),
+    "pbn_aug_crop": (c_int, [c_vp, c_i32p, c_int, c_int, c_i32p, c_vp, c_i32p, c_vp, c_int, c_int, c_i32p, c_i32p, c_vp, c_vp,
+                             c_vp, c_vp]),
+    "pbn_aug_compact": (c_int, [c_vp, c_f32p, c_f32p, c_vp, c_i32p, c_vp, c_i32p, c_i32p, c_int, c_i32p, c_int, c_i32p, c_vp,
+                                c_vp, c_i32p, c_vp, c_vp, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_vp, c_f32p, c_vp, c_i32p,
+                                c_i32p, c_int, c_int, c_vp]),
+    "pbn_aug_instances": (c_int, [c_vp, c_i32p, c_i32p, c_int, c_i32p, c_i32p, c_int, c_int, c_i32p, c_f32p, c_f32p, c_vp,
+                                  c_vp]),
+    "pbn_aug_quantize": (c_int, [c_vp, c_i32p, c_int, c_int, ctypes.c_double, c_i32p, c_f32p, c_vp]),
 }
 
 PBN_OK, PBN_ERR_ARG, PBN_ERR_WORKSPACE, PBN_ERR_HIP, PBN_ERR_RANGE, PBN_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5

@@ -5,7 +5,8 @@ then `ME.utils.sparse_collate`.  Here the scenes of a batch are voxelised togeth
 (the batch index is part of the key, survivors keep the input order, i.e. scene-major with first occurrence inside a
 scene -- exactly what quantising scene by scene and concatenating yields).  SURVEY.md 8(f) rank 2.
 
-Dataset I/O, augmentation and instance bookkeeping stay with the caller (out of scope)."""
+Dataset I/O stays with the caller.  The whole merge -- augmentation, mix-up, the crop loop, instance relabelling and
+instance statistics, then this voxelisation -- runs on the device in `pbnet_amd/loader.py` (DeviceMerge)."""
 import numpy as np
 import torch
 
