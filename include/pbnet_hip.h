@@ -51,7 +51,9 @@ int pbn_last_hip_error(void);
  *                       1: classes may be mixed inside a segment ("component x class" rule, cluster.cu/binary.cu:206)
  *  cluster_id [n]  i32 out  global ids across segments (cluster.cu:91-93,108), -1 = unassigned
  *  cluster_num[n_seg] i32 out
- *  den        [n]  i32 out  neighbour count EXCLUDING self (binary.cu:148); the Python op returns den+1
+ *  den        [n]  i32 out  neighbour count EXCLUDING self (binary.cu:148); the Python op returns den+1.
+ *                       With general_sem bit 2 set: min(that count, min_pts) -- exact wherever it decides
+ *                       den >= min_pts, which is all the grouping reads; the count stops once it is reached
  *  centers    [3*n] f32 out capacity; first 3*C valid (cluster.cu:112-114 resizes instead)
  *  clt_sem    [n]  i32 out  capacity; first C valid (cluster.cu:116-118)
  *  n_clusters [1]  i32 out  C, in DEVICE memory (no host sync inside)
@@ -69,7 +71,8 @@ int pbn_binary_cluster(const float* off_xyz, const float* org_xyz, const int32_t
                        int n_points, int n_segments, float radius, int min_pts, float para_f, int nv_flag,
                        int general_sem /* bit 0: general (mixed-class) rule; bit 1: n_points is a CAPACITY -- the points that
                        exist are the first sum(seg_len) rows, a count that stays on the device (capacity-planned forward:
-                       no host read-back between class selection and grouping) */, int32_t* cluster_id, int32_t* cluster_num, int32_t* den, float* centers,
+                       no host read-back between class selection and grouping); bit 2: den is not needed beyond
+                       den >= min_pts (den = min(count, min_pts), every other output unchanged) */, int32_t* cluster_id, int32_t* cluster_num, int32_t* den, float* centers,
                        int32_t* clt_sem, int32_t* n_clusters, int32_t* member_start, int32_t* member_idx,
                        void* workspace, size_t workspace_bytes, pbn_stream_t stream);
 

@@ -220,10 +220,21 @@ __device__ __forceinline__ int group_max(int v) {
     for (int o = 1; o < NB_Q; o <<= 1) v = max(v, __shfl_xor(v, o, 64));
     return v;
 }
-__global__ __launch_bounds__(TPB) void k_count(const float4* __restrict__ spt, const int* __restrict__ sseg, NRef n_ref,
-                                              float inv_cell, float r2, const unsigned long long* __restrict__ hkeys,
-                                              unsigned hmask, const int* __restrict__ hstart,
-                                              const int* __restrict__ hcount, int* __restrict__ den) {
+// the 125 cells of the 5x5x5 neighbourhood ordered by Chebyshev ring: the own cell, the 26 around it, the outer shell of 98.
+// entry = (dx+2) | (dy+2) << 3 | (dz+2) << 6.  k_count walks in this order, so that the HP-only count settles dense points
+// on the cells that hold most of their neighbours.
+__constant__ unsigned short c_nb_ring[125] = {
+    146, 73,  74,  75,  81,  82,  83,  89,  90,  91,  137, 138, 139, 145, 147, 153, 154, 155, 201, 202, 203, 209, 210, 211, 217,
+    218, 219, 0,   1,   2,   3,   4,   8,   9,   10,  11,  12,  16,  17,  18,  19,  20,  24,  25,  26,  27,  28,  32,  33,  34,
+    35,  36,  64,  65,  66,  67,  68,  72,  76,  80,  84,  88,  92,  96,  97,  98,  99,  100, 128, 129, 130, 131, 132, 136, 140,
+    144, 148, 152, 156, 160, 161, 162, 163, 164, 192, 193, 194, 195, 196, 200, 204, 208, 212, 216, 220, 224, 225, 226, 227, 228,
+    256, 257, 258, 259, 260, 264, 265, 266, 267, 268, 272, 273, 274, 275, 276, 280, 281, 282, 283, 284, 288, 289, 290, 291, 292};
+
+__global__ __launch_bounds__(TPB) void k_count(const float4* __restrict__ spt, const int* __restrict__ sseg,
+                                              const int* __restrict__ sslot, NRef n_ref, float inv_cell, float r2,
+                                              const unsigned long long* __restrict__ hkeys, unsigned hmask,
+                                              const int* __restrict__ hstart, const int* __restrict__ hcount, int min_pts,
+                                              int need_den, int* __restrict__ den) {
     // The 8 points of a wave are neighbours in the cell-sorted slab: in 82 % of the waves (90 % of the tests) they share a
     // cell, hence the 125 candidate ranges.  Then the wave loads every candidate ONCE -- 64 per load, one per lane,
     // through a per-wave LDS line, the next 64 already in flight -- and each point's 8 lanes test them from there instead
@@ -232,6 +243,11 @@ __global__ __launch_bounds__(TPB) void k_count(const float4* __restrict__ spt, c
     // 30.  Also measured, none of them better: packed fp32 tests (298), a per-cell table of the 125 neighbour slots (269, + 16
     // to build and 500 B of workspace per point), cell-by-cell passes so that every test takes the shared path (378), a
     // cell-tiled kernel with candidates through the scalar cache (477).
+    // Round 7: a trusted own cell is credited with its population, no test (any two of its points are within r, as
+    // k_union and k_border already rely on); a clamped border cell keeps the pairwise tests.  need_den == 0 (HP-only mode,
+    // what PBNet.forward asks for): the walk goes ring by ring and a point is settled once count - 1 >= min_pts -- the
+    // wave stops when all its points are (checked after every 64-candidate chunk and every cell of the shared path), a lane
+    // group of the per-group walk stops by itself; den = min(exact count, min_pts), which is all k_tag_hp reads.
     __shared__ float4 s_cand[TPB / 64][64];
     const int n = n_ref.get();
     if (n <= 0) return;
@@ -249,14 +265,20 @@ __global__ __launch_bounds__(TPB) void k_count(const float4* __restrict__ spt, c
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int gbase = lane & ~(NB_Q - 1);
     float4* line = s_cand[wave];
-    int cnt = 0;
     const int cx = cell_coord(me.x, inv_cell), cy = cell_coord(me.y, inv_cell), cz = cell_coord(me.z, inv_cell);
-    constexpr int W = 2 * CELL_R + 1;
-    for (int r = 0; r < W * W * W; r += NB_Q) {
+    const bool own_trusted = cell_trusted(cx, cy, cz);
+    int cnt = (own_trusted && q == 0) ? hcount[sslot[p]] : 0;   // self included, as in the pairwise count
+    // settled lane groups (group-uniform); in the exact mode only the idle groups of the straddling wave
+    bool gdone = !live;
+    if (!need_den) gdone = gdone || group_sum(cnt) > min_pts;
+    bool wdone = __all(gdone);
+    constexpr int NCELL = (2 * CELL_R + 1) * (2 * CELL_R + 1) * (2 * CELL_R + 1);
+    for (int r = 0; r < NCELL && !wdone; r += NB_Q) {
         const int c = r + q;
         int slot = -1, beg = 0, end = 0;
-        if (c < W * W * W) {
-            const int dz = c / (W * W) - CELL_R, dy = (c / W) % W - CELL_R, dx = c % W - CELL_R;
+        if (c < NCELL && !gdone && !(c == 0 && own_trusted)) {
+            const int o = c_nb_ring[c];
+            const int dx = (o & 7) - CELL_R, dy = ((o >> 3) & 7) - CELL_R, dz = (o >> 6) - CELL_R;
             slot = hash_lookup(hkeys, hmask, pack_key(seg, cx + dx, cy + dy, cz + dz));
             if (slot >= 0) { beg = hstart[slot]; end = beg + hcount[slot]; }
         }
@@ -264,7 +286,7 @@ __global__ __launch_bounds__(TPB) void k_count(const float4* __restrict__ spt, c
         const bool same = beg == __shfl(beg, q, 64) && end == __shfl(end, q, 64);
         if (__all(same)) {
 #pragma unroll 1
-            for (int k = 0; k < NB_Q; ++k) {
+            for (int k = 0; k < NB_Q && !wdone; ++k) {
                 const int bk = __shfl(beg, k, 64), ek = __shfl(end, k, 64);   // wave-uniform
                 float4 nxt = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (bk + lane < ek) nxt = spt[bk + lane];
@@ -280,13 +302,18 @@ __global__ __launch_bounds__(TPB) void k_count(const float4* __restrict__ spt, c
                             cnt += (sqdist(me.x, me.y, me.z, v.x, v.y, v.z) <= r2) ? 1 : 0;
                         }
                     }
+                    if (!need_den) {
+                        gdone = gdone || group_sum(cnt) > min_pts;
+                        wdone = __all(gdone);
+                        if (wdone) break;
+                    }
                 }
             }
         } else {
 #pragma unroll
             for (int k = 0; k < NB_Q; ++k) {
                 const int sk = __shfl(slot, gbase + k, 64);
-                if (sk < 0) continue;
+                if (sk < 0 || gdone) continue;
                 const int bk = __shfl(beg, gbase + k, 64), ek = __shfl(end, gbase + k, 64);
                 int j = bk + q;
                 for (; j + NB_Q < ek; j += 2 * NB_Q) {  // two independent loads in flight
@@ -298,11 +325,13 @@ __global__ __launch_bounds__(TPB) void k_count(const float4* __restrict__ spt, c
                     const float4 q0 = spt[j];
                     cnt += (sqdist(me.x, me.y, me.z, q0.x, q0.y, q0.z) <= r2) ? 1 : 0;
                 }
+                if (!need_den) gdone = group_sum(cnt) > min_pts;
             }
+            wdone = __all(gdone);
         }
     }
     cnt = group_sum(cnt);
-    if (live && q == 0) den[__float_as_int(me.w)] = cnt - 1;  // binary_cuda_functions.cu:88
+    if (live && q == 0) den[__float_as_int(me.w)] = need_den ? cnt - 1 : min(cnt - 1, min_pts);  // binary_cuda_functions.cu:88
 }
 
 // tag the HP flag into bit 31 of the index word of the sorted slab; init union-find parents
@@ -353,17 +382,32 @@ __device__ __forceinline__ int uf_union(int* __restrict__ parent, int a, int b) 
 //  * untrusted (clamped border) cells fall back to pairwise unions, each edge handled by its larger endpoint.
 // Every HP-HP edge (i,j) ends with find(i) == find(j): either both cells are trusted and chained to representatives
 // that some witness joined, or the pairwise fallback handled the edge itself.
+// Pass 1 is gated per cell (`unres`).  A representative marks its trusted cell A unresolved when, in pass 0, it meets
+// (a) an HP-bearing trusted cell B != A whose root differed from its own and in which it found no HP within r, or
+// (b) an untrusted cell that holds HPs.  Only the HPs of marked trusted cells (and of untrusted cells) walk in pass 1.
+// Coverage, for an HP-HP edge (i,j), i in cell A, j in cell B (the 5x5x5 neighbourhood depends on the cell only, so
+// the representative of A meets every cell that any HP of A meets):
+//  * A == B trusted: chained to the representative in pass 0;
+//  * A, B trusted, A != B: when the representative of A looked at B, the roots were equal (sets only ever merge, so
+//    they stay equal), or it witnessed an HP of B and joined the two sets, or neither -- then A is marked (a), i walks
+//    in pass 1 and either finds the roots equal or witnesses an HP of B within r (j is one) and joins them;
+//  * A or B untrusted: the larger endpoint joins the edge pairwise.  An endpoint in an untrusted cell walks in both
+//    passes; an endpoint i in a trusted A sees the untrusted B in pass 1 because A is marked (b).
+// Roots are minimum indices, so the components do not depend on which witness or which pass joined them.
+template <int PASS>
 __global__ __launch_bounds__(TPB) void k_union(const float4* __restrict__ spt, const int* __restrict__ sseg, NRef n_ref,
                                               float inv_cell, float r2, const unsigned long long* __restrict__ hkeys,
                                               unsigned hmask, const int* __restrict__ hstart,
                                               const int* __restrict__ hcount, int* parent,
-                                              const int* __restrict__ cell_rep, const int* __restrict__ sslot, int pass) {
+                                              const int* __restrict__ cell_rep, const int* __restrict__ sslot,
+                                              int* __restrict__ unres) {
+    constexpr int pass = PASS;
     const int n = n_ref.get();
     // pass 0: every HP chains to its cell representative; only the representatives (and points of untrusted cells)
     //         look across cells -- a few hundred threads do almost all merging without contention;
     // (k_compress flattens the forest in between)
-    // pass 1: every HP repeats the cross-cell search, which is now a cached parent compare for all merged pairs and
-    //         only does real work for the edges a representative could not witness.
+    // pass 1: the HPs of unresolved cells (see above) repeat the cross-cell search, which is now a cached parent compare
+    //         for all merged pairs and only does real work for the edges a representative could not witness.
     // NB_Q lanes share a point and split its 125 cells; each lane keeps its own cached root (the forest is the only
     // shared state and it is lock-free), which also shortens the serial chain of the few representatives of pass 0
     const long long t = (long long)blockIdx.x * TPB + threadIdx.x;
@@ -373,8 +417,11 @@ __global__ __launch_bounds__(TPB) void k_union(const float4* __restrict__ spt, c
     const int wi = __float_as_int(me.w);
     if (wi >= 0) return;  // LP: never expands (binary_cuda_functions.cu:209)
     const int i = wi & 0x7fffffff;
-    const int my_rep = cell_rep[sslot[p]];
+    const int my_slot = sslot[p];
     const bool own_trusted = cell_trusted(cell_coord(me.x, inv_cell), cell_coord(me.y, inv_cell), cell_coord(me.z, inv_cell));
+    if (pass == 1 && own_trusted && !unres[my_slot]) return;
+    const int my_rep = cell_rep[my_slot];
+    bool unresolved = false;
     int ri = (pass == 0) ? i : parent[i];
     if (pass == 0 && own_trusted) {
         if (my_rep != i) {  // chained; the representative does the rest
@@ -392,15 +439,26 @@ __global__ __launch_bounds__(TPB) void k_union(const float4* __restrict__ spt, c
             if (rep == ri || parent[rep] == ri) return;
             ri = uf_find(parent, ri);
             if (uf_find(parent, rep) == ri) return;
-            for (int j = beg; j < end; ++j) {
-                const float4 q = spt[j];
-                if (__float_as_int(q.w) < 0 && sqdist(me.x, me.y, me.z, q.x, q.y, q.z) <= r2) {
-                    ri = uf_union(parent, ri, __float_as_int(q.w) & 0x7fffffff);
-                    return;
+            // any HP within r is a witness: in pass 0, WIT candidates in flight at a time (a cell that holds none is read
+            // to its end, and this walk is the serial chain of the representatives that do the merging: 201 -> 162 us on
+            // the bench scene); pass 1 rarely gets here and keeps one (registers: occupancy of its 125-cell probes)
+            constexpr int WIT = PASS == 0 ? 8 : 1;
+            for (int j = beg; j < end; j += WIT) {
+                float4 c[WIT];
+#pragma unroll
+                for (int u = 0; u < WIT; ++u) c[u] = (j + u < end) ? spt[j + u] : make_float4(0.f, 0.f, 0.f, 0.f);  // w = 0: an LP
+#pragma unroll
+                for (int u = 0; u < WIT; ++u) {
+                    if (__float_as_int(c[u].w) < 0 && sqdist(me.x, me.y, me.z, c[u].x, c[u].y, c[u].z) <= r2) {
+                        ri = uf_union(parent, ri, __float_as_int(c[u].w) & 0x7fffffff);
+                        return;
+                    }
                 }
             }
+            unresolved = true;   // (a)
             return;
         }
+        unresolved = true;       // (b)
         for (int j = beg; j < end; ++j) {
             const float4 q = spt[j];
             const int wj = __float_as_int(q.w);
@@ -410,6 +468,8 @@ __global__ __launch_bounds__(TPB) void k_union(const float4* __restrict__ spt, c
             }
         }
     });
+    // one store after the walk: a store inside it would sit in the load counter of every later probe
+    if (pass == 0 && own_trusted && unresolved) unres[my_slot] = 1;   // only representatives of trusted cells get here
 }
 
 // flatten the forest between the two union passes: afterwards parent[i] is i's root for every HP
@@ -793,7 +853,7 @@ __global__ void k_member_tail(int* __restrict__ member_start, const int* __restr
 }
 
 struct Workspace {
-    int *seg_off, *seg_of_pt, *slot_of_pt, *hcount, *hstart, *hcursor, *sseg, *sslot, *cell_rep, *parent, *lab, *root, *semseed, *size,
+    int *seg_off, *seg_of_pt, *slot_of_pt, *hcount, *hstart, *hcursor, *unres, *sseg, *sslot, *cell_rep, *parent, *lab, *root, *semseed, *size,
         *keep, *newid, *lab2, *clt_seg, *last_assigned, *fsize, *noise_flag, *noise_pos, *noise_list, *scan_tmp,
         *scalars, *mstart_tmp;
     unsigned long long* scan_state[4];
@@ -812,12 +872,13 @@ unsigned hash_capacity(int n) {
 size_t carve(Carver& cv, Workspace& w, int n, int n_seg, int general) {
     const size_t N = (size_t)(n > 0 ? n : 1);
     w.hcap = hash_capacity(n);
-    // zero-filled block (one memset): scalars | hcount | hcursor | size | fsize
+    // zero-filled block (one memset): scalars | hcount | hcursor | unres | size | fsize
     w.scalars = cv.take<int>(64);
     for (int j = 0; j < 4; ++j)          // states of the four chained scans (zeroed with the block)
         w.scan_state[j] = cv.take<unsigned long long>(scan_chained_state_words((long long)(w.hcap > N ? w.hcap : N)));
     w.hcount = cv.take<int>(w.hcap);
     w.hcursor = cv.take<int>(w.hcap);
+    w.unres = cv.take<int>(w.hcap);
     w.size = cv.take<int>(N);
     w.fsize = cv.take<int>(N);
     w.zero_end = cv.off;
@@ -872,6 +933,7 @@ extern "C" int pbn_binary_cluster(const float* off_xyz, const float* org_xyz, co
     hipStream_t stream = (hipStream_t)stream_;
     const int general = flags & 1;
     const int capacity = (flags >> 1) & 1;   // n is a capacity; the points that exist are the first sum(seg_len) rows
+    const int need_den = !((flags >> 2) & 1);  // bit 2: den is only read as den >= min_pts (den = min(count, min_pts))
     if (n < 0 || n_seg < 0 || n_seg > 65535 || !(radius > 0.0f) || !n_clusters || (n_seg > 0 && !cluster_num))
         return PBN_ERR_ARG;
     if ((member_start == nullptr) != (member_idx == nullptr)) return PBN_ERR_ARG;
@@ -923,15 +985,15 @@ extern "C" int pbn_binary_cluster(const float* off_xyz, const float* org_xyz, co
     if (rc != PBN_OK) return rc;
     hipLaunchKernelGGL(k_cell_scatter, dim3(nb), dim3(TPB), 0, stream, off_xyz, nr, w.slot_of_pt, w.hstart, w.hcursor,
                        w.seg_of_pt, w.spt, w.sseg, w.sslot);
-    hipLaunchKernelGGL(k_count, dim3(cdiv((long long)n * NB_Q, TPB)), dim3(TPB), 0, stream, w.spt, w.sseg, nr, inv_cell, r2, w.hkeys, hmask,
-                       w.hstart, w.hcount, den);
+    hipLaunchKernelGGL(k_count, dim3(cdiv((long long)n * NB_Q, TPB)), dim3(TPB), 0, stream, w.spt, w.sseg, w.sslot, nr, inv_cell, r2,
+                       w.hkeys, hmask, w.hstart, w.hcount, min_pts, need_den, den);
     hipLaunchKernelGGL(k_tag_hp, dim3(nb), dim3(TPB), 0, stream, w.spt, nr, den, min_pts, w.parent, w.lab, w.sslot, w.cell_rep);
     const dim3 nbq(cdiv((long long)n * NB_Q, TPB));
-    hipLaunchKernelGGL(k_union, nbq, dim3(TPB), 0, stream, w.spt, w.sseg, nr, inv_cell, r2, w.hkeys, hmask,
-                       w.hstart, w.hcount, w.parent, w.cell_rep, w.sslot, 0);
+    hipLaunchKernelGGL(k_union<0>, nbq, dim3(TPB), 0, stream, w.spt, w.sseg, nr, inv_cell, r2, w.hkeys, hmask,
+                       w.hstart, w.hcount, w.parent, w.cell_rep, w.sslot, w.unres);
     hipLaunchKernelGGL(k_compress, dim3(nb), dim3(TPB), 0, stream, w.spt, nr, w.parent);
-    hipLaunchKernelGGL(k_union, nbq, dim3(TPB), 0, stream, w.spt, w.sseg, nr, inv_cell, r2, w.hkeys, hmask,
-                       w.hstart, w.hcount, w.parent, w.cell_rep, w.sslot, 1);
+    hipLaunchKernelGGL(k_union<1>, nbq, dim3(TPB), 0, stream, w.spt, w.sseg, nr, inv_cell, r2, w.hkeys, hmask,
+                       w.hstart, w.hcount, w.parent, w.cell_rep, w.sslot, w.unres);
     hipLaunchKernelGGL(k_flatten, dim3(nb), dim3(TPB), 0, stream, w.spt, nr, w.parent, sem, general, w.semseed, w.lab);
     hipLaunchKernelGGL(k_copy_i32, dim3(nb), dim3(TPB), 0, stream, w.lab, w.root, nr);
     if (general)

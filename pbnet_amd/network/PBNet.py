@@ -267,7 +267,8 @@ class PBNet(nn.Module):
                 self._last_sizes["points"] = int(m)
             mark("a7:select queued")
             with section("a7_16_grouping"):
-                res = pbnet_ops.cluster_device(ins_offseted, ins_orig, ins_sem, seg_len, self.radius, self.min_pts)
+                res = pbnet_ops.cluster_device(ins_offseted, ins_orig, ins_sem, seg_len, self.radius, self.min_pts,
+                                              need_den=False)
                 mark("a7:grouping queued")
                 # one read-back for the cluster table AND the first HEAD_CLUSTERS centres / member offsets (a scene has tens
                 # of clusters; a second read-back follows only when there are more)
@@ -482,7 +483,8 @@ class PBNet(nn.Module):
                                                                           s1["offset_pred_p"].detach(), n_pts)
         mark("a7:select queued")
         with section("a7_16_grouping"):
-            res = pbnet_ops.cluster_device(ins_off, ins_orig, ins_sem, seg_len, self.radius, self.min_pts, capacity=True)
+            res = pbnet_ops.cluster_device(ins_off, ins_orig, ins_sem, seg_len, self.radius, self.min_pts, capacity=True,
+                                          need_den=False)
             c_cap = min(FRONT_CLUSTER_CAP, n_pts)
             e_cap = 7 * c_cap
             ent = torch.empty(4 * e_cap + 1, **i32)                    # row_start (e_cap + 1) | member_start | scene | weight bits

@@ -232,7 +232,8 @@ class PlannedForward(object):
                                    N.ptr(seg_len), vp(cptr), st()), "pbn_class_gate")
         ins_ind, ins_orig, ins_off, ins_sem = stage_ops.select_points(sem_pred, class_base, block_hist, xyz, offset_p,
                                                                       int(cap.points))
-        res = pbnet_ops.cluster_device(ins_off, ins_orig, ins_sem, seg_len, m.radius, m.min_pts, capacity=True)
+        res = pbnet_ops.cluster_device(ins_off, ins_orig, ins_sem, seg_len, m.radius, m.min_pts, capacity=True,
+                                      need_den=False)
 
         _dbg("grouping done", counts)
         if _STOP == "grouping":
