@@ -683,6 +683,30 @@ int pbn_aug_instances(const double* xyz, const int32_t* label, const int32_t* ou
 int pbn_aug_quantize(const double* xyz, const int32_t* out_start, int n_scenes, int n_rows, double voxel_size,
                      int32_t* coords, float* xyz_f32, pbn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Mesh decode (csrc/mesh.hip): the per-vertex normals of datasets/scannetv2/decode_scannet.py:76-96 and the superpoints of
+ * lib/segmentator (csrc/segmentator.cpp:154-252 segment_mesh, :282-357 segment_point, main.py:17's unique relabel), float32
+ * operation by operation.  xyz / normals f32[V,3]; faces [F,3] and edges [E,2] are int32 (idx_i64 = 0) or int64 (1).
+ * workspace: pbn_mesh_workspace_bytes(mode, V, F for modes 0/1 or E for mode 2); 0 = sizes out of range.
+ * ------------------------------------------------------------------------------------------------------------ */
+enum { PBN_MESH_NORMALS = 0, PBN_MESH_SEGMENT = 1, PBN_MESH_SEGMENT_POINT = 2 };
+size_t pbn_mesh_workspace_bytes(int mode, int n_vertices, int n_elems);
+/* nl f32[V,3]: vertex_normal(xyz, faces); a face naming a vertex twice adds to it once, unreferenced vertices get 0.
+ * status int32[1] (device): 0, or 1 when an index lies outside [0, V) (nl is then undefined).  Asynchronous. */
+int pbn_mesh_vertex_normals(const float* xyz, int n_vertices, const void* faces, int faces_i64, int n_faces, float* nl,
+                            int32_t* status, void* workspace, size_t workspace_bytes, pbn_stream_t stream);
+/* sup int64[V]: segment_mesh(xyz, faces, k_thresh, seg_min_verts) relabelled to 0..S-1 in ascending root order; nl
+ * (optional) as pbn_mesh_vertex_normals.  Edges sort by (w, edge index), NaN weights last.  SYNCHRONISES the stream (the
+ * Felzenszwalb sweep runs on the host); PBN_ERR_RANGE when an index lies outside [0, V).  times_ms (optional, host
+ * float[7]): incidence, normals, weights, sort, read-back, host sweep, relabel. */
+int pbn_mesh_segment(const float* xyz, int n_vertices, const void* faces, int faces_i64, int n_faces, float k_thresh,
+                     int seg_min_verts, int64_t* sup, float* nl, void* workspace, size_t workspace_bytes, float* times_ms,
+                     pbn_stream_t stream);
+/* sup int64[V]: segment_point(xyz, normals, edges, k_thresh, seg_min_verts), as pbn_mesh_segment. */
+int pbn_mesh_segment_point(const float* xyz, const float* normals, int n_points, const void* edges, int edges_i64, int n_edges,
+                           float k_thresh, int seg_min_verts, int64_t* sup, void* workspace, size_t workspace_bytes,
+                           pbn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -205,6 +205,11 @@ SIGNATURES = {
     "pbn_aug_instances": (c_int, [c_vp, c_i32p, c_i32p, c_int, c_i32p, c_i32p, c_int, c_int, c_i32p, c_f32p, c_f32p, c_vp,
                                   c_vp]),
     "pbn_aug_quantize": (c_int, [c_vp, c_i32p, c_int, c_int, ctypes.c_double, c_i32p, c_f32p, c_vp]),
+    "pbn_mesh_workspace_bytes": (c_size, [c_int, c_int, c_int]),
+    "pbn_mesh_vertex_normals": (c_int, [c_f32p, c_int, c_vp, c_int, c_int, c_f32p, c_i32p, c_vp, c_size, c_vp]),
+    "pbn_mesh_segment": (c_int, [c_f32p, c_int, c_vp, c_int, c_int, c_float, c_int, c_vp, c_f32p, c_vp, c_size,
+                                 ctypes.POINTER(ctypes.c_float), c_vp]),
+    "pbn_mesh_segment_point": (c_int, [c_f32p, c_f32p, c_int, c_vp, c_int, c_int, c_float, c_int, c_vp, c_vp, c_size, c_vp]),
 }
 
 PBN_OK, PBN_ERR_ARG, PBN_ERR_WORKSPACE, PBN_ERR_HIP, PBN_ERR_RANGE, PBN_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5

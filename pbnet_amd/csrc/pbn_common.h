@@ -114,6 +114,13 @@ int coords_number_first(const int32_t* slot_of_row, const int32_t* table_vals, c
 size_t pyramid_scratch_bytes(int n);
 int coords_prepare_sorted(const int32_t* coords, const int32_t* n_dev, int n, int want_k5, int x_fastest, void* arena,
                           const pbn_prepare_layout* P, hipStream_t stream);
+// pyramid.hip: its LSD radix sort (k_sort_pass's digit pass) for 32-bit keys in the low half of u64 keys, values carried;
+// stable, so ties keep the input order.  ghist: RADIX_U32_PASSES x 2048 digit histograms (digit p = key >> 11p & 2047),
+// filled by the caller; the result lands in keys_b / vals_b.  A chained scan that gives up ORs 8 into *status.
+constexpr int RADIX_U32_DIGIT_BITS = 11, RADIX_U32_PASSES = 3;
+size_t radix_sort_u32_scratch_bytes(int n);
+int radix_sort_u32(unsigned long long* keys_a, unsigned long long* keys_b, int32_t* vals_a, int32_t* vals_b, int n,
+                   const unsigned* ghist, int32_t* status, void* scratch, size_t scratch_bytes, hipStream_t stream);
 // prepare.hip: device radix sort of (key, value) pairs; temp from sort_pairs_temp_bytes(n)
 size_t sort_pairs_temp_bytes(int n);
 int sort_pairs_u64_i32(const uint64_t* keys_in, uint64_t* keys_out, const int32_t* vals_in, int32_t* vals_out, int n,

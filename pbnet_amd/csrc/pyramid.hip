@@ -380,6 +380,30 @@ __global__ __launch_bounds__(TPB) void k_sort_pass(const u64* __restrict__ kin, 
     }
 }
 
+// The same digit pass for a caller's 32-bit keys (radix_sort_u32 below): three 11-bit digits, tickets in words of its own
+__global__ __launch_bounds__(TPB) void k_sort_pass_u32(const u64* __restrict__ kin, u64* __restrict__ kout,
+                                                      const int* __restrict__ vin, int* __restrict__ vout, int n, int pass,
+                                                      int* __restrict__ words, int* __restrict__ status,
+                                                      const unsigned* __restrict__ ghist, u64* __restrict__ state) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sort_smem[];      // SORT_LDS_BYTES
+    __shared__ unsigned s_wtot[2][TPB / 64];
+    __shared__ int s_blk;
+    SortShared sh;
+    sh.s_key = reinterpret_cast<u64*>(sort_smem);
+    sh.s_val = reinterpret_cast<int*>(sh.s_key + SORT_TILE);
+    sh.s_cnt = reinterpret_cast<unsigned (*)[RADIX]>(sh.s_val + SORT_TILE);
+    sh.s_base = &sh.s_cnt[TPB / 64][0];
+    sh.s_local = sh.s_base + RADIX;
+    if (n <= 0) return;
+    const int tid = threadIdx.x;
+    if (tid == 0) s_blk = atomicAdd(&words[PL_TICKET0 + pass], 1);
+    for (int e = tid; e < (TPB / 64) * RADIX; e += TPB) (&sh.s_cnt[0][0])[e] = 0u;
+    __syncthreads();
+    const int blk = s_blk;
+    if ((long long)blk * SORT_TILE >= n) return;
+    sort_pass_body<8>(kin, kout, vin, vout, n, pass, words, status, ghist, state, sh, blk, s_wtot);
+}
+
 // ---- 3. all levels from the sorted rows ------------------------------------------------------------------------------------
 struct PyrOut {
     int* coords[5];
@@ -762,6 +786,33 @@ int coords_prepare_sorted(const int32_t* coords, const int32_t* n_dev, int n, in
             hipLaunchKernelGGL(k_maps_down, dim3((unsigned)bl), dim3(TPB), 0, st, dj);
         }
     }
+    PBN_LAUNCH_CHECK();
+    return PBN_OK;
+}
+
+static_assert(RADIX_U32_DIGIT_BITS == RADIX_BITS, "radix_sort_u32 runs sort_pass_body<8>: 11-bit digits");
+
+size_t radix_sort_u32_scratch_bytes(int n) {
+    const size_t sort_blocks = (size_t)cdiv(n > 0 ? n : 1, SORT_TILE);
+    return align_up(PL_WORDS * sizeof(int), 256) + align_up((size_t)RADIX_U32_PASSES * sort_blocks * (RADIX / 2) * sizeof(u64), 256);
+}
+
+int radix_sort_u32(unsigned long long* keys_a, unsigned long long* keys_b, int32_t* vals_a, int32_t* vals_b, int n,
+                   const unsigned* ghist, int32_t* status, void* scratch, size_t scratch_bytes, hipStream_t st) {
+    if (n <= 0) return PBN_OK;
+    if (scratch_bytes < radix_sort_u32_scratch_bytes(n)) return PBN_ERR_WORKSPACE;
+    const size_t sort_blocks = (size_t)cdiv(n, SORT_TILE);
+    int* words = (int*)scratch;
+    u64* state = (u64*)((char*)scratch + align_up(PL_WORDS * sizeof(int), 256));
+    const int frc = fill_bytes(scratch, 0, radix_sort_u32_scratch_bytes(n), st);
+    if (frc != PBN_OK) return frc;
+    static const bool lds_attr = (hipFuncSetAttribute((const void*)k_sort_pass_u32, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                      (int)SORT_LDS_BYTES) == hipSuccess);
+    if (!lds_attr) return PBN_ERR_HIP;
+    for (int p = 0; p < RADIX_U32_PASSES; ++p)
+        hipLaunchKernelGGL(k_sort_pass_u32, dim3((unsigned)sort_blocks), dim3(TPB), SORT_LDS_BYTES, st, (p & 1) ? keys_b : keys_a,
+                           (p & 1) ? keys_a : keys_b, (p & 1) ? vals_b : vals_a, (p & 1) ? vals_a : vals_b, n, p, words, status,
+                           ghist, state + (size_t)p * sort_blocks * (RADIX / 2));
     PBN_LAUNCH_CHECK();
     return PBN_OK;
 }

@@ -41,6 +41,28 @@ def save_scene(npy_dir, scene, **arrays):
         np.save(scene_path(npy_dir, scene, suffix), a)
 
 
+def save_arrays(npy_dir, scene, **arrays):
+    """Any subset of the scene arrays under the same names and dtypes -- e.g. a test-split scene, which
+    decode_scannet.py:123-127 (f_test) writes without sem_label / ins_label."""
+    unknown = set(arrays) - set(SCENE_ARRAYS)
+    if unknown:
+        raise ValueError("save_arrays: unknown arrays %s" % sorted(unknown))
+    os.makedirs(npy_dir, exist_ok=True)
+    n = None
+    for suffix, (dtype, tail) in SCENE_ARRAYS.items():
+        if suffix not in arrays:
+            continue
+        a = np.asarray(arrays[suffix], dtype=dtype)
+        if a.shape[1:] != tail:
+            raise ValueError("save_arrays: %s must have shape [*, %s]" % (suffix, tail))
+        if suffix != "face":
+            if n is None:
+                n = a.shape[0]
+            elif a.shape[0] != n:
+                raise ValueError("save_arrays: %s has %d rows, expected %d" % (suffix, a.shape[0], n))
+        np.save(scene_path(npy_dir, scene, suffix), a)
+
+
 def load_scene(npy_dir, scene, with_mesh=True):
     """dataset_preprocess.py:222-228 (train / val read xyz, rgb, sem_label, ins_label, nl; eval_map.py adds sup)."""
     names = list(SCENE_ARRAYS) if with_mesh else ["xyz", "rgb", "sem_label", "ins_label", "nl"]
