@@ -707,6 +707,26 @@ int pbn_mesh_segment_point(const float* xyz, const float* normals, int n_points,
                            float k_thresh, int seg_min_verts, int64_t* sup, void* workspace, size_t workspace_bytes,
                            pbn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Validation meters (csrc/metrics.hip): the integer counts behind train.py:123-304 (eval_epoch).  No workspace, no
+ * synchronisation, integer atomics only (identical counters run to run).  Neither entry writes its inputs.
+ * ------------------------------------------------------------------------------------------------------------ */
+/* tools/mIOU.py:18-31 (intersectionAndUnionGPU) as counts, ADDED to caller-owned counters.  pred / target: n labels,
+ * int32 (flag 0) or int64 (flag 1), element-aligned.  With q_i = ignore_index where target_i == ignore_index and pred_i
+ * elsewhere (mIOU.py:24):  intersection[c] += #{q_i == target_i == c},  output[c] += #{q_i == c},  target[c] +=
+ * #{target_i == c}, c in [0, K); values outside [0, K) count nowhere (histc drops them), so a target that is out of range
+ * but not the ignore value still counts its prediction in `output`.  acc3k int64[3K] = intersection | output | target.
+ * conf_kk int64[K*K] (optional): [t*K + p] += 1 for t, p in [0, K), t != ignore_index.  n_class in [2, 64]; n == 0 is
+ * PBN_OK and launches nothing; a bad argument is PBN_ERR_ARG before any launch. */
+int pbn_sem_confusion(const void* pred, int pred_i64, const void* target, int target_i64, int64_t n, int n_class,
+                      int ignore_index, int64_t* acc3k, int64_t* conf_kk, pbn_stream_t stream);
+/* train.py:153-168 for one scene, WRITTEN to row8 int64[8] = n, agree, n_pos, pos_pred1, n_neg, neg_pred1, n_nan, 0 with
+ * pred1 = pred_mask >= threshold (compared in float32), agree = #{pred1 == gt}, n_pos = #{gt == 1}, n_neg = #{gt == 0},
+ * pos_pred1 / neg_pred1 the rows of each with pred1 = 1.  A NaN score counts in n_nan only.  pred_mask: n scores of `dtype`
+ * (PBN_F32 / PBN_BF16 / PBN_F16); gt_mask: int32 (gt_i64 0) or int64 (1).  n == 0 writes a zero row. */
+int pbn_mask_accuracy(const void* pred_mask, int dtype, const void* gt_mask, int gt_i64, int64_t n, float threshold,
+                      int64_t* row8, pbn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
