@@ -358,6 +358,12 @@ int pbn_spconv_wgrad_checked(const void* x, int ld_x, long long n_x_rows, const 
  *   pbn_local_plan       network/PBNet.py:182-234 for task 'test': one local scene per cluster; entry table in the layout
  *                        pbn_local_scene_rows reads; counts[ENTRIES, ROWS, SCENES, CLUSTERS].  kNN of the cluster centres:
  *                        ascending (d^2, id) with d^2 = (dx^2+dy^2)+dz^2 in unfused fp32.
+ *                        cluster_num / member_start / centers describe all *n_clusters clusters; scenes are made for the first
+ *                        C = min(*n_clusters, c_cap) (PBN_OVF_CLUSTERS beyond), whose neighbours may be clusters >= C.
+ *                        Written: ent_row_start[0 .. n_ent], the other three entry arrays [0 .. n_ent), nothing beyond.
+ *                        counts[CLUSTERS] = C on EVERY path.  More entries than e_cap (PBN_OVF_ENTRIES): ENTRIES = ROWS =
+ *                        SCENES = 0, ent_row_start[0] = 0 and no other entry word is written.  More rows than r_cap
+ *                        (PBN_OVF_ROWS): the same three counts are 0, the entry arrays are written all the same.
  *   pbn_proposal_offsets network/PBNet.py:330-345: proposals_offset i64[s_cap+1], surviving scene ids, dense renumbering;
  *                        counts[PROPOSALS, PROPOSAL_ROWS].
  *   pbn_batch_starts     seg_start[s] = first row of a batch-sorted [n,4] coordinate list whose batch index is >= s. */

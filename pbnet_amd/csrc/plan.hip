@@ -183,6 +183,7 @@ __global__ __launch_bounds__(PACK_TPB) void k_plan_pack(const int* __restrict__ 
         if (threadIdx.x == 0) {
             atomicOr(&counts[PBN_CNT_OVERFLOW], PBN_OVF_ENTRIES | s_flag);
             counts[PBN_CNT_ENTRIES] = 0; counts[PBN_CNT_ROWS] = 0; counts[PBN_CNT_SCENES] = 0;
+            counts[PBN_CNT_CLUSTERS] = C;      // as on every other path: the clusters planned, whatever overflowed after
             ent_row_start[0] = 0;
         }
         return;
