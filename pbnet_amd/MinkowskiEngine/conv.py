@@ -17,7 +17,7 @@ from .. import _native as N
 from ..scratch import StreamScratch
 from .core import SparseTensor
 
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+_DT = N.DT
 _ELEMS = {torch.float32: 4, torch.bfloat16: 8, torch.float16: 8}
 
 

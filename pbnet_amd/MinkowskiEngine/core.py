@@ -115,9 +115,14 @@ class _Pyramid(object):
 
     def native_tables(self):
         self.finalize()
-        L = self.layout
-        return ([self.ptr(L.k3[l]) for l in range(5)], self.ptr(L.k5), [self.ptr(L.nbr_down[l]) for l in range(4)],
-                [self.ptr(L.up[l]) for l in range(4)])
+        return table_arrays(self.ptr(0), self.layout)
+
+
+def table_arrays(base, L):
+    """The kernel maps of a pyramid (pbn_coords_layout L of an arena at `base`) as the executors' four table arguments."""
+    vp = ctypes.c_void_p
+    return ((vp * 5)(*[base + L.k3[l] for l in range(5)]), vp(base + L.k5),
+            (vp * 4)(*[base + L.nbr_down[l] for l in range(4)]), (vp * 4)(*[base + L.up[l] for l in range(4)]))
 
 
 class SortedView(object):

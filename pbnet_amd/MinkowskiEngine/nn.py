@@ -3,11 +3,10 @@ thin wrappers that apply a torch module to the feature matrix, exactly as Minkow
 import torch
 import torch.nn as nn
 
+from .._native import DT as _DT
 from ..scratch import StreamScratch
 from .core import SparseTensor
 
-
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 _BN_WS = StreamScratch()
 
 
@@ -238,14 +237,16 @@ def _batch_index(x):
     return b, int(b.max().item()) + 1 if b.numel() else 0
 
 
-def segment_pool(feats, batch_sorted, n_batch, want_max=True, want_avg=True):
+def segment_pool(feats, batch_sorted, n_batch, want_max=True, want_avg=True, seg_start=None):
     """Global max / avg pooling per batch index for rows GROUPED by ascending batch index (pbn_segment_pool).
-    Returns fp32 [n_batch, C] tensors (None for the one not requested)."""
+    seg_start i32[n_batch + 1]: the segments' first rows when the caller already has them on the device (the capacity-planned
+    forward: n_batch is then a capacity and batch_sorted is not read).  Returns fp32 [n_batch, C] tensors (None for the one
+    not requested)."""
     from .. import _native as N
-    from .conv import _DT
     assert feats.stride(1) == 1
-    seg_start = torch.searchsorted(batch_sorted.to(torch.int32).contiguous(),
-                                   torch.arange(n_batch + 1, dtype=torch.int32, device=feats.device)).to(torch.int32)
+    if seg_start is None:
+        seg_start = torch.searchsorted(batch_sorted.to(torch.int32).contiguous(),
+                                       torch.arange(n_batch + 1, dtype=torch.int32, device=feats.device)).to(torch.int32)
     c = feats.shape[1]
     mx = torch.empty(n_batch, c, dtype=torch.float32, device=feats.device) if want_max else None
     av = torch.empty(n_batch, c, dtype=torch.float32, device=feats.device) if want_avg else None

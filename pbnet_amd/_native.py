@@ -6,6 +6,8 @@ loudly, instead of routing anywhere else.  torch is used only to own device memo
 import ctypes
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PBNET_HIP_LIB") or os.path.join(_HERE, "libpbnet_hip.so")   # override: A/B of two builds
 
@@ -20,6 +22,8 @@ c_size = ctypes.c_size_t
 
 c_i64 = ctypes.c_int64
 c_i32 = ctypes.c_int32
+
+DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}          # the `dtype` argument of the C ABI (pbn_dtype)
 
 
 class CoordsLayout(ctypes.Structure):
@@ -258,14 +262,10 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
-_torch_C = None
+_torch_C = torch._C
 
 
 def current_stream():
-    global _torch_C
-    if _torch_C is None:
-        import torch
-        _torch_C = torch._C
     return ctypes.c_void_p(_torch_C._cuda_getCurrentRawStream(_torch_C._cuda_getDevice()))
 
 

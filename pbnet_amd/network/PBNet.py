@@ -14,6 +14,7 @@ One host synchronisation per stage boundary (class counts, cluster table, propos
 """
 import os
 import threading
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -23,6 +24,7 @@ from .. import MinkowskiEngine as ME
 from .. import pbnet_ops
 from .. import stage_ops
 from ..prof import section, mark
+from ..stage_ops import CNT
 from .Mink import Mink_unet as unet3d
 
 COUNT_MEAN = [-1., -1., 3917., 12056., 2303., 8331., 3948., 3166., 5629., 11719., 1003., 3317., 4912., 10221., 3889.,
@@ -33,9 +35,9 @@ MASK_THD = 0.45                                                       # PBNet.py
 # training: index-only glue between the networks on the inference path's fused launches (see PBNet.forward); "0" = plain torch
 TRAIN_FUSED_GLUE = os.environ.get("PBNET_TRAIN_FUSED_GLUE", "1") == "1"
 # Round 5: the size-exact inference forward takes its class gate, the selection, the grouping AND the local-scene plan on the
-# device (csrc/plan.hip: pbn_class_gate / pbn_local_plan, the entries the planned forward uses) over buffers bounded by the
-# number of points, and reads the four sizes back ONCE where it used to read the class table, then the cluster table, and run
-# the per-(class, batch) cdist / topk plan on the host (PBNet.py:151-234).  Same integers (the device plan is the one
+# device (csrc/plan.hip through stage_ops.class_gate / local_plan, the launches the planned forward issues) over buffers bounded
+# by the number of points, and reads the four sizes back ONCE where it used to read the class table, then the cluster table, and
+# run the per-(class, batch) cdist / topk plan on the host (PBNet.py:151-234).  Same integers (the device plan is the one
 # tests/test_planned_gpu.py pins to the host plan); more than FRONT_CLUSTER_CAP clusters -> the host path.  "0": the host path.
 DEVICE_FRONT = os.environ.get("PBNET_DEVICE_FRONT", "1") == "1"
 FRONT_CLUSTER_CAP = 1024
@@ -43,6 +45,18 @@ FRONT_CLUSTER_CAP = 1024
 # them by the selected points.  (Measured after k_count stopped folding the lanes past the count onto its last point: +2.5-3.5 % in
 # flight at 162 k points, level at 485 k and at 1.1 M points.)
 FRONT_MAX_POINTS = int(os.environ.get("PBNET_DEVICE_FRONT_MAX_POINTS", "2000000"))      # (round 6: 2 M -- eight merged scenes, pbnet_amd/serving.py)
+
+
+def _pack_entries(plan, dev):
+    """The host's entry lists (PBNet._host_plan) as the packed entry table of stage_ops.local_scene_rows, in ONE host->device
+    copy: (packed, n_ent, n_rows)."""
+    n_ent = len(plan.ent_np)
+    row_start = np.zeros(n_ent + 1, dtype=np.int32)
+    np.cumsum(plan.sizes[plan.ent_np], out=row_start[1:])
+    ent_scene = np.repeat(np.arange(len(plan.scene_len), dtype=np.int32), plan.scene_len)
+    packed = torch.from_numpy(np.concatenate([row_start, plan.member_start[:-1][plan.ent_np].astype(np.int32), ent_scene,
+                                              np.asarray(plan.ent_weight, dtype=np.float32).view(np.int32)])).to(dev)
+    return packed, n_ent, int(row_start[-1])
 
 
 def _mlp(cin, mid, cout, sigmoid=False):
@@ -159,235 +173,86 @@ class PBNet(nn.Module):
             point_feat = self.MEUnet(inputs_v1)
         if fused:   # data-dependent sizes of this forward (pbnet_amd.planned.measure_capacities reads them)
             self._last_sizes = {"lv1": list(inputs_v1.coordinate_manager.row_counts())}
-        _sec = section("a5_heads_gather"); _sec.__enter__()
-        v2p = v2p_v1.long()
-        if fused:
-            # heads evaluated straight at the points (one launch each): the same rows, so the same numbers, as
-            # evaluating them at the voxels and gathering (PBNet.py:124-134)
-            f, row_index = point_feat.rows()              # the U-Net's own row order: fold it into the point index
-            if row_index is not None:
-                v2p = row_index[v2p]
+        with section("a5_heads_gather"):
+            v2p = v2p_v1.long()
+            if fused:
+                # heads evaluated straight at the points (one launch each): the same rows, so the same numbers, as
+                # evaluating them at the voxels and gathering (PBNet.py:124-134)
+                f, row_index = point_feat.rows()              # the U-Net's own row order: fold it into the point index
+                if row_index is not None:
+                    v2p = row_index[v2p]
+                return {
+                    "point_feat_p": f[v2p],
+                    "sem_pred_score_p": stage_ops.mlp_rows(self.linear_sem, f, v2p),
+                    "offset_pred_p": stage_ops.mlp_rows(self.linear_offset, f, v2p),
+                    "batch_head_p": xyz_voxel[:, 0].to(torch.int32)[v2p_v1.long()],
+                }
+            sem_pred_score = self.linear_sem(point_feat)
+            sem_pred_score_sf = self.soft_max(sem_pred_score)
+            offsets_pred = self.linear_offset(point_feat)
             out = {
-                "point_feat_p": f[v2p],
-                "sem_pred_score_p": stage_ops.mlp_rows(self.linear_sem, f, v2p),
-                "offset_pred_p": stage_ops.mlp_rows(self.linear_offset, f, v2p),
-                "batch_head_p": xyz_voxel[:, 0].to(torch.int32)[v2p_v1.long()],
+                "point_feat_p": point_feat.F[v2p],
+                "sem_pred_score_p": sem_pred_score.F[v2p],
+                "sem_pred_score_sfp": sem_pred_score_sf.F[v2p],
+                "offset_pred_p": offsets_pred.F[v2p],
+                "batch_head_p": xyz_voxel[:, 0][v2p],
             }
-            _sec.__exit__(None, None, None)
+            out["sem_pred_p"] = out["sem_pred_score_p"].max(1)[1]
             return out
-        sem_pred_score = self.linear_sem(point_feat)
-        sem_pred_score_sf = self.soft_max(sem_pred_score)
-        offsets_pred = self.linear_offset(point_feat)
-        out = {
-            "point_feat_p": point_feat.F[v2p],
-            "sem_pred_score_p": sem_pred_score.F[v2p],
-            "sem_pred_score_sfp": sem_pred_score_sf.F[v2p],
-            "offset_pred_p": offsets_pred.F[v2p],
-            "batch_head_p": xyz_voxel[:, 0][v2p],
-        }
-        out["sem_pred_p"] = out["sem_pred_score_p"].max(1)[1]
-        _sec.__exit__(None, None, None)
-        return out
 
     # ---- PBNet.py:144-279 -------------------------------------------------------------------------------------
     def cluster_stage(self, s1, xyz_original, ins_label, task, n_batch=None):
+        """Front (gate, selection, grouping, local-scene plan) -> rows of the local scenes -> mask branch -> proposals -> score."""
         dev = xyz_original.device
         xyz_original = xyz_original.float()
-        fused = "table" in s1
-        fused_glue = not torch.is_grad_enabled()      # inference: stage glue as fused launches (stage_ops)
-        sem_pred_p = s1["sem_pred_p"]
-        point_feat_p, offset_pred_p = s1["point_feat_p"], s1["offset_pred_p"]
-        train_glue = fused and torch.is_grad_enabled()       # fused index work, differentiable features (see forward())
-        sem_sfp = s1["sem_prob_p"].view(-1, 1) if (fused and not train_glue) else s1["sem_pred_score_sfp"]
+        fused = "table" in s1                         # the index work between the networks runs as fused launches (stage_ops)
+        infer = not torch.is_grad_enabled()           # inference: so does everything else between them
+        train_glue = fused and not infer              # fused index work, differentiable features (see forward())
+        sem_pred_p, point_feat_p = s1["sem_pred_p"], s1["point_feat_p"]
+        sem_sfp = s1["sem_prob_p"].view(-1, 1) if (fused and infer) else s1["sem_pred_score_sfp"]
         nb = n_batch if n_batch is not None else (self.batch_size if task == "train" else 3)          # PBNet.py:167-170
         self.cluster_batch = nb
-        n_cls = int(self.sem_num)
 
         # inference: gate, selection, grouping and local-scene plan on the device, ONE read-back (see DEVICE_FRONT)
         front = None
-        if (DEVICE_FRONT and fused and not train_glue and task == "test" and ins_label is None and xyz_original.is_contiguous()
+        if (DEVICE_FRONT and fused and infer and task == "test" and ins_label is None and xyz_original.is_contiguous()
                 and xyz_original.shape[0] <= FRONT_MAX_POINTS):
-            front = self._device_front(s1, xyz_original, nb, n_cls)
+            front = self._device_front(s1, xyz_original, nb)
             if isinstance(front, str):
                 return self._empty_stage(dev, task)
         if front is not None:
             ins_ind, res, packed, n_ent, n_rows, n_clt, m = front
-            n_scenes = n_clt                                    # test mode: every cluster heads one local scene (PBNet.py:182-234)
-            with section("a17_gather"), torch.no_grad():
-                point_idx, row_scene, coords, feat = stage_ops.local_scene_rows(
-                    packed, n_ent, n_rows, res.member_idx, ins_ind, xyz_original, LOCAL_VOXEL, point_feat_p.detach(),
-                    sem_sfp.detach(), None)
-            self._last_sizes.update(points=int(m), clusters=int(n_clt), entries=int(n_ent), rows=int(n_rows))
-            _sec = section("a17_plan"); _sec.__enter__()         # (the host plan of the other branch: nothing to do here)
+            n_scenes, scene_gt, plan = n_clt, None, None        # test mode: every cluster heads one local scene (PBNet.py:182-234)
+            self._last_sizes["points"] = int(m)
         else:
-            # (a6) per-class selection, all classes at once; host learns the [class, batch] population table
-            _sec = section("a6_select"); _sec.__enter__()
-            if fused:
-                table = s1["table"]
-            else:
-                batch_head_p = s1["batch_head_p"].long()
-                table = torch.bincount(sem_pred_p * nb + batch_head_p, minlength=n_cls * nb)[:n_cls * nb].view(n_cls, nb)
-            mark("a6:before table sync")
-            tab = table.cpu().numpy()                                                 # sync 1
-            mark("a6:table on host")
-            assert int(tab.sum()) == sem_pred_p.shape[0], "batch index outside [0, cluster_batch)"  # PBNet.py:286
-            per_class = tab.sum(1).tolist()
-            thr05, thr02 = self._class_thresholds()
-            classes = [c for c in range(2, n_cls) if not (float(per_class[c]) < thr05[c])]          # PBNet.py:157
-            if not classes:
+            front = self._host_front(s1, xyz_original, ins_label, task, nb, fused, train_glue)
+            if front is None:
                 return self._empty_stage(dev, task)
-            m = sum(per_class[c] for c in classes)
-            seg_len_h = tab[classes].reshape(-1).astype(np.int32)                    # segments = (class, batch) in order
-            if fused:
-                # stable class-major selection + the grouping inputs in one launch (positions from the class totals);
-                # class_base and the segment lengths travel in ONE host->device copy
-                class_base = np.full(n_cls, -1, dtype=np.int32)
-                run = 0
-                for c in classes:
-                    class_base[c] = run
-                    run += per_class[c]
-                up = torch.from_numpy(np.concatenate([class_base, seg_len_h])).to(dev)
-                seg_len = up[n_cls:]
-                with torch.no_grad():
-                    ins_ind, ins_orig, ins_offseted, ins_sem = stage_ops.select_points(
-                        sem_pred_p, up[:n_cls], s1["block_hist"], xyz_original, offset_pred_p.detach(), m)
+            ins_ind, res, plan, n_clt = front
+            n_scenes, scene_gt = len(plan.scene_len), plan.scene_gt
+
+        # device gathers over points: rows of every local scene, in the reference's order
+        with section("a17_gather"):
+            if plan is not None and not (infer or train_glue):
+                rows = self._rows_torch(plan, res, ins_ind, xyz_original, point_feat_p, sem_sfp, sem_pred_p)
             else:
-                keep = torch.zeros(n_cls, dtype=torch.bool)
-                keep[classes] = True
-                key = torch.where(keep.to(dev)[sem_pred_p], sem_pred_p, torch.full_like(sem_pred_p, n_cls))
-                order = torch.sort(key, stable=True)[1]
-                ins_ind = order[:m]                                   # class-major, ascending point index inside a class
-                ins_orig = xyz_original[ins_ind]
-                ins_offseted = ins_orig + offset_pred_p[ins_ind].float()                 # PBNet.py:165 (fp32 add)
-                ins_sem = sem_pred_p[ins_ind].to(torch.int32)
-                seg_len = torch.from_numpy(seg_len_h).to(dev)
-            _sec.__exit__(None, None, None)
-
-            if fused and not train_glue:
-                self._last_sizes["points"] = int(m)
-            mark("a7:select queued")
-            with section("a7_16_grouping"):
-                res = pbnet_ops.cluster_device(ins_offseted, ins_orig, ins_sem, seg_len, self.radius, self.min_pts,
-                                              need_den=False)
-                mark("a7:grouping queued")
-                # one read-back for the cluster table AND the first HEAD_CLUSTERS centres / member offsets (a scene has tens
-                # of clusters; a second read-back follows only when there are more)
-                n_seg = int(res.cluster_num.shape[0])
-                hc = min(HEAD_CLUSTERS, int(res.member_start.shape[0]) - 1)
-                head = torch.cat([res.n_clusters, res.cluster_num, res.member_start[:hc + 1],
-                                  res.centers[:3 * hc].view(torch.int32)]).cpu().numpy()   # sync 2
-                mark("a7:grouping done")
-                n_clt = int(head[0])
-            if n_clt < 0:
-                raise RuntimeError("grouping rejected its input (class id outside [2,19])")
-            if n_clt == 0:
-                return self._empty_stage(dev, task)
-            _sec = section("a17_plan"); _sec.__enter__()
-            cluster_num = head[1:1 + n_seg].reshape(len(classes), nb).tolist()
-            if n_clt <= hc:
-                member_start = head[1 + n_seg:1 + n_seg + n_clt + 1]
-                centers = torch.from_numpy(head[2 + n_seg + hc:2 + n_seg + hc + 3 * n_clt].view(np.float32).copy()).view(n_clt, 3)
-            else:
-                packed = torch.cat([res.centers[:3 * n_clt], res.member_start[:n_clt + 1].view(torch.float32)]).cpu()  # sync 3
-                centers = packed[:3 * n_clt].view(n_clt, 3)
-                member_start = packed[3 * n_clt:].view(torch.int32).numpy()
-            mark("a17:centres on host")
-            sizes = (member_start[1:] - member_start[:-1])
-            sizes_l = sizes.tolist()
-            labels_h = None
-            if task != "test":
-                labels_h = ins_label[ins_ind[res.member_idx[:int(member_start[-1])].long()]].cpu()
-
-            # (a17) host plan over clusters: which clusters make up each local scene, and with which weight
-            ent_cluster, ent_weight, scene_len, scene_gt = [], [], [], []
-            k_max = self._k_max_list()
-            g = 0                                                   # running global cluster id (class-major, batch, seed)
-            for ci, cls in enumerate(classes):
-                for b in range(nb):
-                    c_b = cluster_num[ci][b]
-                    if c_b == 0:
-                        continue
-                    para_k = min(c_b - 1, k_max[cls])
-                    if para_k > 0:
-                        peak_v = [0.5 * ((para_k + 1) - p_i) / (para_k + 1) for p_i in range(para_k + 1)]
-                        ctr = centers[g:g + c_b]
-                        knn_idx = torch.cdist(ctr, ctr).topk(k=c_b, dim=1, largest=False)[1].tolist()
-                    big = thr02[cls]
-                    for c_i in range(c_b):
-                        gid = g + c_i
-                        gt = None
-                        if task != "test":
-                            gt = int(torch.mode(labels_h[int(member_start[gid]):int(member_start[gid + 1])])[0])
-                            if gt == -100:
-                                continue
-                        ents, wts = [gid], [1.0]
-                        if float(sizes_l[gid]) > big and para_k > 0:                  # PBNet.py:199
-                            row = knn_idx[c_i]
-                            for k_i in range(para_k):
-                                ents.append(g + row[k_i + 1])
-                                wts.append(peak_v[k_i])
-                        ent_cluster += ents
-                        ent_weight += wts
-                        scene_len.append(len(ents))
-                        scene_gt.append(gt)
-                    g += c_b
-            if not scene_len:
-                return self._empty_stage(dev, task)
-
-            _sec.__exit__(None, None, None)
-            mark("a17:plan done")
-            # device gathers over points: rows of every local scene, in the reference's order
-            _sec = section("a17_gather"); _sec.__enter__()
-            ent_np = np.asarray(ent_cluster, dtype=np.int64)
-            if not torch.is_grad_enabled() or train_glue:
-                # inference: ONE launch (pbn_local_scene_rows) driven by one packed host->device copy of the entry table
-                n_ent = len(ent_cluster)
-                row_start = np.zeros(n_ent + 1, dtype=np.int32)
-                np.cumsum(sizes[ent_np], out=row_start[1:])
-                n_rows = int(row_start[-1])
-                ent_scene = np.repeat(np.arange(len(scene_len), dtype=np.int32), scene_len)
-                packed = torch.from_numpy(np.concatenate([row_start, member_start[:-1][ent_np].astype(np.int32), ent_scene,
-                                                          np.asarray(ent_weight, dtype=np.float32).view(np.int32)])).to(dev)
-                with torch.no_grad():
-                    point_idx, row_scene, coords, feat = stage_ops.local_scene_rows(
-                        packed, n_ent, n_rows, res.member_idx, ins_ind, xyz_original, LOCAL_VOXEL, point_feat_p.detach(),
-                        sem_sfp.detach(), None if (fused and not train_glue) else sem_pred_p)
+                if plan is not None:
+                    packed, n_ent, n_rows = _pack_entries(plan, dev)
+                rows = self._rows_fused(packed, n_ent, n_rows, res, ins_ind, xyz_original, point_feat_p, sem_sfp,
+                                        None if (fused and infer) else sem_pred_p)
                 if train_glue:
-                    # the same rows with their gradients: features and own-class scores gathered by torch, the entry weight (a
-                    # constant) taken from the fused launch's last column                                  PBNet.py:162-163,194,230
-                    row_sem_sf = sem_sfp[point_idx, sem_pred_p[point_idx]]
-                    feat = torch.cat([point_feat_p[point_idx], row_sem_sf.view(-1, 1).to(point_feat_p.dtype), feat[:, -1:]], 1)
+                    rows = self._rows_train_glue(rows, point_feat_p, sem_sfp, sem_pred_p)
                 elif fused:
                     self._last_sizes.update(clusters=int(n_clt), entries=int(n_ent), rows=int(n_rows))
-            else:
-                ent_cluster_t = torch.from_numpy(ent_np)
-                ent_rows = torch.from_numpy(sizes.astype(np.int64))[ent_cluster_t]
-                member_start = torch.from_numpy(member_start)
-                ent_scene = torch.repeat_interleave(torch.arange(len(scene_len)), torch.tensor(scene_len))
-                d = lambda t: t.to(dev)
-                row_ent = torch.repeat_interleave(torch.arange(len(ent_cluster), device=dev), d(ent_rows))
-                ent_first = d(torch.cumsum(ent_rows, 0) - ent_rows)
-                pos_in_ent = torch.arange(row_ent.shape[0], device=dev) - ent_first[row_ent]
-                member_pos = d(member_start[:-1][ent_cluster_t])[row_ent] + pos_in_ent
-                local_idx = res.member_idx[member_pos].long()                            # index into the grouped array
-                point_idx = ins_ind[local_idx]                                           # index into the scene's points
-                row_scene = d(ent_scene)[row_ent]
-                row_weight = d(torch.tensor(ent_weight, dtype=torch.float32))[row_ent]
-                row_sem_sf = sem_sfp[point_idx, sem_pred_p[point_idx]]                    # PBNet.py:162-163: own-class score
-                feat = torch.cat([point_feat_p[point_idx], row_sem_sf.view(-1, 1).to(point_feat_p.dtype),
-                                  row_weight.view(-1, 1).to(point_feat_p.dtype)], 1)     # [R, 34]  PBNet.py:194,230
-                coords = torch.cat([row_scene.view(-1, 1).to(torch.int32),
-                                    torch.floor(xyz_original[point_idx] / LOCAL_VOXEL).to(torch.int32)], 1)
-            n_scenes = len(scene_len)
-        out = {}
-        _sec.__exit__(None, None, None)
-
+            point_idx, row_scene, coords, feat = rows
         mark("a17:rows queued")
+
+        out = {}
         # (a18) mask branch
         with section("a18_mask_coords"):
             inputs_v2 = ME.SparseTensor(feat, coords)
         with section("a18_mask_unet"):
-            if fused_glue:   # head evaluated at the rows (PBNet.py:247): same numbers as head-then-gather, one launch
+            if infer:   # head evaluated at the rows (PBNet.py:247): same numbers as head-then-gather, one launch
                 f2, row_index = self.D_Unet(inputs_v2).rows()
                 if fused:
                     self._last_sizes["lv2"] = list(inputs_v2.coordinate_manager.row_counts())
@@ -403,7 +268,7 @@ class PBNet(nn.Module):
         mark("a18:mask unet queued")
         coords3 = feat3 = None
         with section("a19_proposals"):
-            if fused_glue:
+            if infer:
                 out["proposals"], coords3, feat3 = self._proposals_fused(row_scene, point_idx, mask_score, n_scenes,
                                                                          xyz_original, point_feat_p)
             elif train_glue:
@@ -413,104 +278,262 @@ class PBNet(nn.Module):
                 feat3 = point_feat_p[out["proposals"][0][:, 1]]
             else:
                 out["proposals"] = self.get_proposal(row_scene, point_idx, mask_score, n_scenes=n_scenes)
-
         mark("a19:proposals queued")
-        # (a20) score branch
-        proposals_idx, proposals_offset, _, _ = out["proposals"]
-        if proposals_offset.shape[0] > 1:
-            if coords3 is None:
-                pidx = proposals_idx[:, 1]
-                c3 = torch.floor(xyz_original[pidx] * self.scale_size / self.voxel_size).to(torch.int32)
-                coords3 = torch.cat([proposals_idx[:, 0:1].to(torch.int32), c3], 1)
-                feat3 = point_feat_p[pidx]
-            with section("a20_score_coords"):
-                inputs_v3 = ME.SparseTensor(feat3, coords3)
-            with section("a20_score_unet"):
-                if fused_glue:
-                    iou_feat_f = stage_ops.mlp_rows(self.linear_IOU_feat, *self.score_Unet(inputs_v3).rows())
-                    if fused:
-                        self._last_sizes["lv3"] = list(inputs_v3.coordinate_manager.row_counts())
-                else:
-                    iou_feat = self.linear_IOU_feat(self.score_Unet(inputs_v3))
-            with section("a20_pool_head"):
-                # global max + avg pooling per proposal (PBNet.py:274-276); rows are grouped by proposal id
-                if torch.is_grad_enabled():      # training: the same segment-pool kernel with the reductions' backward rules
-                    from ..MinkowskiEngine.nn import global_max_plus_avg_pool
-                    global_feat = global_max_plus_avg_pool(iou_feat) if iou_feat.F.is_cuda else \
-                        self.global_max_pool(iou_feat) + self.global_avg_pool(iou_feat)
-                    out["clt_scores"] = self.linear_IOU(global_feat).F.view(-1)
-                else:                            # inference: one deterministic segment-pool kernel
-                    from ..MinkowskiEngine.nn import segment_pool, _PooledTensor
-                    n_prop = int(proposals_offset.shape[0]) - 1
-                    f = iou_feat_f if fused_glue else iou_feat.F
-                    mx, av = segment_pool(f, inputs_v3.C[:, 0], n_prop)
-                    pooled = (mx + av).to(f.dtype)
-                    if fused_glue:
-                        out["clt_scores"] = stage_ops.mlp_rows(self.linear_IOU, pooled).view(-1)
-                    else:
-                        out["clt_scores"] = self.linear_IOU(_PooledTensor(pooled)).F.view(-1)
-        else:
-            out["clt_scores"] = torch.zeros(0, dtype=torch.float32, device=dev)
+        out["clt_scores"] = self._score_branch(out["proposals"], coords3, feat3, xyz_original, point_feat_p, fused, infer)
         mark("a20:score branch queued")
         return out
 
-    def _device_front(self, s1, xyz_original, nb, n_cls):
-        """Class gate -> selection -> grouping -> local-scene plan without a host decision in between (inference).
-        Returns None (fall back to the host path), "empty", or (ins_ind, res, packed, n_ent, n_rows, n_clt, m)."""
-        from .. import planned as P
-        from .. import _native as N
-        import ctypes
+    def _score_branch(self, proposals, coords3, feat3, xyz_original, point_feat_p, fused, infer):
+        """(a20) PBNet.py:255-279: the proposals' scores."""
+        proposals_idx, proposals_offset, _, _ = proposals
+        if proposals_offset.shape[0] <= 1:
+            return torch.zeros(0, dtype=torch.float32, device=xyz_original.device)
+        if coords3 is None:
+            pidx = proposals_idx[:, 1]
+            c3 = torch.floor(xyz_original[pidx] * self.scale_size / self.voxel_size).to(torch.int32)
+            coords3 = torch.cat([proposals_idx[:, 0:1].to(torch.int32), c3], 1)
+            feat3 = point_feat_p[pidx]
+        with section("a20_score_coords"):
+            inputs_v3 = ME.SparseTensor(feat3, coords3)
+        with section("a20_score_unet"):
+            if infer:
+                iou_feat_f = stage_ops.mlp_rows(self.linear_IOU_feat, *self.score_Unet(inputs_v3).rows())
+                if fused:
+                    self._last_sizes["lv3"] = list(inputs_v3.coordinate_manager.row_counts())
+            else:
+                iou_feat = self.linear_IOU_feat(self.score_Unet(inputs_v3))
+        with section("a20_pool_head"):
+            # global max + avg pooling per proposal (PBNet.py:274-276); rows are grouped by proposal id
+            if not infer:                    # training: the same segment-pool kernel with the reductions' backward rules
+                from ..MinkowskiEngine.nn import global_max_plus_avg_pool
+                global_feat = global_max_plus_avg_pool(iou_feat) if iou_feat.F.is_cuda else \
+                    self.global_max_pool(iou_feat) + self.global_avg_pool(iou_feat)
+                return self.linear_IOU(global_feat).F.view(-1)
+            # inference: one deterministic segment-pool kernel
+            from ..MinkowskiEngine.nn import segment_pool
+            n_prop = int(proposals_offset.shape[0]) - 1
+            mx, av = segment_pool(iou_feat_f, inputs_v3.C[:, 0], n_prop)
+            return stage_ops.mlp_rows(self.linear_IOU, (mx + av).to(iou_feat_f.dtype)).view(-1)
+
+    # ---- the three ways to the rows of the local scenes (PBNet.py:182-234) -----------------------------------------
+    def _rows_fused(self, packed, n_ent, n_rows, res, ins_ind, xyz_original, point_feat_p, sem_sfp, sem_pred_p):
+        """ONE launch (stage_ops.local_scene_rows) driven by the packed entry table."""
+        with torch.no_grad():
+            return stage_ops.local_scene_rows(packed, n_ent, n_rows, res.member_idx, ins_ind, xyz_original, LOCAL_VOXEL,
+                                              point_feat_p.detach(), sem_sfp.detach(), sem_pred_p)
+
+    def _rows_train_glue(self, rows, point_feat_p, sem_sfp, sem_pred_p):
+        """The fused launch's rows with their gradients: features and own-class scores gathered by torch, the entry weight (a
+        constant) taken from the fused launch's last column                                          PBNet.py:162-163,194,230"""
+        point_idx, row_scene, coords, feat = rows
+        row_sem_sf = sem_sfp[point_idx, sem_pred_p[point_idx]]
+        feat = torch.cat([point_feat_p[point_idx], row_sem_sf.view(-1, 1).to(point_feat_p.dtype), feat[:, -1:]], 1)
+        return point_idx, row_scene, coords, feat
+
+    def _rows_torch(self, plan, res, ins_ind, xyz_original, point_feat_p, sem_sfp, sem_pred_p):
+        """Plain tensor operations (autograd enabled, no fused glue)."""
         dev = xyz_original.device
-        lib = N.lib()
-        vp = ctypes.c_void_p
-        consts = self.__dict__.setdefault("_front_consts", {})
+        ent_cluster_t = torch.from_numpy(plan.ent_np)
+        ent_rows = torch.from_numpy(plan.sizes.astype(np.int64))[ent_cluster_t]
+        member_start = torch.from_numpy(plan.member_start)
+        ent_scene = torch.repeat_interleave(torch.arange(len(plan.scene_len)), torch.tensor(plan.scene_len))
+        d = lambda t: t.to(dev)
+        row_ent = torch.repeat_interleave(torch.arange(len(plan.ent_np), device=dev), d(ent_rows))
+        ent_first = d(torch.cumsum(ent_rows, 0) - ent_rows)
+        pos_in_ent = torch.arange(row_ent.shape[0], device=dev) - ent_first[row_ent]
+        member_pos = d(member_start[:-1][ent_cluster_t])[row_ent] + pos_in_ent
+        local_idx = res.member_idx[member_pos].long()                            # index into the grouped array
+        point_idx = ins_ind[local_idx]                                           # index into the scene's points
+        row_scene = d(ent_scene)[row_ent]
+        row_weight = d(torch.tensor(plan.ent_weight, dtype=torch.float32))[row_ent]
+        row_sem_sf = sem_sfp[point_idx, sem_pred_p[point_idx]]                    # PBNet.py:162-163: own-class score
+        feat = torch.cat([point_feat_p[point_idx], row_sem_sf.view(-1, 1).to(point_feat_p.dtype),
+                          row_weight.view(-1, 1).to(point_feat_p.dtype)], 1)     # [R, 34]  PBNet.py:194,230
+        coords = torch.cat([row_scene.view(-1, 1).to(torch.int32),
+                            torch.floor(xyz_original[point_idx] / LOCAL_VOXEL).to(torch.int32)], 1)
+        return point_idx, row_scene, coords, feat
+
+    def _host_select(self, s1, xyz_original, nb, fused):
+        """(a6) per-class selection, all classes at once; the host learns the [class, batch] population table.  Returns None (no
+        class passes its gate) or (classes, m, ins_ind, ins_orig, ins_offseted, ins_sem, seg_len)."""
+        dev = xyz_original.device
+        n_cls = int(self.sem_num)
+        sem_pred_p, offset_pred_p = s1["sem_pred_p"], s1["offset_pred_p"]
+        if fused:
+            table = s1["table"]
+        else:
+            batch_head_p = s1["batch_head_p"].long()
+            table = torch.bincount(sem_pred_p * nb + batch_head_p, minlength=n_cls * nb)[:n_cls * nb].view(n_cls, nb)
+        mark("a6:before table sync")
+        tab = table.cpu().numpy()                                                 # sync 1
+        mark("a6:table on host")
+        assert int(tab.sum()) == sem_pred_p.shape[0], "batch index outside [0, cluster_batch)"  # PBNet.py:286
+        per_class = tab.sum(1).tolist()
+        thr05, _ = self._class_thresholds()
+        classes = [c for c in range(2, n_cls) if not (float(per_class[c]) < thr05[c])]          # PBNet.py:157
+        if not classes:
+            return None
+        m = sum(per_class[c] for c in classes)
+        seg_len_h = tab[classes].reshape(-1).astype(np.int32)                    # segments = (class, batch) in order
+        if fused:
+            # stable class-major selection + the grouping inputs in one launch (positions from the class totals);
+            # class_base and the segment lengths travel in ONE host->device copy
+            class_base = np.full(n_cls, -1, dtype=np.int32)
+            run = 0
+            for c in classes:
+                class_base[c] = run
+                run += per_class[c]
+            up = torch.from_numpy(np.concatenate([class_base, seg_len_h])).to(dev)
+            with torch.no_grad():
+                selected = stage_ops.select_points(sem_pred_p, up[:n_cls], s1["block_hist"], xyz_original,
+                                                   offset_pred_p.detach(), m)
+            return (classes, m) + selected + (up[n_cls:],)
+        keep = torch.zeros(n_cls, dtype=torch.bool)
+        keep[classes] = True
+        key = torch.where(keep.to(dev)[sem_pred_p], sem_pred_p, torch.full_like(sem_pred_p, n_cls))
+        order = torch.sort(key, stable=True)[1]
+        ins_ind = order[:m]                                   # class-major, ascending point index inside a class
+        ins_orig = xyz_original[ins_ind]
+        ins_offseted = ins_orig + offset_pred_p[ins_ind].float()                 # PBNet.py:165 (fp32 add)
+        return classes, m, ins_ind, ins_orig, ins_offseted, sem_pred_p[ins_ind].to(torch.int32), torch.from_numpy(seg_len_h).to(dev)
+
+    def _host_front(self, s1, xyz_original, ins_label, task, nb, fused, train_glue):
+        """Class gate -> selection -> grouping -> local-scene plan with every decision on the host (two or three read-backs).
+        Returns None (nothing to group: the empty stage) or (ins_ind, res, plan, n_clt), plan = the host's entry lists."""
+        with section("a6_select"):
+            sel = self._host_select(s1, xyz_original, nb, fused)
+        if sel is None:
+            return None
+        classes, m, ins_ind, ins_orig, ins_offseted, ins_sem, seg_len = sel
+        if fused and not train_glue:
+            self._last_sizes["points"] = int(m)
+        mark("a7:select queued")
+        with section("a7_16_grouping"):
+            res = pbnet_ops.cluster_device(ins_offseted, ins_orig, ins_sem, seg_len, self.radius, self.min_pts,
+                                          need_den=False)
+            mark("a7:grouping queued")
+            # one read-back for the cluster table AND the first HEAD_CLUSTERS centres / member offsets (a scene has tens
+            # of clusters; a second read-back follows only when there are more)
+            n_seg = int(res.cluster_num.shape[0])
+            hc = min(HEAD_CLUSTERS, int(res.member_start.shape[0]) - 1)
+            head = torch.cat([res.n_clusters, res.cluster_num, res.member_start[:hc + 1],
+                              res.centers[:3 * hc].view(torch.int32)]).cpu().numpy()   # sync 2
+            mark("a7:grouping done")
+            n_clt = int(head[0])
+        if n_clt < 0:
+            raise RuntimeError("grouping rejected its input (class id outside [2,19])")
+        if n_clt == 0:
+            return None
+        with section("a17_plan"):
+            cluster_num = head[1:1 + n_seg].reshape(len(classes), nb).tolist()
+            if n_clt <= hc:
+                member_start = head[1 + n_seg:1 + n_seg + n_clt + 1]
+                centers = torch.from_numpy(head[2 + n_seg + hc:2 + n_seg + hc + 3 * n_clt].view(np.float32).copy()).view(n_clt, 3)
+            else:
+                packed = torch.cat([res.centers[:3 * n_clt], res.member_start[:n_clt + 1].view(torch.float32)]).cpu()  # sync 3
+                centers = packed[:3 * n_clt].view(n_clt, 3)
+                member_start = packed[3 * n_clt:].view(torch.int32).numpy()
+            mark("a17:centres on host")
+            labels_h = None
+            if task != "test":
+                labels_h = ins_label[ins_ind[res.member_idx[:int(member_start[-1])].long()]].cpu()
+            plan = self._host_plan(classes, nb, cluster_num, centers, member_start, labels_h)
+            if plan is None:
+                return None
+        mark("a17:plan done")
+        return ins_ind, res, plan, n_clt
+
+    def _host_plan(self, classes, nb, cluster_num, centers, member_start, labels_h):
+        """(a17) host plan over clusters: which clusters make up each local scene, and with which weight; labels_h (outside 'test'):
+        the ground-truth labels of the grouped points, whose mode names a scene's instance.  Returns None (no scene) or the lists."""
+        sizes = (member_start[1:] - member_start[:-1])
+        sizes_l = sizes.tolist()
+        _, thr02 = self._class_thresholds()
+        ent_cluster, ent_weight, scene_len, scene_gt = [], [], [], []
+        k_max = self._k_max_list()
+        g = 0                                                   # running global cluster id (class-major, batch, seed)
+        for ci, cls in enumerate(classes):
+            for b in range(nb):
+                c_b = cluster_num[ci][b]
+                if c_b == 0:
+                    continue
+                para_k = min(c_b - 1, k_max[cls])
+                if para_k > 0:
+                    peak_v = [0.5 * ((para_k + 1) - p_i) / (para_k + 1) for p_i in range(para_k + 1)]
+                    ctr = centers[g:g + c_b]
+                    knn_idx = torch.cdist(ctr, ctr).topk(k=c_b, dim=1, largest=False)[1].tolist()
+                big = thr02[cls]
+                for c_i in range(c_b):
+                    gid = g + c_i
+                    gt = None
+                    if labels_h is not None:
+                        gt = int(torch.mode(labels_h[int(member_start[gid]):int(member_start[gid + 1])])[0])
+                        if gt == -100:
+                            continue
+                    ents, wts = [gid], [1.0]
+                    if float(sizes_l[gid]) > big and para_k > 0:                  # PBNet.py:199
+                        row = knn_idx[c_i]
+                        for k_i in range(para_k):
+                            ents.append(g + row[k_i + 1])
+                            wts.append(peak_v[k_i])
+                    ent_cluster += ents
+                    ent_weight += wts
+                    scene_len.append(len(ents))
+                    scene_gt.append(gt)
+                g += c_b
+        if not scene_len:
+            return None
+        return SimpleNamespace(ent_np=np.asarray(ent_cluster, dtype=np.int64), ent_weight=ent_weight, scene_len=scene_len,
+                               scene_gt=scene_gt, sizes=sizes, member_start=member_start)
+
+    def _front_consts(self, dev):
+        """Per device: the class gates (thr05, thr02 f32[S]) and K_max (i32[S]) the device plan reads."""
+        consts = self.__dict__.setdefault("_front_consts_cache", {})
         c = consts.get(dev)
         if c is None:
             thr05, thr02 = self._class_thresholds()
-            c = consts[dev] = (torch.tensor(thr05, dtype=torch.float32, device=dev), torch.tensor(thr02, dtype=torch.float32, device=dev),
+            f32 = dict(dtype=torch.float32, device=dev)
+            c = consts[dev] = (torch.tensor(thr05, **f32), torch.tensor(thr02, **f32),
                                torch.tensor(self._k_max_list(), dtype=torch.int32, device=dev))
-        thr05_d, thr02_d, kmax_d = c
-        n_pts = int(xyz_original.shape[0])
-        n_seg = (n_cls - 2) * nb
-        i32 = dict(dtype=torch.int32, device=dev)
-        counts = torch.zeros(P.CNT.WORDS, **i32)
-        class_base = torch.empty(n_cls, **i32)
-        seg_len = torch.empty(n_seg, **i32)
+        return c
+
+    def _front_launches(self, table, sem_pred, block_hist, xyz, offset, nb, m_cap, c_cap, e_cap, r_cap, counts):
+        """Class gate -> selection -> grouping -> local-scene plan as launches only, every size a capacity and every count on the
+        device (counts i32[CNT.WORDS], zeroed by the caller): what the size-exact device front and pbnet_amd/planned.py both
+        issue.  Returns (ins_ind, the grouping result, the entry table)."""
+        thr05, thr02, kmax = self._front_consts(xyz.device)
         with section("a6_select"):
-            N.check(lib.pbn_class_gate(N.ptr(s1["table"]), N.ptr(thr05_d), n_cls, nb, n_pts, n_pts, N.ptr(class_base), N.ptr(seg_len),
-                                       vp(counts.data_ptr()), N.current_stream()), "pbn_class_gate")
-            ins_ind, ins_orig, ins_off, ins_sem = stage_ops.select_points(s1["sem_pred_p"], class_base, s1["block_hist"], xyz_original,
-                                                                          s1["offset_pred_p"].detach(), n_pts)
+            class_base, seg_len = stage_ops.class_gate(table, thr05, nb, m_cap, int(xyz.shape[0]), counts)
+            ins_ind, ins_orig, ins_off, ins_sem = stage_ops.select_points(sem_pred, class_base, block_hist, xyz, offset.detach(),
+                                                                          m_cap)
         mark("a7:select queued")
         with section("a7_16_grouping"):
             res = pbnet_ops.cluster_device(ins_off, ins_orig, ins_sem, seg_len, self.radius, self.min_pts, capacity=True,
                                           need_den=False)
-            c_cap = min(FRONT_CLUSTER_CAP, n_pts)
-            e_cap = 7 * c_cap
-            ent = torch.empty(4 * e_cap + 1, **i32)                    # row_start (e_cap + 1) | member_start | scene | weight bits
-            wsb = int(lib.pbn_local_plan_workspace_bytes(c_cap))
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            base = ent.data_ptr()
-            N.check(lib.pbn_local_plan(N.ptr(res.cluster_num), n_seg, nb, N.ptr(res.member_start), N.ptr(res.centers),
-                                       N.ptr(res.n_clusters), N.ptr(thr02_d), N.ptr(kmax_d), c_cap, e_cap, 2 ** 31 - 1,
-                                       vp(base), vp(base + 4 * (e_cap + 1)), vp(base + 4 * (2 * e_cap + 1)),
-                                       vp(base + 4 * (3 * e_cap + 1)), vp(counts.data_ptr()), N.ptr(ws), wsb, N.current_stream()),
-                    "pbn_local_plan")
+            ent = stage_ops.local_plan(res, nb, thr02, kmax, c_cap, e_cap, r_cap, counts)
             mark("a7:grouping queued")
-            h = torch.cat([counts, res.n_clusters]).cpu().tolist()                    # the ONE read-back of the front
-            mark("a7:grouping done")
-        if h[P.CNT.WORDS] < 0:
+        return ins_ind, res, ent
+
+    def _device_front(self, s1, xyz_original, nb):
+        """Class gate -> selection -> grouping -> local-scene plan without a host decision in between (inference).
+        Returns None (fall back to the host path), "empty", or (ins_ind, res, packed, n_ent, n_rows, n_clt, m)."""
+        n_pts = int(xyz_original.shape[0])
+        c_cap = min(FRONT_CLUSTER_CAP, n_pts)
+        counts = torch.zeros(CNT.WORDS, dtype=torch.int32, device=xyz_original.device)
+        ins_ind, res, ent = self._front_launches(s1["table"], s1["sem_pred_p"], s1["block_hist"], xyz_original,
+                                                 s1["offset_pred_p"], nb, n_pts, c_cap, 7 * c_cap, 2 ** 31 - 1, counts)
+        h = torch.cat([counts, res.n_clusters]).cpu().tolist()                    # the ONE read-back of the front
+        mark("a7:grouping done")
+        if h[CNT.WORDS] < 0:
             raise RuntimeError("grouping rejected its input (class id outside [2,19])")
-        if h[P.CNT.OVERFLOW] & 32:
+        if h[CNT.OVERFLOW] & 32:
             raise AssertionError("batch index outside [0, cluster_batch)")            # PBNet.py:286
-        if h[P.CNT.OVERFLOW]:
+        if h[CNT.OVERFLOW]:
             return None                                                               # more clusters than the plan holds: host path
-        m, n_clt, n_ent, n_rows = h[P.CNT.POINTS], h[P.CNT.CLUSTERS], h[P.CNT.ENTRIES], h[P.CNT.ROWS]
+        m, n_clt, n_ent, n_rows = h[CNT.POINTS], h[CNT.CLUSTERS], h[CNT.ENTRIES], h[CNT.ROWS]
         if m == 0 or n_clt == 0 or n_ent == 0:
             return "empty"
-        packed = torch.cat([ent[:n_ent + 1], ent[e_cap + 1:e_cap + 1 + n_ent], ent[2 * e_cap + 1:2 * e_cap + 1 + n_ent],
-                            ent[3 * e_cap + 1:3 * e_cap + 1 + n_ent]])
-        return ins_ind, res, packed, n_ent, n_rows, n_clt, m
+        return ins_ind, res, ent.compact(n_ent), n_ent, n_rows, n_clt, m
 
     def _class_thresholds(self):
         """Per-class population gates as Python floats of the fp32 products (PBNet.py:157 `count_mean * 0.05`,

@@ -11,12 +11,15 @@ Two execution paths over the same parameters:
     block stores its result directly into the right-hand columns of the decoder's concat slab, the transposed
     convolution into the left-hand columns), so no activation is touched twice.
 """
+import ctypes
 import operator
 import os
 
 import torch
 import torch.nn as nn
 
+from .. import _native as N
+from .. import stage_ops
 from .. import MinkowskiEngine as ME
 from ..MinkowskiEngine.conv import spconv_forward, _pad_vec
 from ..MinkowskiEngine.modules.resnet_block import BasicBlock
@@ -191,7 +194,6 @@ class MinkUNet(nn.Module):
     def _build_plan(self, dtype):
         """Static list of fused convolution ops over symbolic buffers: the body of Mink.py:291-354 in eval mode.
         Buffer 0 is the input slab; levels 0..4 are tensor strides 1..16."""
-        from .. import _native as N
         P = self.PLANES
         keep, ops, bufs, true_io, folded_io = [], [], [(0, 0)], [], []
         skip_c = (INIT_DIM, P[0], P[1], P[2])
@@ -325,46 +327,28 @@ class MinkUNet(nn.Module):
             self._plans[dtype] = hit
         return hit[1]
 
+    def _output_rows(self, plan, arena, offs, n, dtype):
+        """The fused forward's output [n, out_channels]: a view of the arena."""
+        out = arena_rows(arena, offs[plan["out_buf"]], n, plan["out_width"], dtype)
+        cout = self.final_sematic.kernel.shape[-1]
+        return out if out.shape[1] == cout else out[:, :cout]
+
     def _forward_fused(self, x):
-        import ctypes
-        from .. import _native as N
-        from ..MinkowskiEngine.conv import _DT, _workspace
+        from ..MinkowskiEngine.conv import _workspace
         cm = x.coordinate_manager
         assert x.tensor_stride == 1
         sv = cm.sorted() if self.MORTON else None      # the lineage in Z-order: compact tiles, L2-local gathers
         pyr = sv.pyramid if sv is not None else cm.plain()
-        feats = x.F
-        dt, dev = feats.dtype, feats.device
+        dt, dev = x.F.dtype, x.F.device
         plan = self._plan(dt)
-        cin_p = plan["cin_p"]
-        if sv is not None or feats.shape[1] < cin_p or feats.stride(1) != 1 \
-                or (feats.stride(0) * feats.element_size()) % 16 or feats.data_ptr() % 16:
-            es = feats.element_size()
-            if feats.stride(1) == 1 and (feats.shape[1] * es) % 4 == 0 and (feats.stride(0) * es) % 4 == 0 \
-                    and feats.data_ptr() % 4 == 0:
-                # one pass: rows in Z-order (or as they are), zero-padded to whole 16-byte vectors
-                n_in = int(feats.shape[0]) if sv is None else int(sv.perm.shape[0])
-                padded = torch.empty(n_in, cin_p, dtype=dt, device=dev)
-                N.check(N.lib().pbn_gather_pad_rows(
-                    ctypes.c_void_p(feats.data_ptr()), feats.stride(0) * es, feats.shape[1] * es,
-                    None if sv is None else ctypes.c_void_p(sv.perm.data_ptr()), n_in, ctypes.c_void_p(padded.data_ptr()),
-                    cin_p * es, N.current_stream()), "pbn_gather_pad_rows")
-            else:
-                padded = torch.zeros(feats.shape[0], cin_p, dtype=dt, device=dev)
-                padded[:, :feats.shape[1]] = feats if sv is None else feats[sv.perm]
-            feats = padded
+        feats = input_slab(x.F, plan["cin_p"], None if sv is None else sv.perm)
         rows = list(pyr.n)
-        n_rows = (ctypes.c_int32 * 5)(*rows)
-        offs = (ctypes.c_int64 * plan["n_bufs"])()
+        arena, nbytes, offs, n_rows = alloc_arena(plan["bufs"], plan["n_bufs"], rows, dt, dev)
         lib = N.lib()
-        nbytes = lib.pbn_unet_arena_bytes(plan["bufs"], plan["n_bufs"], n_rows, _DT[dt], offs)
-        arena = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-        k3, k5, down, up = pyr.native_tables()
         vp = ctypes.c_void_p
         ws = _workspace(dev)
-        args = (plan["ops"], plan["n_ops"], plan["bufs"], plan["n_bufs"], n_rows, vp(feats.data_ptr()), feats.stride(0),
-                (vp * 5)(*k3), vp(k5), (vp * 4)(*down), (vp * 4)(*up), vp(arena.data_ptr()), nbytes, _DT[dt],
-                vp(ws.data_ptr()), ws.numel(), N.current_stream())
+        args = (plan["ops"], plan["n_ops"], plan["bufs"], plan["n_bufs"], n_rows, vp(feats.data_ptr()), feats.stride(0)) \
+            + pyr.native_tables() + (vp(arena.data_ptr()), nbytes, N.DT[dt], vp(ws.data_ptr()), ws.numel(), N.current_stream())
         if MinkUNet.OP_TIMING_SINK is None:
             rc = lib.pbn_unet_forward(*args)
         else:  # bench.py's roofline probe: per-op HIP-event durations (synchronises)
@@ -372,11 +356,7 @@ class MinkUNet(nn.Module):
             rc = lib.pbn_unet_forward_timed(*(args + (op_ms,)))
             MinkUNet.OP_TIMING_SINK(self, plan, rows, pyr, feats.element_size(), list(op_ms))
         N.check(rc, "pbn_unet_forward")
-        o = offs[plan["out_buf"]]
-        width = plan["out_width"]
-        out = arena[o:o + rows[0] * width * feats.element_size()].view(dt).view(rows[0], width)
-        cout = self.final_sematic.kernel.shape[-1]
-        out = out if width == cout else out[:, :cout]
+        out = self._output_rows(plan, arena, offs, rows[0], dt)
         if sv is not None:                                 # rows are in Z-order: external row i = out[inv_perm[i]]
             return ME.SparseTensor._from_stored_rows(out, sv.inv_perm, cm)
         return ME.SparseTensor(out, coordinate_manager=cm, tensor_stride=1)
@@ -411,6 +391,38 @@ class MinkUNet(nn.Module):
         out = spconv_forward(cur, None, n[1], packed, shift=_pad_vec(fs.bias, packed[3], 0.0))
         cout = fs.kernel.shape[-1]
         return ME.SparseTensor(out if out.shape[1] == cout else out[:, :cout], coordinate_manager=cm, tensor_stride=1)
+
+
+def input_slab(feats, cin_p, perm=None, perm2=None, n=None, n_dev=None):
+    """Input rows -> the slab the native executors read: row i = feats[perm2[perm[i]]] (either index None = identity) in cin_p
+    zero-padded columns (whole 16-byte vectors) at a 16-byte-aligned address; n / n_dev as stage_ops.gather_pad_rows.  Rows
+    that already have that form pass through: the test is width == cin_p, for cin_p is the first convolution's input width
+    rounded up to whole vectors (_build_plan, train_engine.TrainPlan) and x.F carries exactly that width -- a wider row cannot
+    occur.  Otherwise one launch pads and permutes; rows it cannot address (not 4-byte granular) take torch ops."""
+    es, width = feats.element_size(), int(feats.shape[1])
+    assert width <= cin_p, "input rows of %d channels for a network of at most %d" % (width, cin_p)
+    if perm is None and n_dev is None and width == cin_p and feats.stride(1) == 1 and (feats.stride(0) * es) % 16 == 0 \
+            and feats.data_ptr() % 16 == 0:
+        return feats
+    if feats.stride(1) == 1 and (width * es) % 4 == 0 and (feats.stride(0) * es) % 4 == 0 and feats.data_ptr() % 4 == 0:
+        return stage_ops.gather_pad_rows(feats, cin_p, perm, perm2, n, n_dev)
+    assert perm2 is None and n_dev is None, "rows the padding launch cannot address have no capacity form"
+    padded = torch.zeros(feats.shape[0], cin_p, dtype=feats.dtype, device=feats.device)
+    padded[:, :width] = feats if perm is None else feats[perm]
+    return padded
+
+
+def alloc_arena(bufs, n_bufs, rows, dtype, device):
+    """The activation arena of a plan's buffers for `rows` per level: (arena, nbytes, byte offsets of the buffers, rows as int32[5])."""
+    n_rows = (ctypes.c_int32 * 5)(*[int(v) for v in rows])
+    offs = (ctypes.c_int64 * n_bufs)()
+    nbytes = N.lib().pbn_unet_arena_bytes(bufs, n_bufs, n_rows, N.DT[dtype], offs)
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device), nbytes, offs, n_rows
+
+
+def arena_rows(arena, offset, n, width, dtype):
+    """View of one arena buffer as [n, width] rows."""
+    return arena[offset:offset + n * width * torch.empty(0, dtype=dtype).element_size()].view(dtype).view(n, width)
 
 
 def _variant(name):

@@ -24,6 +24,7 @@ from .. import _native as N
 from ..MinkowskiEngine import conv as C
 from ..MinkowskiEngine.nn import _bn_workspace
 from ..MinkowskiEngine.core import SparseTensor
+from .mink_unet import _DOWN, _DOWN_BN, _UP, _UP_BN, INIT_DIM, alloc_arena, arena_rows, input_slab
 
 ENABLED = os.environ.get("PBN_TRAIN_ENGINE", "1") == "1"     # "0": the module path (one autograd node per block)
 # PBN_TRAIN_SORTED=1: the body runs on the lineage in Z-order (as the fused inference path does: a 128-row tile is a compact
@@ -34,11 +35,6 @@ ENABLED = os.environ.get("PBN_TRAIN_ENGINE", "1") == "1"     # "0": the module p
 SORTED = os.environ.get("PBN_TRAIN_SORTED", "0") == "1"
 # a list while a caller collects what one step's bodies compute (scripts/train_step.py: the step's roofline figure); None otherwise
 ACCOUNTING = None
-_DOWN = ("conv1p1s2", "conv2p2s2", "conv3p4s2", "conv4p8s2")
-_DOWN_BN = ("bn1", "bn2", "bn3", "bn4")
-_UP = ("convtr4p16s2", "convtr5p8s2", "convtr6p4s2", "convtr7p2s2")
-_UP_BN = ("bntr4", "bntr5", "bntr6", "bntr7")
-INIT_DIM = 32
 _K_OF = {0: 1, 1: 27, 2: 125, 3: 8, 4: 8}
 
 
@@ -291,27 +287,12 @@ class _BodyFn(torch.autograd.Function):
         lib = N.lib()
         es = feats.element_size()
         n = int(feats.shape[0])
-        cin_p = plan.cin_p
-        if perm is None and feats.shape[1] == cin_p and feats.stride(1) == 1 and (feats.stride(0) * es) % 16 == 0 \
-                and feats.data_ptr() % 16 == 0:
-            padded = feats
-        elif feats.stride(1) == 1 and (feats.shape[1] * es) % 4 == 0 and (feats.stride(0) * es) % 4 == 0 and feats.data_ptr() % 4 == 0:
-            padded = torch.empty(n, cin_p, dtype=dt, device=dev)
-            N.check(lib.pbn_gather_pad_rows(ctypes.c_void_p(feats.data_ptr()), feats.stride(0) * es, feats.shape[1] * es,
-                                            None if perm is None else ctypes.c_void_p(perm.data_ptr()), n,
-                                            ctypes.c_void_p(padded.data_ptr()), cin_p * es, N.current_stream()), "pbn_gather_pad_rows")
-        else:
-            padded = torch.zeros(n, cin_p, dtype=dt, device=dev)
-            padded[:, :feats.shape[1]] = feats if perm is None else feats[perm]
+        padded = input_slab(feats, plan.cin_p, perm)
         rows = list(pyr.n)
-        n_rows = (ctypes.c_int32 * 5)(*rows)
-        offs = (ctypes.c_int64 * len(plan.bufs))()
-        nbytes = lib.pbn_unet_arena_bytes(plan.bufs_arr, len(plan.bufs), n_rows, C._DT[dt], offs)
-        arena = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        arena, nbytes, offs, n_rows = alloc_arena(plan.bufs_arr, len(plan.bufs), rows, dt, dev)
         stats = torch.empty(plan.stat_floats, dtype=torch.float32, device=dev)
-        k3, k5, down, up = pyr.native_tables()
+        tables = pyr.native_tables()
         vp = ctypes.c_void_p
-        tables = ((vp * 5)(*k3), vp(k5), (vp * 4)(*down), (vp * 4)(*up))
         ws, bws = C._workspace(dev), _bn_workspace(dev, plan.max_channels)
         for nm in plan.norms:
             nm._tick()
@@ -332,7 +313,7 @@ class _BodyFn(torch.autograd.Function):
         ctx.in_shape, ctx.in_dtype = (n, int(feats.shape[1])), feats.dtype
         ob, oc = plan.out_view
         width = plan.bufs[ob][1]
-        out = arena[offs[ob]:offs[ob] + rows[0] * width * es].view(dt).view(rows[0], width)
+        out = arena_rows(arena, offs[ob], rows[0], width, dt)
         out = out[:, oc:oc + plan.out_channels] if (oc or width != plan.out_channels) else out
         out = out if inv_perm is None else out.index_select(0, inv_perm)       # external row i = stored row inv_perm[i]
         st.out_ref, st.out_version = weakref.ref(out), int(out._version)       # an in-place op on the output would corrupt the arena
@@ -354,12 +335,11 @@ class _BodyFn(torch.autograd.Function):
                                "in-place update): the packed weights of the forward no longer match")
         dt, dev = plan.dtype, dout.device
         lib = N.lib()
-        es = torch.empty(0, dtype=dt).element_size()
         rows = list(pyr.n)
         garena = torch.empty(max(st.nbytes, 16), dtype=torch.uint8, device=dev)
         ob, oc = plan.out_view
         width = plan.bufs[ob][1]
-        gout = garena[st.offs[ob]:st.offs[ob] + rows[0] * width * es].view(dt).view(rows[0], width)
+        gout = arena_rows(garena, st.offs[ob], rows[0], width, dt)
         gout[:, oc:oc + plan.out_channels].copy_(dout if st.perm is None else dout.index_select(0, st.perm))
         pgrads = torch.empty(plan.grad_floats, dtype=torch.float32, device=dev)
         dinput = torch.empty(rows[0], plan.dinput_width, dtype=dt, device=dev) if plan.want_input_grad else None

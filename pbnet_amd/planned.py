@@ -20,32 +20,36 @@ order only (tests/test_planned_gpu.py)."""
 import ctypes
 import os
 import sys
-from types import SimpleNamespace
 
-import numpy as np
 import torch
 
 from . import _native as N
-from . import pbnet_ops, stage_ops
+from . import stage_ops
 from .MinkowskiEngine import conventions as CV
-from .MinkowskiEngine.conv import _DT, SPLITK_WORKSPACE_BYTES
+from .MinkowskiEngine.conv import SPLITK_WORKSPACE_BYTES
+from .MinkowskiEngine.core import table_arrays
+from .MinkowskiEngine.nn import segment_pool
+from .network.PBNet import LOCAL_VOXEL, MASK_THD
+from .network.mink_unet import alloc_arena, input_slab
+from .stage_ops import CNT, OVF_NAMES          # (re-exported: the names callers of this module use)
 
-CNT = SimpleNamespace(POINTS=0, CLUSTERS=1, ENTRIES=2, ROWS=3, SCENES=4, PROPOSAL_ROWS=5, PROPOSALS=6, OVERFLOW=7, WORDS=16)
-OVF_NAMES = {1: "selected points", 2: "clusters", 4: "local-scene entries", 8: "local-scene rows",
-             16: "clusters of one (class, batch) segment", 32: "batch index outside [0, cluster_batch)", 64: "rows of a level", 128: "a segment of more than 25 clusters (torch.cdist ranks through its matrix-multiply path: host plan)"}
-MASK_THD = 0.45
-LOCAL_VOXEL = 0.02
 _DEBUG = os.environ.get("PBN_PLANNED_DEBUG", "0") == "1"
 HINTS = os.environ.get("PBN_PLANNED_HINTS", "1") != "0"      # kernel choice by the rows expected, not by the capacities
 _STOP = os.environ.get("PBN_PLANNED_STOP", "")      # debugging: end the launch sequence after the named stage
+_TRACE = _DEBUG or bool(_STOP)
 
 
-def _dbg(stage, counts=None):
-    """PBN_PLANNED_DEBUG=1: synchronise after every stage and say where the forward is (hang / fault localisation)."""
+def _stage_done(stage, counts, live):
+    """End of a stage of the launch sequence.  PBN_PLANNED_DEBUG=1: synchronise and say where the forward is (hang / fault
+    localisation).  PBN_PLANNED_STOP=<stage>: returns what `run` returns instead of going on -- the counts and, kept alive, the
+    tensors and lineages among `live` (the caller's locals)."""
     if _DEBUG:
         torch.cuda.synchronize()
-        sys.stderr.write("[planned] %s%s\n" % (stage, "" if counts is None else " counts=%s" % counts.tolist()[:8]))
+        sys.stderr.write("[planned] %s done counts=%s\n" % (stage, counts.tolist()[:8]))
         sys.stderr.flush()
+    if _STOP == stage:
+        return {"counts": counts, "_keep": {k: v for k, v in live.items() if torch.is_tensor(v) or isinstance(v, _Lineage)}}
+    return None
 
 
 class Capacities(object):
@@ -84,7 +88,8 @@ def measure_capacities(model, feat_voxel, xyz_voxel, xyz_original, v2p_index, te
 
 
 class _Lineage(object):
-    """pbn_coords_prepare(_dev) of one SparseTensor lineage into a private arena; views of what the forward needs."""
+    """pbn_coords_prepare(_dev) of one SparseTensor lineage into a private arena; views of what the forward needs.
+    n_dev: device-side count of the coordinate rows (a one-element int32 view; n_cap is then their capacity) or None."""
 
     def __init__(self, coords, n_cap, n_dev, dev):
         lib = N.lib()
@@ -95,7 +100,7 @@ class _Lineage(object):
             rc = lib.pbn_coords_prepare(N.ptr(coords), int(n_cap), 1, int(CV.X_FASTEST), N.ptr(self.arena), nbytes,
                                         ctypes.byref(self.P), N.current_stream())
         else:
-            rc = lib.pbn_coords_prepare_dev(N.ptr(coords), ctypes.c_void_p(n_dev), int(n_cap), 1, int(CV.X_FASTEST),
+            rc = lib.pbn_coords_prepare_dev(N.ptr(coords), N.ptr(n_dev), int(n_cap), 1, int(CV.X_FASTEST),
                                             N.ptr(self.arena), nbytes, ctypes.byref(self.P), N.current_stream())
         N.check(rc, "pbn_coords_prepare")
         self.n_cap = int(n_cap)
@@ -112,21 +117,14 @@ class _Lineage(object):
         return self.arena[offset:offset + nbytes].view(dtype)
 
     def tables(self):
-        base, L = self.arena.data_ptr(), self.P.pyramid
-        vp = ctypes.c_void_p
-        return ((vp * 5)(*[base + L.k3[l] for l in range(5)]), vp(base + L.k5),
-                (vp * 4)(*[base + L.nbr_down[l] for l in range(4)]), (vp * 4)(*[base + L.up[l] for l in range(4)]))
+        return table_arrays(self.arena.data_ptr(), self.P.pyramid)
 
 
 class PlannedForward(object):
     def __init__(self, model, cap, dtype=torch.bfloat16, device=None):
         self.model, self.cap, self.dtype = model, cap, dtype
         self.dev = device or next(model.parameters()).device
-        thr05, thr02 = model._class_thresholds()
-        f32 = dict(dtype=torch.float32, device=self.dev)
-        self.thr05 = torch.tensor(thr05, **f32)
-        self.thr02 = torch.tensor(thr02, **f32)
-        self.kmax = torch.tensor(model._k_max_list(), dtype=torch.int32, device=self.dev)
+        model._front_consts(self.dev)                                  # built here, not inside a capture
         self.nb = 3                                                    # PBNet.py:167-170: cluster_batch outside training
         self.graph = None
         # level capacities on the device (compared with the row counts of each pyramid; built here, not inside a capture)
@@ -134,24 +132,16 @@ class PlannedForward(object):
                         for lv in (cap.lv1, cap.lv2, cap.lv3)}
 
     # ---- helpers ----------------------------------------------------------------------------------------------------
-    def _unet(self, net, lin, cap_levels, feats, row_bytes, expect=None):
+    def _unet(self, net, lin, cap_levels, feats, expect=None):
         """Fused U-Net on a lineage: feats are the INPUT rows (before de-duplication); returns the output slab in Z-order
         [cap_levels[0], cout] and flags a level whose row count exceeds its capacity."""
         lib = N.lib()
         dt, dev = self.dtype, self.dev
-        es = torch.empty(0, dtype=dt).element_size()
         plan = net._plan(dt)
         cin_p = plan["cin_p"]
         n0 = int(cap_levels[0])
-        padded = torch.empty(n0, cin_p, dtype=dt, device=dev)
-        N.check(lib.pbn_gather_pad_rows_dev(ctypes.c_void_p(feats.data_ptr()), feats.stride(0) * es, int(row_bytes),
-                                            N.ptr(lin.perm), N.ptr(lin.unique_index), n0,
-                                            ctypes.c_void_p(lin.counts.data_ptr()), ctypes.c_void_p(padded.data_ptr()),
-                                            cin_p * es, N.current_stream()), "pbn_gather_pad_rows_dev")
-        n_rows = (ctypes.c_int32 * 5)(*[int(v) for v in cap_levels])
-        offs = (ctypes.c_int64 * plan["n_bufs"])()
-        nbytes = lib.pbn_unet_arena_bytes(plan["bufs"], plan["n_bufs"], n_rows, _DT[dt], offs)
-        arena = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        padded = input_slab(feats, cin_p, lin.perm, lin.unique_index, n0, lin.counts)
+        arena, nbytes, offs, n_rows = alloc_arena(plan["bufs"], plan["n_bufs"], cap_levels, dt, dev)
         k3, k5, down, up = lin.tables()
         # split-K scratch of THIS forward: the per-stream cache of the size-exact path must not be used here -- every graph
         # capture of a process runs on torch's one shared capture stream, so a cached block would be handed from the private
@@ -162,52 +152,31 @@ class PlannedForward(object):
             lib.pbn_unet_set_rows_hint((ctypes.c_int32 * 5)(*[max(1, min(int(e), int(c))) for e, c in zip(expect, cap_levels)]))
         N.check(lib.pbn_unet_forward_dev(plan["ops"], plan["n_ops"], plan["bufs"], plan["n_bufs"], n_rows,
                                          vp(lin.counts.data_ptr()), vp(padded.data_ptr()), cin_p, k3, k5, down, up,
-                                         vp(arena.data_ptr()), nbytes, _DT[dt], vp(ws.data_ptr()), ws.numel(),
+                                         vp(arena.data_ptr()), nbytes, N.DT[dt], vp(ws.data_ptr()), ws.numel(),
                                          N.current_stream()), "pbn_unet_forward_dev")
-        o, width = offs[plan["out_buf"]], plan["out_width"]
-        out = arena[o:o + n0 * width * es].view(dt).view(n0, width)
-        cout = net.final_sematic.kernel.shape[-1]
         self._level_overflow.append((lin.counts > self._caps_t[id(cap_levels)]).any())
-        return out if width == cout else out[:, :cout]
-
-    def _mlp(self, head, feats, idx_a, idx_b, n_cap, n_dev_ptr):
-        hp = stage_ops._HEADS.setdefault(id(head), stage_ops._HeadParams()).get(head)
-        out = torch.empty(int(n_cap), hp.n_out, dtype=feats.dtype, device=feats.device)
-        vp = ctypes.c_void_p
-        rc = N.lib().pbn_mlp_rows_dev(vp(feats.data_ptr()), feats.stride(0), int(feats.shape[0]), hp.channels, N.ptr(idx_a),
-                                      N.ptr(idx_b), int(n_cap),
-                                      vp(n_dev_ptr), N.ptr(hp.w1), N.ptr(hp.scale), N.ptr(hp.shift), N.ptr(hp.slope), hp.hidden,
-                                      N.ptr(hp.w2), N.ptr(hp.b2), hp.n_out, int(hp.sigmoid), vp(out.data_ptr()), hp.n_out,
-                                      _DT[feats.dtype], N.current_stream())
-        N.check(rc, "pbn_mlp_rows_dev")
-        return out
+        return net._output_rows(plan, arena, offs, n0, dt)
 
     # ---- the forward: launches only -------------------------------------------------------------------------------------
     def run(self, feat_voxel, xyz_voxel, xyz_original, v2p_index, teacher=None):
         """Returns capacity-sized device tensors + the device-side counts; nothing is read back."""
-        m, cap, dev, dt, lib = self.model, self.cap, self.dev, self.dtype, N.lib()
-        vp = ctypes.c_void_p
-        es = torch.empty(0, dtype=dt).element_size()
+        m, cap, dev, dt = self.model, self.cap, self.dev, self.dtype
         n_pts, n_vox, nb = cap.n_points, cap.n_voxels, self.nb
         assert feat_voxel.shape[0] == n_vox and xyz_original.shape[0] == n_pts and feat_voxel.dtype == dt
         self._level_overflow = []
         self._splitk_ws = torch.empty(SPLITK_WORKSPACE_BYTES, dtype=torch.uint8, device=dev)
         counts = torch.zeros(CNT.WORDS, dtype=torch.int32, device=dev)
-        cptr = counts.data_ptr()
-        cnt = lambda k: cptr + 4 * k
+        n_ent_d, n_rows_d, n_prop_rows_d = (counts[k:k + 1] for k in (CNT.ENTRIES, CNT.ROWS, CNT.PROPOSAL_ROWS))
         xyz = xyz_original.float().contiguous()
-        st = N.current_stream
 
         # ---- backbone + heads (PBNet.py:117-136) ----
         coords1 = xyz_voxel.to(torch.int32).contiguous()
         lin1 = _Lineage(coords1, n_vox, None, dev)
         if _STOP == "prepare1":
             return {"counts": counts, "_keep": {"lin1": lin1, "coords1": coords1}}
-        feats1 = feat_voxel.contiguous()
-        f = self._unet(m.MEUnet, lin1, cap.lv1, feats1, feats1.shape[1] * es, cap.expect["lv1"])
-        _dbg("backbone done", counts)
-        if _STOP == "backbone":
-            return {"counts": counts, "_keep": {k: v for k, v in locals().items() if torch.is_tensor(v) or isinstance(v, _Lineage)}}
+        f = self._unet(m.MEUnet, lin1, cap.lv1, feat_voxel.contiguous(), cap.expect["lv1"])
+        if _TRACE and (stop := _stage_done("backbone", counts, locals())):
+            return stop
         v2p = v2p_index.long()
         v2p_z = lin1.inv_perm[v2p]                                   # Z-order row of every point's voxel
         point_feat_p = f[v2p_z]
@@ -219,106 +188,49 @@ class PlannedForward(object):
             offset_p = teacher["offset"].to(dev, offset_p.dtype)
         sem_pred, sem_prob, table, block_hist = stage_ops.sem_argmax_table(sem_score, batch_head.contiguous(), nb)
         out = {"sem_pred_p": sem_pred, "sem_pred_score_p": sem_score, "offset_pred_p": offset_p, "counts": counts}
+        if _TRACE and (stop := _stage_done("heads", counts, locals())):
+            return stop
 
-        _dbg("heads done", counts)
-        if _STOP == "heads":
-            return {"counts": counts, "_keep": {k: v for k, v in locals().items() if torch.is_tensor(v) or isinstance(v, _Lineage)}}
-        # ---- class gate -> selection -> grouping (PBNet.py:151-179), sizes on the device ----
-        n_cls = int(m.sem_num)
-        n_seg = (n_cls - 2) * nb
-        class_base = torch.empty(n_cls, dtype=torch.int32, device=dev)
-        seg_len = torch.empty(n_seg, dtype=torch.int32, device=dev)
-        N.check(lib.pbn_class_gate(N.ptr(table), N.ptr(self.thr05), n_cls, nb, int(cap.points), n_pts, N.ptr(class_base),
-                                   N.ptr(seg_len), vp(cptr), st()), "pbn_class_gate")
-        ins_ind, ins_orig, ins_off, ins_sem = stage_ops.select_points(sem_pred, class_base, block_hist, xyz, offset_p,
-                                                                      int(cap.points))
-        res = pbnet_ops.cluster_device(ins_off, ins_orig, ins_sem, seg_len, m.radius, m.min_pts, capacity=True,
-                                      need_den=False)
+        # ---- class gate -> selection -> grouping -> local-scene plan (PBNet.py:151-234), sizes on the device ----
+        c_cap, r_cap = int(cap.clusters), int(cap.rows)
+        ins_ind, res, ent = m._front_launches(table, sem_pred, block_hist, xyz, offset_p, nb, int(cap.points), c_cap,
+                                              int(cap.entries), r_cap, counts)
+        if _TRACE and (stop := _stage_done("grouping", counts, locals())):
+            return stop
+        # ---- rows of the local scenes by one launch ----
+        point_idx, row_scene, coords2, feat2 = stage_ops.local_scene_rows(
+            ent, ent.n, r_cap, res.member_idx, ins_ind, xyz, LOCAL_VOXEL, point_feat_p, sem_prob.view(-1, 1), None,
+            n_ent_dev=n_ent_d, n_rows_dev=n_rows_d)
+        if _TRACE and (stop := _stage_done("local scene rows", counts, locals())):
+            return stop
 
-        _dbg("grouping done", counts)
-        if _STOP == "grouping":
-            return {"counts": counts, "_keep": {k: v for k, v in locals().items() if torch.is_tensor(v) or isinstance(v, _Lineage)}}
-        # ---- local scenes (PBNet.py:182-234): plan on the device, rows by one launch ----
-        c_cap, e_cap, r_cap = int(cap.clusters), int(cap.entries), int(cap.rows)
-        i32 = dict(dtype=torch.int32, device=dev)
-        ent_row_start = torch.empty(e_cap + 1, **i32)
-        ent_member_start = torch.empty(e_cap, **i32)
-        ent_scene = torch.empty(e_cap, **i32)
-        ent_weight = torch.empty(e_cap, dtype=torch.float32, device=dev)
-        wsb = int(lib.pbn_local_plan_workspace_bytes(c_cap))
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        N.check(lib.pbn_local_plan(N.ptr(res.cluster_num), n_seg, nb, N.ptr(res.member_start), N.ptr(res.centers),
-                                   N.ptr(res.n_clusters), N.ptr(self.thr02), N.ptr(self.kmax), c_cap, e_cap, r_cap,
-                                   N.ptr(ent_row_start), N.ptr(ent_member_start), N.ptr(ent_scene), N.ptr(ent_weight), vp(cptr),
-                                   N.ptr(ws), wsb, st()), "pbn_local_plan")
-        c_in = int(point_feat_p.shape[1])
-        ld2 = c_in + 2
-        point_idx = torch.empty(r_cap, dtype=torch.int64, device=dev)
-        row_scene = torch.empty(r_cap, dtype=torch.int64, device=dev)
-        coords2 = torch.empty(r_cap, 4, **i32)
-        feat2 = torch.empty(r_cap, ld2, dtype=dt, device=dev)
-        sem_prob2 = sem_prob.view(-1, 1)
-        N.check(lib.pbn_local_scene_rows_dev(
-            N.ptr(ent_row_start), N.ptr(ent_member_start), N.ptr(ent_scene), N.ptr(ent_weight), e_cap, r_cap,
-            vp(cnt(CNT.ENTRIES)), vp(cnt(CNT.ROWS)), N.ptr(res.member_idx), N.ptr(ins_ind), N.ptr(xyz),
-            stage_ops.reciprocal_f32(LOCAL_VOXEL), vp(point_feat_p.data_ptr()), point_feat_p.stride(0), c_in,
-            vp(sem_prob2.data_ptr()), sem_prob2.stride(0), None, _DT[dt], N.ptr(point_idx), N.ptr(row_scene), N.ptr(coords2),
-            vp(feat2.data_ptr()), ld2, st()), "pbn_local_scene_rows_dev")
-
-        _dbg("local scene rows done", counts)
-        if _STOP == "local scene rows":
-            return {"counts": counts, "_keep": {k: v for k, v in locals().items() if torch.is_tensor(v) or isinstance(v, _Lineage)}}
         # ---- mask branch (PBNet.py:236-252) ----
-        lin2 = _Lineage(coords2, r_cap, cnt(CNT.ROWS), dev)
-        f2 = self._unet(m.D_Unet, lin2, cap.lv2, feat2, ld2 * es, cap.expect["lv2"])
-        mask_score = self._mlp(m.linear_binary, f2, lin2.inverse, lin2.inv_perm, r_cap, cnt(CNT.ROWS))      # [r_cap, 1]
+        lin2 = _Lineage(coords2, r_cap, n_rows_d, dev)
+        f2 = self._unet(m.D_Unet, lin2, cap.lv2, feat2, cap.expect["lv2"])
+        mask_score = stage_ops.mlp_rows(m.linear_binary, f2, lin2.inverse, lin2.inv_perm, r_cap, n_dev=n_rows_d)     # [r_cap, 1]
+        if _TRACE and (stop := _stage_done("mask branch", counts, locals())):
+            return stop
 
-        _dbg("mask branch done", counts)
-        if _STOP == "mask branch":
-            return {"counts": counts, "_keep": {k: v for k, v in locals().items() if torch.is_tensor(v) or isinstance(v, _Lineage)}}
         # ---- proposals (PBNet.py:317-347) ----
-        per_scene = torch.empty(c_cap, **i32)
-        block_cnt = torch.empty(max(int(lib.pbn_select_blocks(r_cap)), 1), **i32)
-        N.check(lib.pbn_mask_count_dev(vp(mask_score.data_ptr()), 1, float(MASK_THD), N.ptr(row_scene), r_cap, vp(cnt(CNT.ROWS)),
-                                       c_cap, _DT[dt], N.ptr(per_scene), N.ptr(block_cnt), st()), "pbn_mask_count_dev")
-        proposals_offset = torch.zeros(c_cap + 1, dtype=torch.int64, device=dev)
-        alive_ids = torch.zeros(c_cap, dtype=torch.int64, device=dev)
-        dense_of = torch.empty(c_cap, **i32)
-        N.check(lib.pbn_proposal_offsets(N.ptr(per_scene), c_cap, N.ptr(proposals_offset), N.ptr(alive_ids), N.ptr(dense_of),
-                                         vp(cptr), st()), "pbn_proposal_offsets")
-        prop_idx = torch.empty(r_cap, 2, dtype=torch.int64, device=dev)
-        prop_ms = torch.empty(r_cap, dtype=dt, device=dev)
-        coords3 = torch.empty(r_cap, 4, **i32)
-        feat3 = torch.empty(r_cap, c_in, dtype=dt, device=dev)
-        N.check(lib.pbn_proposal_rows_dev(
-            vp(mask_score.data_ptr()), 1, float(MASK_THD), N.ptr(row_scene), N.ptr(point_idx), r_cap, vp(cnt(CNT.ROWS)),
-            N.ptr(dense_of), N.ptr(block_cnt), N.ptr(xyz), float(np.float32(m.scale_size)), stage_ops.reciprocal_f32(m.voxel_size),
-            vp(point_feat_p.data_ptr()), point_feat_p.stride(0), c_in, _DT[dt], N.ptr(prop_idx), vp(prop_ms.data_ptr()),
-            N.ptr(coords3), vp(feat3.data_ptr()), st()), "pbn_proposal_rows_dev")
+        per_scene, block_cnt = stage_ops.mask_count(mask_score, MASK_THD, row_scene, c_cap, n_dev=n_rows_d)
+        proposals_offset, alive_ids, dense_of = stage_ops.proposal_offsets(per_scene, counts)
+        prop_idx, prop_ms, coords3, feat3 = stage_ops.proposal_rows(
+            mask_score, MASK_THD, row_scene, point_idx, dense_of, block_cnt, r_cap, xyz, m.scale_size, m.voxel_size,
+            point_feat_p, n_dev=n_rows_d)
+        if _TRACE and (stop := _stage_done("proposals", counts, locals())):
+            return stop
 
-        _dbg("proposals done", counts)
-        if _STOP == "proposals":
-            return {"counts": counts, "_keep": {k: v for k, v in locals().items() if torch.is_tensor(v) or isinstance(v, _Lineage)}}
         # ---- score branch (PBNet.py:255-279) ----
-        lin3 = _Lineage(coords3, r_cap, cnt(CNT.PROPOSAL_ROWS), dev)
-        f3 = self._unet(m.score_Unet, lin3, cap.lv3, feat3, c_in * es, cap.expect["lv3"])
+        lin3 = _Lineage(coords3, r_cap, n_prop_rows_d, dev)
+        f3 = self._unet(m.score_Unet, lin3, cap.lv3, feat3, cap.expect["lv3"])
         n3 = int(cap.lv3[0])
-        iou_feat = self._mlp(m.linear_IOU_feat, f3, lin3.inv_perm, None, n3, lin3.counts.data_ptr())     # external row order
-        seg_start = torch.empty(c_cap + 1, **i32)
-        N.check(lib.pbn_batch_starts(N.ptr(lin3.ucoords), vp(lin3.counts.data_ptr()), n3, c_cap, N.ptr(seg_start), st()),
-                "pbn_batch_starts")
-        ch = int(iou_feat.shape[1])
-        mx = torch.empty(c_cap, ch, dtype=torch.float32, device=dev)
-        av = torch.empty(c_cap, ch, dtype=torch.float32, device=dev)
-        pws = int(lib.pbn_segment_pool_workspace_bytes(c_cap, ch))
-        pw = torch.empty(max(pws, 16), dtype=torch.uint8, device=dev)
-        N.check(lib.pbn_segment_pool(vp(iou_feat.data_ptr()), iou_feat.stride(0), ch, _DT[dt], N.ptr(seg_start), c_cap,
-                                     N.ptr(mx), N.ptr(av), vp(pw.data_ptr()), pws, st()), "pbn_segment_pool")
+        iou_feat = stage_ops.mlp_rows(m.linear_IOU_feat, f3, lin3.inv_perm, None, n3, n_dev=lin3.counts)     # external row order
+        seg_start = stage_ops.batch_starts(lin3.ucoords, n3, lin3.counts, c_cap)
+        mx, av = segment_pool(iou_feat, None, c_cap, seg_start=seg_start)
         pooled = (mx + av).to(dt)
         clt_scores = stage_ops.mlp_rows(m.linear_IOU, pooled).view(-1)
-        _dbg("score branch done", counts)
-        if _STOP == "score branch":
-            return {"counts": counts, "_keep": {k: v for k, v in locals().items() if torch.is_tensor(v) or isinstance(v, _Lineage)}}
+        if _TRACE and (stop := _stage_done("score branch", counts, locals())):
+            return stop
         # a level of one of the three pyramids that outgrew its capacity (rows were dropped): flag it
         ovf = torch.stack(self._level_overflow).any().to(torch.int32) * 64
         counts[CNT.OVERFLOW:CNT.OVERFLOW + 1] |= ovf

@@ -186,3 +186,107 @@ def test_proposal_compaction_matches_get_proposal(dtype):
     want_c = torch.cat([want_idx[:, 0:1].to(torch.int32), torch.floor(xyz[p] * scale / voxel).to(torch.int32)], 1)
     assert torch.equal(coords, want_c)
     assert torch.equal(f3, feat[p])
+
+
+N_CAP, N_SCENES, E_CAP = 1500, 12, 64
+
+
+@pytest.fixture(scope="module")
+def capacity_case():
+    """Inputs of the capacity-form test, built once per dtype: N_CAP rows of 32 channels in N_SCENES local scenes.  Everything
+    past a count is in range too (and would change the result if it were read: scores above the threshold)."""
+    made = {}
+
+    def make(dtype):
+        if dtype not in made:
+            g = torch.Generator().manual_seed(11)
+            n_points, m, n_members = 4000, 3000, 2500
+            c = dict(n_points=n_points, m=m, n_members=n_members)
+            c["xyz"] = (torch.rand(n_points, 3, generator=g) * 8 - 2).to(DEV)
+            c["point_feat"] = torch.randn(n_points, 32, generator=g).to(dtype).to(DEV)
+            c["sem_prob"] = torch.rand(n_points, 1, generator=g).to(dtype).to(DEV)
+            c["ins_ind"] = torch.randperm(n_points, generator=g)[:m].to(DEV)
+            c["member_idx"] = torch.randint(0, m, (n_members,), generator=g, dtype=torch.int32).to(DEV)
+            c["row_scene"] = torch.sort(torch.randint(0, N_SCENES, (N_CAP,), generator=g))[0].to(DEV)
+            c["point_idx"] = torch.randint(0, n_points, (N_CAP,), generator=g).to(DEV)
+            score = torch.rand(N_CAP, 1, generator=g)
+            score[c["row_scene"].cpu() == 4] = 0.1                   # a scene that dies entirely
+            c["score"] = score.to(dtype).to(DEV)
+            c["idx"] = torch.randint(0, 2000, (N_CAP,), generator=g).to(DEV)
+            c["idx2"] = torch.randperm(n_points, generator=g)[:2000].to(DEV)
+            import pbnet_amd.MinkowskiEngine as ME
+            torch.manual_seed(5)
+            c["head"] = torch.nn.Sequential(ME.MinkowskiLinear(32, 16, bias=False), ME.MinkowskiBatchNorm(16), ME.MinkowskiPReLU(),
+                                            ME.MinkowskiLinear(16, 3, bias=True)).eval().to(DEV)
+            made[dtype] = c
+        return made[dtype]
+    return make
+
+
+def _entry_tables(n, c):
+    """n rows split over at most 20 entries: (size-exact packed table, n_ent, the same entries in an E_CAP-entry table)."""
+    rng = np.random.default_rng(n)
+    n_ent = min(n, 20)
+    cuts = np.sort(rng.choice(np.arange(1, n), n_ent - 1, replace=False)) if n_ent > 1 else np.zeros(0, dtype=np.int64)
+    row_start = np.concatenate([[0], cuts, [n]]).astype(np.int32) if n_ent else np.zeros(1, dtype=np.int32)
+    sizes = np.diff(row_start)
+    cols = [row_start, np.asarray([rng.integers(0, c["n_members"] - s + 1) for s in sizes], dtype=np.int32),
+            np.sort(rng.integers(0, N_SCENES, n_ent)).astype(np.int32), rng.uniform(0.05, 1.0, n_ent).astype(np.float32).view(np.int32)]
+    wide = np.zeros(4 * E_CAP + 1, dtype=np.int32)
+    for k, col in enumerate(cols):
+        at = k * E_CAP + 1 if k else 0
+        wide[at:at + len(col)] = col
+    return torch.from_numpy(np.concatenate(cols)).to(DEV), n_ent, stage_ops.EntryTable(torch.from_numpy(wide).to(DEV), E_CAP)
+
+
+@pytest.mark.parametrize("n", [0, 1, 1025, 1500])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_capacity_form_equals_size_exact_form(capacity_case, dtype, n):
+    """The wrappers' own marshalling: each stage op on n rows (host sizes) against the same op at capacity N_CAP with the count n
+    on the device -- N_CAP crosses one 1024-row selection block and several 256-thread blocks.  Bit equality on the first n rows."""
+    c = capacity_case(dtype)
+    CNT = stage_ops.CNT
+    counts = torch.zeros(CNT.WORDS, dtype=torch.int32)
+    packed, n_ent, wide = _entry_tables(n, c)
+    counts[CNT.ENTRIES], counts[CNT.ROWS], counts[CNT.SCENES] = n_ent, n, N_SCENES      # (proposal_offsets reads SCENES)
+    counts = counts.to(DEV)
+    n_d = counts[CNT.ROWS:CNT.ROWS + 1]
+    same = lambda got, want, k: all(torch.equal(g[:k], w) for g, w in zip(got, want))
+
+    # local_scene_rows
+    common = (c["member_idx"], c["ins_ind"], c["xyz"], 0.02, c["point_feat"], c["sem_prob"], None)
+    want = stage_ops.local_scene_rows(packed, n_ent, n, *common)
+    got = stage_ops.local_scene_rows(wide, E_CAP, N_CAP, *common, n_ent_dev=counts[CNT.ENTRIES:CNT.ENTRIES + 1], n_rows_dev=n_d)
+    assert want[3].shape == (n, 34) and got[3].shape == (N_CAP, 34) and same(got, want, n)
+
+    # mlp_rows (two index levels; in_rows = the rows of the input)
+    feats = c["point_feat"]
+    want = stage_ops.mlp_rows(c["head"], feats, c["idx"][:n], c["idx2"])
+    got = stage_ops.mlp_rows(c["head"], feats, c["idx"], c["idx2"], N_CAP, n_dev=n_d, in_rows=c["n_points"])
+    assert want.shape == (n, 3) and got.shape == (N_CAP, 3) and torch.equal(got[:n], want)
+
+    # gather_pad_rows: one index, and (capacity form only) two
+    x = c["point_feat"]
+    want = stage_ops.gather_pad_rows(x, 40, c["idx"][:n])
+    got = stage_ops.gather_pad_rows(x, 40, c["idx"], None, N_CAP, n_d)
+    assert want.shape == (n, 40) and torch.equal(got[:n], want) and torch.equal(want[:, :32], x[c["idx"][:n]]) and not want[:, 32:].any()
+    got = stage_ops.gather_pad_rows(x, 40, c["idx"], c["idx2"], N_CAP, n_d)
+    assert torch.equal(got[:n], stage_ops.gather_pad_rows(x, 40, c["idx2"][c["idx"][:n]]))
+
+    # mask_count -> proposal_offsets -> proposal_rows; the size-exact form takes its offsets from the host (PBNet._proposals_fused)
+    thd, rs, pi, sc = 0.45, c["row_scene"], c["point_idx"], c["score"]
+    per_scene, block_cnt = stage_ops.mask_count(sc[:n], thd, rs[:n], N_SCENES)
+    per_scene_h = per_scene.cpu().long()
+    alive = per_scene_h > 0
+    total, n_alive = int(per_scene_h.sum()), int(alive.sum())
+    dense_of = (torch.cumsum(alive.to(torch.int32), 0) - 1).to(torch.int32).to(DEV)
+    want = stage_ops.proposal_rows(sc[:n], thd, rs[:n], pi[:n], dense_of, block_cnt, total, c["xyz"], 1, 0.02, c["point_feat"])
+    per_scene_c, block_cnt_c = stage_ops.mask_count(sc, thd, rs, N_SCENES, n_dev=n_d)
+    assert torch.equal(per_scene_c, per_scene)
+    offsets, alive_ids, dense_of_c = stage_ops.proposal_offsets(per_scene_c, counts)
+    got = stage_ops.proposal_rows(sc, thd, rs, pi, dense_of_c, block_cnt_c, N_CAP, c["xyz"], 1, 0.02, c["point_feat"], n_dev=n_d)
+    h = counts.cpu().tolist()
+    assert h[CNT.PROPOSAL_ROWS] == total and h[CNT.PROPOSALS] == n_alive and h[CNT.OVERFLOW] == 0
+    assert torch.equal(offsets[:n_alive + 1].cpu(), torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(per_scene_h[alive], 0)]))
+    assert torch.equal(alive_ids[:n_alive].cpu(), torch.nonzero(alive).view(-1))
+    assert got[0].shape == (N_CAP, 2) and same(got, want, total)
