@@ -733,6 +733,45 @@ int pbn_sem_confusion(const void* pred, int pred_i64, const void* target, int ta
 int pbn_mask_accuracy(const void* pred_mask, int dtype, const void* gt_mask, int gt_i64, int64_t n, float threshold,
                       int64_t* row8, pbn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Training losses (csrc/losses.hip): the seven terms of model_fn (network/PBNet.py:366-416, diceLoss :463-468) in one
+ * forward call and their gradients in one backward call.  Float32 arithmetic per row, float64 sums through per-workgroup
+ * partials in the workspace (grids depend on the row counts only, no floating-point atomics: the same inputs give the same
+ * bits).  Asynchronous, no host synchronisation.  Every *_dtype is PBN_F32 / PBN_BF16 / PBN_F16.
+ *   points   sem_score [n_points, n_class] with leading dimension sem_ld, sem_label / ins_label int64 (-100 = ignore),
+ *            offset_pred [n_points, 3], inst_info f32[n_points, 9] (columns 0-2 used), xyz f32[n_points, 3]
+ *   mask     pred_mask [n_rows], gt_mask int64[n_rows] with -1 = ignore.  n_rows < 0: only the three point terms exist
+ *            (below cluster_epoch) and no mask / proposal argument is read
+ *   scores   iou f32[n_prop, n_inst] as pbn_get_iou writes it, clt_scores [n_prop]
+ * Return codes, all before any launch: PBN_ERR_ARG (a null required pointer, a misaligned one, a negative n_points / n_prop,
+ * n_class outside [2, 64], sem_ld < n_class), PBN_ERR_UNSUPPORTED (an unknown dtype), PBN_ERR_WORKSPACE (workspace too small).
+ * ------------------------------------------------------------------------------------------------------------ */
+size_t pbn_losses_workspace_bytes(int64_t n_points, int64_t n_rows, int64_t n_prop);
+/* terms f32[8] = semantic, offset_norm, offset_dir, mask, dice, score, loss (their sum), 0.  counts int64[4] = rows with
+ * ins_label != -100, rows with gt_mask != -1, rows with a class label, rows whose label is neither -100 nor in [0, n_class)
+ * (such a row is ignored and never used as an index).  state f64[8]: what the backward needs (n_keep, n_valid + 1e-6, R,
+ * 2A + 1, U, P).  gt_mask is REWRITTEN with -1 -> 0 (the reference assigns 0.5 in place into a long tensor) and mask_weight
+ * u8[n_rows] receives gt_mask != -1; gt_scores f32[n_prop] = get_segmented_scores(max_i iou[p, i], fg, bg), bit for bit.
+ * An empty mean (no class label, n_rows = 0, n_prop = 0) is 0 / 0 = NaN, as torch's.  Unlike torch, a NaN in `iou` is dropped
+ * by the row maximum and a NaN pred_mask on an ignored row stays out of the mask term (neither arises from pbn_get_iou or
+ * from sigmoid scores).  workspace: 16-byte aligned. */
+int pbn_losses_forward(const void* sem_score, int sem_dtype, int sem_ld, const int64_t* sem_label, const void* offset_pred,
+                       int offset_dtype, const float* inst_info, const float* xyz, const int64_t* ins_label, int64_t n_points,
+                       int n_class, const void* pred_mask, int mask_dtype, int64_t* gt_mask, uint8_t* mask_weight,
+                       int64_t n_rows, const float* iou, int n_inst, const void* clt_scores, int clt_dtype, int64_t n_prop,
+                       double fg_thresh, double bg_thresh, float* gt_scores, float* terms, int64_t* counts, double* state,
+                       void* workspace, size_t workspace_bytes, pbn_stream_t stream);
+/* d terms[6] / d (sem_score, offset_pred, pred_mask, clt_scores) times the DEVICE scalar *grad_loss, each written once in its
+ * input's dtype: g_sem [n_points, n_class] (contiguous), g_offset [n_points, 3], g_mask [n_rows], g_clt [n_prop].  Inputs as
+ * the forward left them (gt_mask rewritten, mask_weight, gt_scores, state); nothing of size n_points x n_class is kept
+ * between the calls: the softmax is recomputed. */
+int pbn_losses_backward(const void* sem_score, int sem_dtype, int sem_ld, const int64_t* sem_label, const void* offset_pred,
+                        int offset_dtype, const float* inst_info, const float* xyz, const int64_t* ins_label, int64_t n_points,
+                        int n_class, const void* pred_mask, int mask_dtype, const int64_t* gt_mask, const uint8_t* mask_weight,
+                        int64_t n_rows, const void* clt_scores, int clt_dtype, const float* gt_scores, int64_t n_prop,
+                        const double* state, const float* grad_loss, void* g_sem, void* g_offset, void* g_mask, void* g_clt,
+                        pbn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -216,6 +216,12 @@ SIGNATURES = {
     "pbn_mesh_segment_point": (c_int, [c_f32p, c_f32p, c_int, c_vp, c_int, c_int, c_float, c_int, c_vp, c_vp, c_size, c_vp]),
     "pbn_sem_confusion": (c_int, [c_vp, c_int, c_vp, c_int, c_i64, c_int, c_int, c_vp, c_vp, c_vp]),
     "pbn_mask_accuracy": (c_int, [c_vp, c_int, c_vp, c_int, c_i64, c_float, c_vp, c_vp]),
+    "pbn_losses_workspace_bytes": (c_size, [c_i64, c_i64, c_i64]),
+    "pbn_losses_forward": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_f32p, c_f32p, c_vp, c_i64, c_int, c_vp, c_int, c_vp,
+                                   c_vp, c_i64, c_f32p, c_int, c_vp, c_int, c_i64, ctypes.c_double, ctypes.c_double, c_f32p,
+                                   c_f32p, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "pbn_losses_backward": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_f32p, c_f32p, c_vp, c_i64, c_int, c_vp, c_int, c_vp,
+                                    c_vp, c_i64, c_vp, c_int, c_f32p, c_i64, c_vp, c_f32p, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 PBN_OK, PBN_ERR_ARG, PBN_ERR_WORKSPACE, PBN_ERR_HIP, PBN_ERR_RANGE, PBN_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5

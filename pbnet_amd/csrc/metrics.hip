@@ -12,9 +12,8 @@
 // tools/mIOU.py bins with histc(bins=K, min=0, max=K-1): the integer v lands in bin floor(v * K / (K - 1)), which is v for
 // 0 <= v < K - 1 (v / (K - 1) < 1) and the clamped last bin for v = K - 1, and nowhere for v outside [0, K - 1]: the
 // identity on [0, K).  K = 1 would make min == max, where histc takes its range from the data instead: refused.
-#include <hip/hip_fp16.h>
-
 #include "pbn_common.h"
+#include "vec4_dev.h"
 
 namespace pbn {
 namespace {
@@ -25,44 +24,6 @@ constexpr int GRID_CAP = 1024;              // 4 workgroups per CU on 256 CUs; b
 constexpr int MIN_ITERS = 4;                // a workgroup is worth starting for 4 * 1024 points
 constexpr long long CHUNK = 1LL << 36;      // points per launch (a multiple of 4)
 constexpr int MASK_DIRECT_MAX = 65536;      // rows one workgroup reduces alone (no zero fill, plain stores)
-
-// four consecutive elements: one or two aligned vector loads, or four scalar loads
-__device__ __forceinline__ void load4(const int* p, bool vec, int (&v)[4]) {
-    if (vec) {
-        const int4 q = *reinterpret_cast<const int4*>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = p[j];
-    }
-}
-__device__ __forceinline__ void load4(const long long* p, bool vec, long long (&v)[4]) {
-    if (vec) {
-        const longlong2 a = *reinterpret_cast<const longlong2*>(p), b = *reinterpret_cast<const longlong2*>(p + 2);
-        v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = p[j];
-    }
-}
-__device__ __forceinline__ void load4(const float* p, bool vec, float (&v)[4]) {
-    if (vec) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = p[j];
-    }
-}
-__device__ __forceinline__ void load4(const unsigned short* p, bool vec, unsigned short (&v)[4]) {
-    if (vec) {
-        const ushort4 q = *reinterpret_cast<const ushort4*>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = p[j];
-    }
-}
 
 // LDS: `copies` private histograms of C = 3K (+ K*K) counters: intersection | output | target | confusion[target][pred].
 template <typename TP, typename TT>
@@ -114,37 +75,19 @@ __global__ __launch_bounds__(TPB) void k_sem_confusion(const TP* __restrict__ pr
     }
 }
 
-template <int DT>
-struct MaskScore;
-template <>
-struct MaskScore<PBN_F32> {
-    typedef float T;
-    static __device__ __forceinline__ float widen(float v) { return v; }
-};
-template <>
-struct MaskScore<PBN_BF16> {
-    typedef unsigned short T;
-    static __device__ __forceinline__ float widen(unsigned short v) { return __uint_as_float((unsigned)v << 16); }
-};
-template <>
-struct MaskScore<PBN_F16> {
-    typedef unsigned short T;
-    static __device__ __forceinline__ float widen(unsigned short v) { return __half2float(__ushort_as_half(v)); }
-};
-
 // row8 = rows seen, agree, n_pos, pos_pred1, n_neg, neg_pred1, n_nan, 0.  direct: ONE workgroup, plain stores; otherwise
 // the row was zeroed before the launch and every workgroup adds its non-zero sums.
 template <int DT, typename TG>
-__global__ __launch_bounds__(TPB) void k_mask_accuracy(const typename MaskScore<DT>::T* __restrict__ pred,
+__global__ __launch_bounds__(TPB) void k_mask_accuracy(const typename Elem<DT>::T* __restrict__ pred,
                                                       const TG* __restrict__ gt, long long n, int head, int vec_p, int vec_g,
                                                       float threshold, int direct, unsigned long long* __restrict__ row8) {
-    typedef typename MaskScore<DT>::T TP;
+    typedef typename Elem<DT>::T TP;
     __shared__ int part[WAVES][8];
     const int tid = (int)threadIdx.x;
     int c[7] = {0, 0, 0, 0, 0, 0, 0};
 
     auto count = [&](TP raw, long long g) {
-        const float v = MaskScore<DT>::widen(raw);
+        const float v = Elem<DT>::widen(raw);
         const bool nan = v != v;
         const bool one = v >= threshold;                   // train.py:155 `>=`: exactly the threshold is 1
         const bool pos = g == 1, neg = g == 0;
@@ -189,19 +132,6 @@ __global__ __launch_bounds__(TPB) void k_mask_accuracy(const typename MaskScore<
     }
 }
 
-// The 0-3 leading points after which the most bytes per group come from aligned vector loads.  A group of array X loads as
-// vectors when its address is a multiple of min(16, 4 * element size).
-int pick_head(uintptr_t a, int es_a, uintptr_t b, int es_b, int* vec_a, int* vec_b) {
-    const int al_a = 4 * es_a < 16 ? 4 * es_a : 16, al_b = 4 * es_b < 16 ? 4 * es_b : 16;
-    int best = 0, best_score = -1;
-    for (int h = 0; h < 4; ++h) {
-        const int va = (a + (uintptr_t)h * es_a) % al_a == 0, vb = (b + (uintptr_t)h * es_b) % al_b == 0;
-        const int score = va * es_a + vb * es_b;
-        if (score > best_score) { best = h; best_score = score; *vec_a = va; *vec_b = vb; }
-    }
-    return best;
-}
-
 int grid_for(long long n) {
     const long long want = (n / 4 + (long long)TPB * MIN_ITERS - 1) / ((long long)TPB * MIN_ITERS);
     return (int)(want < 1 ? 1 : (want > GRID_CAP ? GRID_CAP : want));
@@ -229,7 +159,7 @@ int launch_sem(const void* pred, const void* target, int64_t n, int K, int ignor
 
 template <int DT, typename TG>
 int launch_mask(const void* pred, const void* gt, int64_t n, float threshold, int64_t* row8, hipStream_t stream) {
-    typedef typename MaskScore<DT>::T TP;
+    typedef typename Elem<DT>::T TP;
     const int direct = n <= MASK_DIRECT_MAX;
     if (!direct) {
         const int rc = fill_bytes(row8, 0, 8 * sizeof(int64_t), stream);

@@ -649,8 +649,9 @@ def model_losses(ret, sem_label, ins_label, instance_info, instance_pointnum, xy
 
 
 def model_fn(batch, model, epoch, cfg, task="train"):
-    """PBNet.py:349-444: forward + losses.  Losses are plain torch on the device (outside the kernel scope); their
-    arithmetic is restated independently in oracle/loss_ref.py and compared in tests/test_losses.py."""
+    """PBNet.py:349-444: forward + losses.  Losses are plain torch on the device by default (model_losses; its arithmetic
+    is restated independently in oracle/loss_ref.py and compared in tests/test_losses.py); cfg.native_losses = True
+    computes the same terms and gradients in csrc/losses.hip (pbnet_amd/losses.py, tests/test_losses_native_gpu.py)."""
     xyz_original = batch["xyz_original"].cuda()
     ins_label = batch["ins"].cuda()
     ret = model(batch["feat_voxel"], batch["xyz_voxel"], xyz_original, batch["v2p_index"], ins_label, epoch, task)
@@ -658,8 +659,12 @@ def model_fn(batch, model, epoch, cfg, task="train"):
     instance_info = batch["inst_info"].cuda()
     instance_pointnum = batch["instance_pointnum"].cuda()
     offset_pred_p, sem_pred_p = ret["offset_pred_p"].float(), ret["sem_pred_p"]
-    loss, parts, valid, weight, gt_mask = model_losses(ret, sem_label, ins_label, instance_info, instance_pointnum,
-                                                       xyz_original.float(), epoch, cfg)
+    if getattr(cfg, "native_losses", False):                       # one forward and one backward launch group (pbnet_amd/losses.py)
+        from ..losses import model_losses_native as losses_fn
+    else:
+        losses_fn = model_losses
+    loss, parts, valid, weight, gt_mask = losses_fn(ret, sem_label, ins_label, instance_info, instance_pointnum,
+                                                    xyz_original.float(), epoch, cfg)
     with torch.no_grad():
         pred = {"sem": sem_pred_p, "offseted_xyz": xyz_original + offset_pred_p}
         # the logged terms in ONE read-back (the reference calls .item() per term: five synchronisations)
