@@ -267,14 +267,25 @@ def _pad_vec(v, cout_p, fill):
 WGRAD_PAIR_SEGMENT = 4096         # rule pairs per batched-GEMM segment of the compacted weight gradient
 
 
-def _gather_rows(src, idx):
-    """out[i] = src[idx[i]] (zero row for idx < 0), 16-byte rows, one launch (pbn_gather_rows)."""
-    es = src.element_size()
-    out = torch.empty(idx.shape[0], src.shape[1], dtype=src.dtype, device=src.device)
-    N.check(N.lib().pbn_gather_rows(N.c_vp(src.data_ptr()), src.stride(0) * es, N.ptr(idx), int(idx.shape[0]),
-                                    src.shape[1] * es, N.c_vp(out.data_ptr()), src.shape[1] * es, N.current_stream()),
-            "pbn_gather_rows")
-    return out
+def _pair_lists(dev, n_seg, segment):
+    """in_idx, out_idx int32 [n_seg * segment] and seg_offset int64 [n_seg] of a map's pair lists, uninitialised."""
+    return (torch.empty(n_seg * segment, dtype=torch.int32, device=dev), torch.empty(n_seg * segment, dtype=torch.int32, device=dev),
+            torch.empty(n_seg, dtype=torch.int64, device=dev))
+
+
+def _pair_buffers(nbr, segment, worst_case=True):
+    """Validate a map and allocate what the pbn_rulebook_pair_* launches fill: (rows, offsets, per-block count table, pair
+    totals per offset) and, with `worst_case`, the lists sized without a read-back (rows x offsets / segment + offsets
+    segments): + (in_idx, out_idx, seg_offset, seg_begin [offsets + 1])."""
+    N.require_cuda(nbr)
+    assert nbr.dtype == torch.int32 and nbr.is_contiguous()
+    v, k = int(nbr.shape[0]), int(nbr.shape[1])
+    dev = nbr.device
+    table = torch.empty(max(N.lib().pbn_rulebook_pair_blocks(v), 1) * k, dtype=torch.int32, device=dev)
+    totals = torch.empty(k, dtype=torch.int32, device=dev)
+    if not worst_case:
+        return v, k, table, totals
+    return (v, k, table, totals) + _pair_lists(dev, (v * k) // segment + k, segment) + (torch.empty(k + 1, dtype=torch.int32, device=dev),)
 
 
 def rulebook_pairs(nbr, segment=WGRAD_PAIR_SEGMENT):
@@ -284,24 +295,15 @@ def rulebook_pairs(nbr, segment=WGRAD_PAIR_SEGMENT):
     hit = getattr(nbr, "_pbn_pairs", None)
     if hit is not None and hit[4] == segment:
         return hit[:4]
-    N.require_cuda(nbr)
-    assert nbr.dtype == torch.int32 and nbr.is_contiguous()
-    lib = N.lib()
-    v, k = int(nbr.shape[0]), int(nbr.shape[1])
-    dev = nbr.device
-    table = torch.empty(max(lib.pbn_rulebook_pair_blocks(v), 1) * k, dtype=torch.int32, device=dev)
-    totals = torch.empty(k, dtype=torch.int32, device=dev)
-    st = N.current_stream()
+    v, k, table, totals = _pair_buffers(nbr, segment, worst_case=False)
+    lib, st = N.lib(), N.current_stream()
     N.check(lib.pbn_rulebook_pair_counts(N.ptr(nbr), v, k, N.ptr(table), N.ptr(totals), st), "pbn_rulebook_pair_counts")
     cnt = totals.cpu().numpy().astype(np.int64)                                  # the one read-back
     segs = (cnt + segment - 1) // segment
     seg_begin = np.concatenate([[0], np.cumsum(segs)]).astype(np.int32)        # [K+1]
-    seg_start = seg_begin[:-1]
     n_seg = int(segs.sum())
-    in_idx = torch.empty(n_seg * segment, dtype=torch.int32, device=dev)
-    out_idx = torch.empty(n_seg * segment, dtype=torch.int32, device=dev)
-    seg_offset = torch.empty(n_seg, dtype=torch.int64, device=dev)
-    seg_begin_d = torch.from_numpy(seg_begin).to(dev)
+    in_idx, out_idx, seg_offset = _pair_lists(nbr.device, n_seg, segment)
+    seg_begin_d = torch.from_numpy(seg_begin).to(nbr.device)
     N.check(lib.pbn_rulebook_pair_fill(N.ptr(nbr), v, k, N.ptr(table), N.ptr(seg_begin_d), segment,
                                        n_seg, N.ptr(in_idx), N.ptr(out_idx), N.ptr(seg_offset), st), "pbn_rulebook_pair_fill")
     hit = (in_idx, out_idx, seg_offset, n_seg, segment, seg_begin_d, totals)
@@ -320,20 +322,9 @@ def rulebook_pairs_dev(nbr, segment=WGRAD_PAIR_SEGMENT):
     hit = getattr(nbr, "_pbn_pairs_dev", None)
     if hit is not None and hit[4] == segment:
         return hit[:4]
-    N.require_cuda(nbr)
-    assert nbr.dtype == torch.int32 and nbr.is_contiguous()
-    lib = N.lib()
-    v, k = int(nbr.shape[0]), int(nbr.shape[1])
-    dev = nbr.device
-    table = torch.empty(max(lib.pbn_rulebook_pair_blocks(v), 1) * k, dtype=torch.int32, device=dev)
-    totals = torch.empty(k, dtype=torch.int32, device=dev)
-    st = N.current_stream()
+    v, k, table, totals, in_idx, out_idx, seg_offset, seg_begin = _pair_buffers(nbr, segment)
+    lib, st = N.lib(), N.current_stream()
     N.check(lib.pbn_rulebook_pair_counts(N.ptr(nbr), v, k, N.ptr(table), N.ptr(totals), st), "pbn_rulebook_pair_counts")
-    cap = (v * k) // segment + k
-    in_idx = torch.empty(cap * segment, dtype=torch.int32, device=dev)
-    out_idx = torch.empty(cap * segment, dtype=torch.int32, device=dev)
-    seg_offset = torch.empty(cap, dtype=torch.int64, device=dev)
-    seg_begin = torch.empty(k + 1, dtype=torch.int32, device=dev)
     N.check(lib.pbn_rulebook_pair_fill_dev(N.ptr(nbr), v, k, N.ptr(table), N.ptr(totals), segment, N.ptr(seg_begin),
                                            N.ptr(in_idx), N.ptr(out_idx), N.ptr(seg_offset), st), "pbn_rulebook_pair_fill_dev")
     hit = (in_idx, out_idx, seg_begin, totals, segment)
@@ -348,29 +339,17 @@ def rulebook_pairs_dev_multi(maps, segment=WGRAD_PAIR_SEGMENT):
     """rulebook_pairs_dev of several maps in three launches (pbn_rulebook_pairs_multi; maps whose lists exist are skipped);
     the results are cached on the map tensors exactly as rulebook_pairs_dev caches them."""
     todo = [m for m in maps if getattr(m, "_pbn_pairs_dev", None) is None or m._pbn_pairs_dev[4] != segment]
-    lib = N.lib()
     for i in range(0, len(todo), 16):
         group = todo[i:i + 16]
         jobs = (N.PairJob * len(group))()
         keep = []
-        for j, nbr in enumerate(group):
-            N.require_cuda(nbr)
-            assert nbr.dtype == torch.int32 and nbr.is_contiguous()
-            v, k = int(nbr.shape[0]), int(nbr.shape[1])
-            dev = nbr.device
-            table = torch.empty(max(lib.pbn_rulebook_pair_blocks(v), 1) * k, dtype=torch.int32, device=dev)
-            totals = torch.empty(k, dtype=torch.int32, device=dev)
-            cap = (v * k) // segment + k
-            in_idx = torch.empty(cap * segment, dtype=torch.int32, device=dev)
-            out_idx = torch.empty(cap * segment, dtype=torch.int32, device=dev)
-            seg_offset = torch.empty(cap, dtype=torch.int64, device=dev)
-            seg_begin = torch.empty(k + 1, dtype=torch.int32, device=dev)
-            q = jobs[j]
+        for q, nbr in zip(jobs, group):
+            v, k, table, totals, in_idx, out_idx, seg_offset, seg_begin = _pair_buffers(nbr, segment)
             q.nbr, q.n, q.n_offsets = nbr.data_ptr(), v, k
             q.table, q.totals, q.seg_begin = table.data_ptr(), totals.data_ptr(), seg_begin.data_ptr()
             q.in_idx, q.out_idx, q.seg_offset = in_idx.data_ptr(), out_idx.data_ptr(), seg_offset.data_ptr()
             keep.append((nbr, (in_idx, out_idx, seg_begin, totals, segment), table, seg_offset))
-        N.check(lib.pbn_rulebook_pairs_multi(jobs, len(group), segment, N.current_stream()), "pbn_rulebook_pairs_multi")
+        N.check(N.lib().pbn_rulebook_pairs_multi(jobs, len(group), segment, N.current_stream()), "pbn_rulebook_pairs_multi")
         for nbr, hit, _, _ in keep:
             nbr._pbn_pairs_dev = hit
     return [m._pbn_pairs_dev[:4] for m in maps]
@@ -410,10 +389,6 @@ def wgrad_native(feats, grad_out, nbr, cin, cout):
     return dw
 
 
-def _wgrad(feats, grad_out, nbr, cin, cout):
-    return wgrad_native(feats, grad_out, nbr, cin, cout)
-
-
 class _ConvFn(torch.autograd.Function):
     """Sparse convolution with autograd.  forward / dgrad run on the implicit-GEMM kernel (the input gradient of an
     output-stationary table is the same kind of table: the mirrored offset of the same map for odd kernels, the up table
@@ -442,7 +417,7 @@ class _ConvFn(torch.autograd.Function):
             gi = spconv_forward(grad_out, ctx.dgrad_nbr, feats.shape[0], packed)
             grad_feats = gi if gi.shape[1] == feats.shape[1] else gi[:, :feats.shape[1]]
         if ctx.needs_input_grad[1]:
-            grad_kernel = _wgrad(feats, grad_out, ctx.nbr, cin, cout).to(kernel.dtype).view_as(kernel)
+            grad_kernel = wgrad_native(feats, grad_out, ctx.nbr, cin, cout).to(kernel.dtype).view_as(kernel)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             grad_bias = grad_out.float().sum(0, keepdim=True)
         return grad_feats, grad_kernel, grad_bias, None, None, None, None, None

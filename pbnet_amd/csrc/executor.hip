@@ -10,6 +10,7 @@
 #include <cstring>
 #include "pbn_common.h"
 #include "spconv_common.h"
+#include "unet_plan.h"
 
 using namespace pbn;
 
@@ -203,8 +204,6 @@ extern "C" int pbn_coords_prepare_hash(const int32_t* coords, const int32_t* n_d
     return coords_prepare_impl(coords, n_dev, n_cap, want_k5, x_fastest, arena, arena_bytes, P, stream, true);
 }
 
-static inline int esize(int dtype) { return dtype == PBN_F32 ? 4 : 2; }
-
 extern "C" size_t pbn_unet_arena_bytes(const pbn_unet_buf* bufs, int n_bufs, const int32_t* n_rows, int dtype,
                                        int64_t* buf_offsets) {
     if (!bufs || !n_rows || n_bufs < 1) return 0;
@@ -243,41 +242,31 @@ static int unet_forward_impl(const pbn_unet_op* ops, int n_ops, const pbn_unet_b
     int64_t offs[512];
     if (pbn_unet_arena_bytes(bufs, n_bufs, n_rows, dtype, offs) > arena_bytes) return PBN_ERR_WORKSPACE;
     const int es = esize(dtype);
-    char* A = (char*)arena;
     struct RsGuard { ~RsGuard() { g_rows_hint = 0; } } rs_guard;   // cleared on every return path
-    auto base = [&](int b) -> char* { return b == 0 ? (char*)input : A + offs[b]; };
-    auto ld = [&](int b) -> int { return b == 0 ? ld_input : bufs[b].width; };
+    const PlanArena B(arena, offs, bufs, input, ld_input, es);
+    const MapTables T{k3, k5, down, up};
     for (int i = 0; i < n_ops; ++i) {
         const pbn_unet_op& o = ops[i];
-        if (o.in_buf < 0 || o.in_buf >= n_bufs || o.out_buf < 1 || o.out_buf >= n_bufs || o.res_buf >= n_bufs ||
-            o.level_in < 0 || o.level_in > 4 || o.level_out < 0 || o.level_out > 4)
-            return PBN_ERR_ARG;
-        const int32_t* nbr = nullptr;
-        int K = 1;
-        switch (o.map_kind) {
-            case 0: break;
-            case 1: nbr = k3[o.level_out]; K = 27; break;
-            case 2: nbr = k5; K = 125; break;
-            case 3: nbr = down[o.level_in]; K = 8; break;   // level_in = fine level
-            case 4: nbr = up[o.level_out]; K = 8; break;    // level_out = fine level
-            default: return PBN_ERR_ARG;
-        }
-        if (o.map_kind != 0 && !nbr) return PBN_ERR_ARG;
-        const void* in = base(o.in_buf) + (size_t)o.in_col * es;
-        void* out = base(o.out_buf) + (size_t)o.out_col * es;
-        const void* res = o.res_buf >= 0 ? base(o.res_buf) + (size_t)o.res_col * es : nullptr;
+        if (!op_index_ok(o.in_buf, o.res_buf, o.out_buf, o.level_in, o.level_out, n_bufs)) return PBN_ERR_ARG;
+        const OpTables m = op_tables(o.map_kind, o.level_in, o.level_out, T);
+        if (!m.ok) return PBN_ERR_ARG;
+        const int32_t* nbr = m.fwd;
+        const int K = m.K;
+        const void* in = B.at(o.in_buf, o.in_col);
+        void* out = B.at(o.out_buf, o.out_col);
+        const void* res = o.res_buf >= 0 ? B.at(o.res_buf, o.res_col) : nullptr;
         // the NEXT op's packed weights are touched by this op's workgroups (spconv_common.h: prefetch_next_weights)
         g_next_weights = NextWeights{nullptr, 0, 0, 0, 0};
         static const int pf_env = getenv("PBN_CONV_PREFETCH") ? atoi(getenv("PBN_CONV_PREFETCH")) : 0;   // (off by default: nothing to describe)
         if (pf_env && i + 1 < n_ops) {
             const pbn_unet_op& q = ops[i + 1];
-            if (q.in_buf >= 0 && q.in_buf < n_bufs && q.level_in >= 0 && q.level_in <= 4 && q.level_out >= 0 && q.level_out <= 4 && q.w) {
+            if (op_index_ok(q.in_buf, q.res_buf, q.out_buf, q.level_in, q.level_out, n_bufs) && q.w) {
                 ConvArgs nx;
                 memset(&nx, 0, sizeof(nx));
-                nx.K = q.map_kind == 0 ? 1 : (q.map_kind == 1 ? 27 : (q.map_kind == 2 ? 125 : 8));
+                nx.K = op_tables(q.map_kind, q.level_in, q.level_out, T).K;
                 nx.vpo = q.vpo; nx.n_steps = q.n_steps; nx.ntiles_total = q.cout_p / 16; nx.n_out = nx.n_sel = n_rows[q.level_out];
                 nx.w_bytes = (unsigned)((unsigned long long)q.n_steps * (q.cout_p / 16) * 1024ull);
-                nx.in_bytes = (unsigned)((unsigned long long)n_rows[q.level_in] * ld(q.in_buf) * es);
+                nx.in_bytes = (unsigned)((unsigned long long)n_rows[q.level_in] * B.ld(q.in_buf) * es);
                 LaunchDesc d;
                 describe_launch(nx, dtype, &d);
                 g_next_weights = NextWeights{q.w, q.n_steps, q.cout_p / 16, d.wave_family ? d.nt : 0, d.wmajor ? d.groups : 0};
@@ -288,17 +277,17 @@ static int unet_forward_impl(const pbn_unet_op* ops, int n_ops, const pbn_unet_b
         int rc = PBN_ERR_UNSUPPORTED;
         if (o.in2_buf >= 0) {           // a BasicBlock's 1x1 shortcut folded into this convolution's reduction
             if (o.in2_buf >= n_bufs) return PBN_ERR_ARG;
-            const void* in2 = base(o.in2_buf) + (size_t)o.in2_col * es;
-            rc = pbn_spconv_forward_dual(in, ld(o.in_buf), n_rows[o.level_in], nbr, K,
+            const void* in2 = B.at(o.in2_buf, o.in2_col);
+            rc = pbn_spconv_forward_dual(in, B.ld(o.in_buf), n_rows[o.level_in], nbr, K,
                                          n_rows_dev ? n_rows_dev + o.level_out : nullptr, n_rows[o.level_out], o.w, o.vpo,
-                                         o.n_steps, o.cout_p, o.scale, o.shift, res, o.res_buf >= 0 ? ld(o.res_buf) : 0, o.relu,
-                                         out, ld(o.out_buf), dtype, 0, splitk_ws, splitk_bytes, in2, ld(o.in2_buf),
+                                         o.n_steps, o.cout_p, o.scale, o.shift, res, o.res_buf >= 0 ? B.ld(o.res_buf) : 0, o.relu,
+                                         out, B.ld(o.out_buf), dtype, 0, splitk_ws, splitk_bytes, in2, B.ld(o.in2_buf),
                                          n_rows[o.level_out], o.vpo2, stream);
         } else
-            rc = pbn_spconv_forward(in, ld(o.in_buf), n_rows[o.level_in], nbr, K, nullptr,
+            rc = pbn_spconv_forward(in, B.ld(o.in_buf), n_rows[o.level_in], nbr, K, nullptr,
                                     n_rows_dev ? n_rows_dev + o.level_out : nullptr, n_rows[o.level_out], o.w, o.vpo,
-                                    o.n_steps, o.cout_p, o.scale, o.shift, res, o.res_buf >= 0 ? ld(o.res_buf) : 0,
-                                    o.relu, out, ld(o.out_buf), dtype, 0, splitk_ws, splitk_bytes, stream);
+                                    o.n_steps, o.cout_p, o.scale, o.shift, res, o.res_buf >= 0 ? B.ld(o.res_buf) : 0,
+                                    o.relu, out, B.ld(o.out_buf), dtype, 0, splitk_ws, splitk_bytes, stream);
         g_next_weights = NextWeights{nullptr, 0, 0, 0, 0};
         if (rc != PBN_OK) return rc;
         if (events) PBN_HIP_CHECK(hipEventRecord(events[2 * i + 1], (hipStream_t)stream));

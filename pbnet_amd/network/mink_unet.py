@@ -10,6 +10,10 @@ Two execution paths over the same parameters:
     its epilogue together with ReLU and the residual add; skip concatenations are written in place (the encoder
     block stores its result directly into the right-hand columns of the decoder's concat slab, the transposed
     convolution into the left-hand columns), so no activation is touched twice.
+
+The body's topology is stated twice: _forward_modules (the reference-shaped one) and walk_body, the one walk that the
+inference plan (_build_plan), the training plan (train_engine.TrainPlan) and the Python-issued cross-check
+(_forward_fused_py) all consume.
 """
 import ctypes
 import operator
@@ -21,7 +25,7 @@ import torch.nn as nn
 from .. import _native as N
 from .. import stage_ops
 from .. import MinkowskiEngine as ME
-from ..MinkowskiEngine.conv import spconv_forward, _pad_vec
+from ..MinkowskiEngine.conv import spconv_forward, pack_weight, _pad_vec, _vpo, _workspace
 from ..MinkowskiEngine.modules.resnet_block import BasicBlock
 from ..MinkowskiEngine.fused_train import conv_bn_act
 from ..prof import section
@@ -55,6 +59,58 @@ def _group_steps(spo):
 
 
 _VERSION_OF = operator.attrgetter("_version")
+
+# map kind of a plan op (include/pbnet_hip.h) -> (kernel volume, slot in pbn_pair_lists[14] of (level_in, level_out), the map of a
+# pyramid or coordinate manager for (level_in, level_out)); levels 0..4 are tensor strides 1..16.  csrc/unet_plan.h: op_tables
+MAP_KINDS = {
+    0: (1, None, lambda pyr, lin, lout: None),                                                  # 1x1: identity pairs
+    1: (27, lambda lin, lout: lout, lambda pyr, lin, lout: pyr.kernel_map(1 << lout, 3)),
+    2: (125, lambda lin, lout: 5, lambda pyr, lin, lout: pyr.kernel_map(1, 5)),
+    3: (8, lambda lin, lout: 6 + lin, lambda pyr, lin, lout: pyr.down_map(1 << lin)),           # k2s2: level_in = fine level
+    4: (8, lambda lin, lout: 10 + lout, lambda pyr, lin, lout: pyr.up_map(2 << lout)),          # transposed: level_out = fine
+}
+
+
+def walk_body(net, src, slab, conv, shortcut_block=None):
+    """The body of a MinkUNet (Mink.py:291-350: everything but the final 1x1 convolution) as one sequence of convolutions
+    over views the caller defines -- symbolic (buffer, column) pairs for the two native plans, tensors for the Python-issued
+    cross-check.  Owns the order of the ops and where results go, nothing else:
+      * the decoder slab of level l is [up | skip]: the stem and the encoder stages 1-3 write the right-hand columns, the
+        transposed convolution of level l+1 the left-hand ones, the decoder stage reads the whole slab;
+      * the last block of a stage writes into the view the stage was asked for.
+    src: the input view.  slab(level, up_channels, skip_channels) -> (up view, skip view, whole slab), called for levels 0..3
+    before any op.  conv(conv, norm, map_kind, level_in, level_out, src, residual, out, relu) -> the view it wrote (out =
+    None: wherever the caller likes).  shortcut_block(blk, h, cur, level, out), optional, is offered every block with a 1x1
+    shortcut after its first convolution (h = conv1's output, cur = the block's input): it may issue
+    relu(bn2(conv2(h)) + bn_d(conv_d(cur))) its own way and return the view, or return None for the two separate ops.
+    Returns the view of the body's output."""
+    P = net.PLANES
+    skip_c, up_c = (INIT_DIM, P[0], P[1], P[2]), (P[7], P[6], P[5], P[4])
+    slabs = [slab(l, up_c[l], skip_c[l]) for l in range(4)]
+
+    def stage(blocks, cur, l, out=None):
+        for bi, blk in enumerate(blocks):
+            h = conv(blk.conv1, blk.norm1, 1, l, l, cur, None, None, True)
+            last_out = out if bi == len(blocks) - 1 else None
+            nxt = None
+            if blk.downsample is not None and shortcut_block is not None:
+                nxt = shortcut_block(blk, h, cur, l, last_out)
+            if nxt is None:
+                res = cur
+                if blk.downsample is not None:
+                    res = conv(blk.downsample[0], blk.downsample[1], 0, l, l, cur, None, None, False)
+                nxt = conv(blk.conv2, blk.norm2, 1, l, l, h, res, last_out, True)
+            cur = nxt
+        return cur
+
+    cur = conv(net.conv0p1s1, net.bn0, 2, 0, 0, src, None, slabs[0][1], True)
+    for l in range(1, 5):
+        cur = conv(getattr(net, _DOWN[l - 1]), getattr(net, _DOWN_BN[l - 1]), 3, l - 1, l, cur, None, None, True)
+        cur = stage(getattr(net, "block%d" % l), cur, l, out=slabs[l][1] if l < 4 else None)
+    for i, l in enumerate((3, 2, 1, 0)):
+        conv(getattr(net, _UP[i]), getattr(net, _UP_BN[i]), 4, l + 1, l, cur, None, slabs[l][0], True)
+        cur = stage(getattr(net, "block%d" % (i + 5)), slabs[l][2], l)
+    return cur
 
 
 class MinkUNet(nn.Module):
@@ -180,38 +236,24 @@ class MinkUNet(nn.Module):
         scale, shift = self._fold(bn, packed[3])
         return spconv_forward(feats, nbr, n_out, packed, scale=scale, shift=shift, residual=residual, relu=relu, out=out)
 
-    def _stage_fused(self, stage, feats, nbr, n, out=None):
-        nb = len(stage)
-        for bi, blk in enumerate(stage):
-            h = self._cbr(blk.conv1, blk.norm1, feats, nbr, n)
-            res = feats
-            if blk.downsample is not None:
-                res = self._cbr(blk.downsample[0], blk.downsample[1], feats, None, n, relu=False)
-            feats = self._cbr(blk.conv2, blk.norm2, h, nbr, n, relu=True, residual=res, out=out if bi == nb - 1 else None)
-        return feats
-
     # ---- native executor: the fused forward as ONE C call (csrc/executor.hip) ------------------------------------
     def _build_plan(self, dtype):
-        """Static list of fused convolution ops over symbolic buffers: the body of Mink.py:291-354 in eval mode.
+        """Static list of fused convolution ops over symbolic buffers: walk_body in eval mode (BatchNorm folded into the
+        epilogue, a 1x1 shortcut folded into its block's second convolution where that is safe) plus the final 1x1.
         Buffer 0 is the input slab; levels 0..4 are tensor strides 1..16."""
-        P = self.PLANES
         keep, ops, bufs, true_io, folded_io = [], [], [(0, 0)], [], []
-        skip_c = (INIT_DIM, P[0], P[1], P[2])
-        up_c = (P[7], P[6], P[5], P[4])
 
         def new_buf(level, width):
             bufs.append((level, width))
             return len(bufs) - 1
 
-        def add(conv, bn, src, map_kind, lin, lout, relu=True, res=None, out=None):
-            w, vpo, n_steps, cout_p = conv._cache.get(conv.kernel, dtype)
-            if bn is not None:
-                scale, shift = self._fold(bn, cout_p)
-            else:
-                scale = None
-                shift = _pad_vec(conv.bias.detach(), cout_p, 0.0) if conv.bias is not None else None
+        def slab(level, up, skip):
+            b = new_buf(level, up + skip)
+            return (b, 0), (b, up), (b, 0)
+
+        def emit(map_kind, lin, lout, src, res, out, packed, scale, shift, relu, src2=(-1, 0), vpo2=0):
+            w, vpo, n_steps, cout_p = packed
             keep.extend([w, scale, shift])
-            true_io.append((int(conv.kernel.shape[-2]), int(conv.kernel.shape[-1])))   # un-padded (C_in, C_out)
             if out is None:
                 out = (new_buf(lout, cout_p), 0)
             op = N.UnetOp()
@@ -220,18 +262,33 @@ class MinkUNet(nn.Module):
             op.res_buf, op.res_col = res if res is not None else (-1, 0)
             op.out_buf, op.out_col = out
             op.vpo, op.n_steps, op.cout_p, op.relu = vpo, n_steps, cout_p, int(relu)
-            op.in2_buf, op.in2_col, op.vpo2 = -1, 0, 0
+            op.in2_buf, op.in2_col = src2
+            op.vpo2 = vpo2
             op.w = w.data_ptr()
             op.scale = scale.data_ptr() if scale is not None else None
             op.shift = shift.data_ptr() if shift is not None else None
             ops.append(op)
             return out
 
+        def add(conv, bn, map_kind, lin, lout, src, res, out, relu):
+            packed = conv._cache.get(conv.kernel, dtype)
+            if bn is not None:
+                scale, shift = self._fold(bn, packed[3])
+            else:
+                scale = None
+                shift = _pad_vec(conv.bias.detach(), packed[3], 0.0) if conv.bias is not None else None
+            true_io.append((int(conv.kernel.shape[-2]), int(conv.kernel.shape[-1])))   # un-padded (C_in, C_out)
+            return emit(map_kind, lin, lout, src, res, out, packed, scale, shift, relu)
+
         def add_folded(blk, h, cur, l, out):
             """relu(bn2(conv2(h)) + bn_d(conv_d(cur))) as ONE convolution over two sources: both BatchNorm scales go into the
-            weights (they differ per branch), the shifts add up, the 1x1 kernel becomes the reduction steps behind the map's."""
-            from ..MinkowskiEngine.conv import pack_weight
+            weights (they differ per branch), the shifts add up, the 1x1 kernel becomes the reduction steps behind the map's.
+            None (the two separate ops) when folding is off, the channel counts do not fill whole barrier groups or the scaled
+            weights would leave the dtype's range."""
             conv2, convd = blk.conv2, blk.downsample[0]
+            if not (self.FOLD_SHORTCUT and _vpo(int(conv2.kernel.shape[-2]), dtype) % 4 == 0
+                    and _vpo(int(convd.kernel.shape[-2]), dtype) % 4 == 0 and self._fold_is_safe(blk, dtype)):
+                return None
             cout = int(conv2.kernel.shape[-1])
             cout_p = (cout + 15) // 16 * 16
             s2, b2 = self._fold(blk.norm2, cout_p)
@@ -246,52 +303,12 @@ class MinkUNet(nn.Module):
             pad = (-n2) % cg                           # whole barrier groups of the first source: zero weights behind the real ones
             parts = [w2, wd] + ([torch.zeros(pad, *wd.shape[1:], dtype=wd.dtype, device=wd.device)] if pad else [])
             w = torch.cat(parts, 0).contiguous()
-            shift = (b2 + bd).contiguous()
-            keep.extend([w, shift])
-            true_io.append((int(conv2.kernel.shape[-2]) , cout))
+            true_io.append((int(conv2.kernel.shape[-2]), cout))
             folded_io.append((len(ops), int(kd.shape[-2]), cout))
-            if out is None:
-                out = (new_buf(l, cout_p), 0)
-            op = N.UnetOp()
-            op.map_kind, op.level_in, op.level_out = 1, l, l
-            op.in_buf, op.in_col = h
-            op.res_buf, op.res_col = -1, 0
-            op.out_buf, op.out_col = out
-            op.vpo, op.n_steps, op.cout_p, op.relu = vpo, n_main + n2 + pad, cout_p, 1
-            op.in2_buf, op.in2_col = cur
-            op.vpo2 = vpo2
-            op.w, op.scale, op.shift = w.data_ptr(), None, shift.data_ptr()
-            ops.append(op)
-            return out
+            return emit(1, l, l, h, None, out, (w, vpo, n_main + n2 + pad, cout_p), None, (b2 + bd).contiguous(), True, cur, vpo2)
 
-        def stage(blocks, cur, l, out=None):
-            for bi, blk in enumerate(blocks):
-                h = add(blk.conv1, blk.norm1, cur, 1, l, l)
-                last_out = out if bi == len(blocks) - 1 else None
-                if blk.downsample is not None and self.FOLD_SHORTCUT:
-                    from ..MinkowskiEngine.conv import _vpo
-                    if _vpo(int(blk.conv2.kernel.shape[-2]), dtype) % 4 == 0 and _vpo(int(blk.downsample[0].kernel.shape[-2]), dtype) % 4 == 0 \
-                            and self._fold_is_safe(blk, dtype):
-                        cur = add_folded(blk, h, cur, l, last_out)
-                        continue
-                res = cur
-                if blk.downsample is not None:
-                    res = add(blk.downsample[0], blk.downsample[1], cur, 0, l, l, relu=False)
-                cur = add(blk.conv2, blk.norm2, h, 1, l, l, relu=True, res=res, out=last_out)
-            return cur
-
-        slab = [new_buf(l, up_c[l] + skip_c[l]) for l in range(4)]
-        cur = add(self.conv0p1s1, self.bn0, (0, 0), 2, 0, 0, out=(slab[0], up_c[0]))
-        l = 0
-        for i in range(4):
-            cur = add(getattr(self, _DOWN[i]), getattr(self, _DOWN_BN[i]), cur, 3, l, l + 1)
-            l += 1
-            cur = stage(getattr(self, "block%d" % (i + 1)), cur, l, out=(slab[l], up_c[l]) if l < 4 else None)
-        for i in range(4):
-            add(getattr(self, _UP[i]), getattr(self, _UP_BN[i]), cur, 4, l, l - 1, out=(slab[l - 1], 0))
-            l -= 1
-            cur = stage(getattr(self, "block%d" % (i + 5)), (slab[l], 0), l)
-        final = add(self.final_sematic, None, cur, 0, 0, 0, relu=False)
+        cur = walk_body(self, (0, 0), slab, add, add_folded)
+        final = add(self.final_sematic, None, 0, 0, 0, cur, None, None, False)
         cin_p = self.conv0p1s1._cache.get(self.conv0p1s1.kernel, dtype)[1] * (16 // torch.empty(0, dtype=dtype).element_size())
         bufs[0] = (0, cin_p)
         ops_arr = (N.UnetOp * len(ops))(*ops)
@@ -334,7 +351,6 @@ class MinkUNet(nn.Module):
         return out if out.shape[1] == cout else out[:, :cout]
 
     def _forward_fused(self, x):
-        from ..MinkowskiEngine.conv import _workspace
         cm = x.coordinate_manager
         assert x.tensor_stride == 1
         sv = cm.sorted() if self.MORTON else None      # the lineage in Z-order: compact tiles, L2-local gathers
@@ -362,33 +378,27 @@ class MinkUNet(nn.Module):
         return ME.SparseTensor(out, coordinate_manager=cm, tensor_stride=1)
 
     def _forward_fused_py(self, x):
-        """The same fused forward issued launch by launch from Python (kept as a cross-check of the native plan)."""
+        """The fused forward issued from Python: walk_body with real tensors -- torch allocates the slabs, every op is one
+        _cbr / spconv_forward launch, no pbn_unet_forward, no folded shortcuts.  It shares the walk with _build_plan on purpose:
+        what it cross-checks is csrc/executor.hip's sequencing and pointer arithmetic, bit for bit
+        (tests/test_backbone_gpu.py::test_unet_matches_golden_and_oracle).  The independent statements of the topology are
+        _forward_modules, oracle/sparse_ref.py and the golden files."""
         cm = x.coordinate_manager
         assert x.tensor_stride == 1
-        P = self.PLANES
         dt, dev = x.F.dtype, x.F.device
-        n = {s: cm.num_rows(s) for s in (1, 2, 4, 8, 16)}
-        k3 = {s: cm.kernel_map(s, 3) for s in (1, 2, 4, 8, 16)}
-        skip_c = (INIT_DIM, P[0], P[1], P[2])
-        up_c = (P[7], P[6], P[5], P[4])
-        strides = (1, 2, 4, 8)
-        slab = {s: torch.empty(n[s], up_c[i] + skip_c[i], dtype=dt, device=dev) for i, s in enumerate(strides)}
-        skip_view = {s: slab[s][:, up_c[i]:] for i, s in enumerate(strides)}
-        up_view = {s: slab[s][:, :up_c[i]] for i, s in enumerate(strides)}
-        cur = self._cbr(self.conv0p1s1, self.bn0, x.F, cm.kernel_map(1, 5), n[1], out=skip_view[1])
-        s = 1
-        for i in range(4):
-            cur = self._cbr(getattr(self, _DOWN[i]), getattr(self, _DOWN_BN[i]), cur, cm.down_map(s), n[2 * s])
-            s *= 2
-            cur = self._stage_fused(getattr(self, "block%d" % (i + 1)), cur, k3[s], n[s],
-                                    out=skip_view[s] if s < 16 else None)
-        for i in range(4):
-            self._cbr(getattr(self, _UP[i]), getattr(self, _UP_BN[i]), cur, cm.up_map(s), n[s // 2], out=up_view[s // 2])
-            s //= 2
-            cur = self._stage_fused(getattr(self, "block%d" % (i + 5)), slab[s], k3[s], n[s])
+        n = [cm.num_rows(1 << l) for l in range(5)]
+
+        def slab(level, up, skip):
+            t = torch.empty(n[level], up + skip, dtype=dt, device=dev)
+            return t[:, :up], t[:, up:], t
+
+        def conv(conv, bn, map_kind, lin, lout, src, res, out, relu):
+            return self._cbr(conv, bn, src, MAP_KINDS[map_kind][2](cm, lin, lout), n[lout], relu=relu, residual=res, out=out)
+
+        cur = walk_body(self, x.F, slab, conv)
         fs = self.final_sematic
         packed = fs._cache.get(fs.kernel, dt)
-        out = spconv_forward(cur, None, n[1], packed, shift=_pad_vec(fs.bias, packed[3], 0.0))
+        out = spconv_forward(cur, None, n[0], packed, shift=_pad_vec(fs.bias, packed[3], 0.0))
         cout = fs.kernel.shape[-1]
         return ME.SparseTensor(out if out.shape[1] == cout else out[:, :cout], coordinate_manager=cm, tensor_stride=1)
 

@@ -4,7 +4,7 @@ The body = every layer of /root/reference/network/Mink.py:291-350 but the final 
 convolutions, the residual stages, four transposed convolutions with their skip concatenations.  The module path issues it as
 ~330 native calls per network and direction from Python (MinkowskiEngine/fused_train.py) and the configs[2] step was
 host-bound on exactly that; here the whole body is ONE autograd node whose forward and backward are one C call each over a
-static plan (the train-mode twin of MinkUNet._build_plan):
+static plan (TrainPlan: like MinkUNet._build_plan a consumer of the one walk of the body, mink_unet.walk_body):
 
   * plan   : ops (convolution -> batch norm with its tail) over symbolic buffers; skip concatenations are written in place
              (encoder output -> right-hand columns of the decoder's slab, transposed convolution -> left-hand columns);
@@ -24,7 +24,7 @@ from .. import _native as N
 from ..MinkowskiEngine import conv as C
 from ..MinkowskiEngine.nn import _bn_workspace
 from ..MinkowskiEngine.core import SparseTensor
-from .mink_unet import _DOWN, _DOWN_BN, _UP, _UP_BN, INIT_DIM, alloc_arena, arena_rows, input_slab
+from .mink_unet import MAP_KINDS, alloc_arena, arena_rows, input_slab, walk_body
 
 ENABLED = os.environ.get("PBN_TRAIN_ENGINE", "1") == "1"     # "0": the module path (one autograd node per block)
 # PBN_TRAIN_SORTED=1: the body runs on the lineage in Z-order (as the fused inference path does: a 128-row tile is a compact
@@ -35,12 +35,6 @@ ENABLED = os.environ.get("PBN_TRAIN_ENGINE", "1") == "1"     # "0": the module p
 SORTED = os.environ.get("PBN_TRAIN_SORTED", "0") == "1"
 # a list while a caller collects what one step's bodies compute (scripts/train_step.py: the step's roofline figure); None otherwise
 ACCOUNTING = None
-_K_OF = {0: 1, 1: 27, 2: 125, 3: 8, 4: 8}
-
-
-def _pair_slot(map_kind, level_in, level_out):
-    """include/pbnet_hip.h: 0..4 k3 of levels 0..4, 5 k5, 6..9 down of fine levels, 10..13 up of fine levels."""
-    return {1: level_out, 2: 5, 3: 6 + level_in, 4: 10 + level_out}[map_kind]
 
 
 class _Covered(object):
@@ -68,17 +62,18 @@ class TrainPlan(object):
 
     def __init__(self, net, dtype, want_input_grad):
         self.dtype, self.want_input_grad = dtype, want_input_grad
-        P = net.PLANES
         bufs = [(0, 0)]
         recs = []                   # (conv, norm, map_kind, lin, lout, in view, pre, res view, out view, relu)
-        skip_c = (INIT_DIM, P[0], P[1], P[2])
-        up_c = (P[7], P[6], P[5], P[4])
 
         def new_buf(level, width):
             bufs.append((level, width))
             return len(bufs) - 1
 
-        def add(conv, norm, src, map_kind, lin, lout, relu=True, res=None, out=None):
+        def slab(level, up, skip):
+            b = new_buf(level, up + skip)
+            return (b, 0), (b, up), (b, 0)
+
+        def add(conv, norm, map_kind, lin, lout, src, res, out, relu):
             cout = int(conv.kernel.shape[-1])
             pre = new_buf(lout, cout)
             if out is None:
@@ -86,27 +81,7 @@ class TrainPlan(object):
             recs.append((conv, norm, map_kind, lin, lout, src, pre, res, out, relu))
             return out
 
-        def stage(blocks, cur, l, out=None):
-            for bi, blk in enumerate(blocks):
-                h = add(blk.conv1, blk.norm1, cur, 1, l, l)
-                res = cur
-                if blk.downsample is not None:
-                    res = add(blk.downsample[0], blk.downsample[1], cur, 0, l, l, relu=False)
-                cur = add(blk.conv2, blk.norm2, h, 1, l, l, relu=True, res=res, out=out if bi == len(blocks) - 1 else None)
-            return cur
-
-        slab = [new_buf(l, up_c[l] + skip_c[l]) for l in range(4)]
-        cur = add(net.conv0p1s1, net.bn0, (0, 0), 2, 0, 0, out=(slab[0], up_c[0]))
-        l = 0
-        for i in range(4):
-            cur = add(getattr(net, _DOWN[i]), getattr(net, _DOWN_BN[i]), cur, 3, l, l + 1)
-            l += 1
-            cur = stage(getattr(net, "block%d" % (i + 1)), cur, l, out=(slab[l], up_c[l]) if l < 4 else None)
-        for i in range(4):
-            add(getattr(net, _UP[i]), getattr(net, _UP_BN[i]), cur, 4, l, l - 1, out=(slab[l - 1], 0))
-            l -= 1
-            cur = stage(getattr(net, "block%d" % (i + 5)), (slab[l], 0), l)
-        self.out_view = cur
+        self.out_view = walk_body(net, (0, 0), slab, add)
         self.out_channels = int(recs[-1][0].kernel.shape[-1])
         e = C._ELEMS[dtype]
         cin0 = int(net.conv0p1s1.kernel.shape[-2])
@@ -154,9 +129,10 @@ class TrainPlan(object):
             self.split_sizes += [conv.kernel.numel(), norm.bn.weight.numel(), norm.bn.bias.numel()]
         self.norms = [r[1] for r in recs]
         self.max_channels = max(int(r[0].kernel.shape[-1]) for r in recs)
-        self.wgrad_ws_bytes = max(int(N.lib().pbn_spconv_wgrad_workspace_bytes(_K_OF[r[2]], int(r[0].kernel.shape[-2]),
+        self.wgrad_ws_bytes = max(int(N.lib().pbn_spconv_wgrad_workspace_bytes(MAP_KINDS[r[2]][0], int(r[0].kernel.shape[-2]),
                                                                                 int(r[0].kernel.shape[-1]))) for r in recs)
-        self.pair_slots = sorted({_pair_slot(r[2], r[3], r[4]) for r in recs if r[2] != 0})
+        self.slot_maps = {MAP_KINDS[mk][1](lin, lout): (mk, lin, lout) for _, _, mk, lin, lout, *_ in recs if mk != 0}
+        self.pair_slots = sorted(self.slot_maps)
         # the ctypes image: everything but the packed-weight pointers is fixed
         ops = (N.TrainOp * len(recs))()
         for i, (conv, norm, mk, lin, lout, src, pre, res, out, relu) in enumerate(recs):
@@ -246,16 +222,7 @@ def _pair_array(pyr, plan):
     if hit is None:
         arr = (N.PairLists * 14)()
         keep = []
-        maps = {}
-        for slot in plan.pair_slots:
-            if slot < 5:
-                maps[slot] = pyr.kernel_map(1 << slot, 3)
-            elif slot == 5:
-                maps[slot] = pyr.kernel_map(1, 5)
-            elif slot < 10:
-                maps[slot] = pyr.down_map(1 << (slot - 6))
-            else:
-                maps[slot] = pyr.up_map(2 << (slot - 10))
+        maps = {slot: MAP_KINDS[mk][2](pyr, lin, lout) for slot, (mk, lin, lout) in plan.slot_maps.items()}
         C.rulebook_pairs_dev_multi([maps[sl] for sl in plan.pair_slots])       # all lists of the lineage in three launches
         for slot in plan.pair_slots:
             nbr = maps[slot]
@@ -399,22 +366,14 @@ def step_accounting(records):
         pair_cache = {}
         for i, (conv, norm, mk, lin, lout, src, pre, res, out, relu) in enumerate(plan.recs):
             cin, cout = int(conv.kernel.shape[-2]), int(conv.kernel.shape[-1])
-            k = _K_OF[mk]
+            k, slot_of, map_of = MAP_KINDS[mk]
             v_in, v_out = rows[lin], rows[lout]
             if mk == 0:
                 pairs = v_out
             else:
-                slot = _pair_slot(mk, lin, lout)
+                slot = slot_of(lin, lout)
                 if slot not in pair_cache:
-                    if slot < 5:
-                        nbr = pyr.kernel_map(1 << slot, 3)
-                    elif slot == 5:
-                        nbr = pyr.kernel_map(1, 5)
-                    elif slot < 10:
-                        nbr = pyr.down_map(1 << (slot - 6))
-                    else:
-                        nbr = pyr.up_map(2 << (slot - 10))
-                    pair_cache[slot] = int(C.rulebook_pairs_dev(nbr)[3].sum().item())
+                    pair_cache[slot] = int(C.rulebook_pairs_dev(map_of(pyr, lin, lout))[3].sum().item())
                 pairs = pair_cache[slot]
             f = 2 * pairs * cin * cout
             io = (v_in * cin + v_out * cout) * es
