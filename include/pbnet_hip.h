@@ -188,7 +188,8 @@ int pbn_spconv_forward_dual(const void* in_feat, int ld_in, int n_in, const int3
                             pbn_stream_t stream);
 
 /* Which kernel family pbn_spconv_forward's automatic choice (rows_per_wave = 0) gives a launch of this shape: 0 workgroup-tile
- * (csrc/spconv.hip), 1 wave-autonomous (spconv_wave.hip), 2 row-stationary (spconv_rs.hip).  No launch; for reports. */
+ * (csrc/spconv.hip), 1 wave-autonomous (spconv_wave.hip), 2 row-stationary (spconv_rs.hip); the experiments library with
+ * PBN_CONV_PC set may answer 3, pair-compacted.  No launch; for reports. */
 int pbn_spconv_family(int n_out, int n_offsets, int vecs_per_offset, int n_steps, int cout_padded, int dtype, int has_map);
 
 /* out[i, :] = in[idx[i], :] on 16-byte multiples (voxel -> point gathers, network/PBNet.py:130-134,250); a negative
@@ -565,14 +566,13 @@ typedef struct {
 } pbn_unet_buf;
 
 size_t pbn_unet_arena_bytes(const pbn_unet_buf* bufs, int n_bufs, const int32_t* n_rows, int dtype, int64_t* buf_offsets);
-/* Round 5: rows EXPECTED per level (5 ints, copied) for the next pbn_unet_forward_dev call of this thread, whose row counts are
- * capacities: kernel families and tile shapes are then chosen for the rows expected (as the size-exact forward would choose them),
- * grids for the capacities.  NULL disarms.  Consumed by the next pbn_unet_forward* call of the thread, whatever it returns. */
-void pbn_unet_set_rows_hint(const int32_t* rows);
+/* Capacity form: n_rows_cap are capacities, the rows that exist are n_rows_dev[level] (device).  rows_expected (host, 5 ints, read
+ * during the call, nothing of the caller's is kept; NULL = choose by the capacities): the rows the caller EXPECTS per level --
+ * kernel families and tile shapes are then chosen for them (as the size-exact forward would choose them), grids for the capacities. */
 int pbn_unet_forward_dev(const pbn_unet_op* ops, int n_ops, const pbn_unet_buf* bufs, int n_bufs, const int32_t* n_rows_cap,
-                         const int32_t* n_rows_dev, const void* input, int ld_input, const int32_t* const* k3,
-                         const int32_t* k5, const int32_t* const* down, const int32_t* const* up, void* arena,
-                         size_t arena_bytes, int dtype, void* splitk_ws, size_t splitk_bytes, pbn_stream_t stream);
+                         const int32_t* n_rows_dev, const int32_t* rows_expected, const void* input, int ld_input,
+                         const int32_t* const* k3, const int32_t* k5, const int32_t* const* down, const int32_t* const* up,
+                         void* arena, size_t arena_bytes, int dtype, void* splitk_ws, size_t splitk_bytes, pbn_stream_t stream);
 int pbn_unet_forward(const pbn_unet_op* ops, int n_ops, const pbn_unet_buf* bufs, int n_bufs, const int32_t* n_rows,
                      const void* input, int ld_input, const int32_t* const* k3, const int32_t* k5,
                      const int32_t* const* down, const int32_t* const* up, void* arena, size_t arena_bytes, int dtype,

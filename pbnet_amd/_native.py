@@ -105,7 +105,6 @@ SIGNATURES = {
                                    c_f32p, c_f32p, c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_size, c_vp]),
     "pbn_spconv_forward_dual": (c_int, [c_vp, c_int, c_int, c_i32p, c_int, c_i32p, c_int, c_vp, c_int, c_int, c_int, c_f32p, c_f32p,
                                         c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_size, c_vp, c_int, c_int, c_int, c_vp]),
-    "pbn_unet_set_rows_hint": (None, [c_i32p]),
     "pbn_spconv_family": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "pbn_spconv_wgrad_workspace_bytes": (c_size, [c_int, c_int, c_int]),
     "pbn_spconv_wgrad": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_i32p, c_i32p, c_int, c_int, c_int, c_int, c_int,
@@ -158,7 +157,7 @@ SIGNATURES = {
     "pbn_coords_prepare_dev": (c_int, [c_i32p, c_i32p, c_int, c_int, c_int, c_vp, c_size, ctypes.POINTER(PrepareLayout), c_vp]),
     "pbn_coords_prepare_hash": (c_int, [c_i32p, c_i32p, c_int, c_int, c_int, c_vp, c_size, ctypes.POINTER(PrepareLayout), c_vp]),
     "pbn_unet_forward_dev": (c_int, [ctypes.POINTER(UnetOp), c_int, ctypes.POINTER(UnetBuf), c_int, ctypes.POINTER(c_i32),
-                                     c_i32p, c_vp, c_int, ctypes.POINTER(ctypes.c_void_p), c_vp,
+                                     c_i32p, ctypes.POINTER(c_i32), c_vp, c_int, ctypes.POINTER(ctypes.c_void_p), c_vp,
                                      ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), c_vp, c_size, c_int,
                                      c_vp, c_size, c_vp]),
     "pbn_class_gate": (c_int, [c_i32p, c_f32p, c_int, c_int, c_int, c_int, c_i32p, c_i32p, c_i32p, c_vp]),

@@ -7,7 +7,6 @@
 //                       folded into the convolution epilogues and skip concatenations written in place.
 // Both only sequence the kernels of coords.hip / spconv.hip; no new arithmetic lives here.
 #include <cstdlib>
-#include <cstring>
 #include "pbn_common.h"
 #include "spconv_common.h"
 #include "unet_plan.h"
@@ -217,78 +216,56 @@ extern "C" size_t pbn_unet_arena_bytes(const pbn_unet_buf* bufs, int n_bufs, con
     return off;
 }
 
-// Rows expected per level for the NEXT forward of this thread whose row counts are capacities (pbn_unet_forward_dev): the values are
-// COPIED (nothing of the caller's is kept) and consumed at the top of every entry point, whatever it returns.
-static thread_local int g_unet_rows_hint[6] = {0, 0, 0, 0, 0, 0};      // [5] = armed
-extern "C" void pbn_unet_set_rows_hint(const int32_t* rows) {
-    for (int l = 0; l < 5; ++l) g_unet_rows_hint[l] = rows ? rows[l] : 0;
-    g_unet_rows_hint[5] = rows ? 1 : 0;
-}
-struct RowsHint { int rows[5]; bool armed; };
-static RowsHint take_rows_hint() {
-    RowsHint h;
-    for (int l = 0; l < 5; ++l) h.rows[l] = g_unet_rows_hint[l];
-    h.armed = g_unet_rows_hint[5] != 0;
-    g_unet_rows_hint[5] = 0;
-    return h;
+// Next-op weight prefetch (PBN_CONV_PREFETCH: 0 off -- the default: it loses 3-8 % with four scenes in flight, profiles/README.md --,
+// 1 with XCD ownership, 2 plain slices): what op `q` will read, as the workgroups of the launch in front of it touch it
+static NextWeights next_weights(const pbn_unet_op& q, int n_bufs, const MapTables& T, const int32_t* n_rows, const PlanArena& B,
+                                int dtype, int mode) {
+    if (!op_index_ok(q.in_buf, q.res_buf, q.out_buf, q.level_in, q.level_out, n_bufs) || !q.w) return {};
+    const OpTables m = op_tables(q.map_kind, q.level_in, q.level_out, T);
+    const ConvArgs nx = shape_args(n_rows[q.level_out], m.K, q.vpo, q.n_steps, q.cout_p, m.fwd != nullptr,
+                                   (unsigned)((unsigned long long)q.n_steps * (q.cout_p / 16) * 1024ull),
+                                   (unsigned)((unsigned long long)n_rows[q.level_in] * B.ld(q.in_buf) * esize(dtype)));
+    LaunchDesc d;
+    describe_launch(nx, dtype, &d);
+    return {q.w, q.n_steps, q.cout_p / 16, d.wave_family ? d.nt : 0, (mode == 1 && d.wmajor) ? d.groups : 0};
 }
 
+// n_rows_dev: the rows that exist per level when n_rows are capacities (else null); rows_expected: the caller's expectation of
+// them (host, 5 levels, else null) -- kernel families and tile shapes follow it, grids and allocations the capacities
 static int unet_forward_impl(const pbn_unet_op* ops, int n_ops, const pbn_unet_buf* bufs, int n_bufs,
                              const int32_t* n_rows, const void* input, int ld_input, const int32_t* const* k3,
                              const int32_t* k5, const int32_t* const* down, const int32_t* const* up, void* arena,
                              size_t arena_bytes, int dtype, void* splitk_ws, size_t splitk_bytes, pbn_stream_t stream,
-                             hipEvent_t* events, const int32_t* n_rows_dev = nullptr, const RowsHint* hint = nullptr) {
+                             hipEvent_t* events, const int32_t* n_rows_dev = nullptr, const int32_t* rows_expected = nullptr) {
     if (!ops || !bufs || !n_rows || !input || !arena || n_ops < 1 || n_bufs < 2 || n_bufs > 512) return PBN_ERR_ARG;
     int64_t offs[512];
     if (pbn_unet_arena_bytes(bufs, n_bufs, n_rows, dtype, offs) > arena_bytes) return PBN_ERR_WORKSPACE;
-    const int es = esize(dtype);
-    struct RsGuard { ~RsGuard() { g_rows_hint = 0; } } rs_guard;   // cleared on every return path
-    const PlanArena B(arena, offs, bufs, input, ld_input, es);
+    static const int pf_env = getenv("PBN_CONV_PREFETCH") ? atoi(getenv("PBN_CONV_PREFETCH")) : 0;
+    const PlanArena B(arena, offs, bufs, input, ld_input, esize(dtype));
     const MapTables T{k3, k5, down, up};
     for (int i = 0; i < n_ops; ++i) {
         const pbn_unet_op& o = ops[i];
         if (!op_index_ok(o.in_buf, o.res_buf, o.out_buf, o.level_in, o.level_out, n_bufs)) return PBN_ERR_ARG;
         const OpTables m = op_tables(o.map_kind, o.level_in, o.level_out, T);
         if (!m.ok) return PBN_ERR_ARG;
-        const int32_t* nbr = m.fwd;
-        const int K = m.K;
-        const void* in = B.at(o.in_buf, o.in_col);
-        void* out = B.at(o.out_buf, o.out_col);
-        const void* res = o.res_buf >= 0 ? B.at(o.res_buf, o.res_col) : nullptr;
-        // the NEXT op's packed weights are touched by this op's workgroups (spconv_common.h: prefetch_next_weights)
-        g_next_weights = NextWeights{nullptr, 0, 0, 0, 0};
-        static const int pf_env = getenv("PBN_CONV_PREFETCH") ? atoi(getenv("PBN_CONV_PREFETCH")) : 0;   // (off by default: nothing to describe)
-        if (pf_env && i + 1 < n_ops) {
-            const pbn_unet_op& q = ops[i + 1];
-            if (op_index_ok(q.in_buf, q.res_buf, q.out_buf, q.level_in, q.level_out, n_bufs) && q.w) {
-                ConvArgs nx;
-                memset(&nx, 0, sizeof(nx));
-                nx.K = op_tables(q.map_kind, q.level_in, q.level_out, T).K;
-                nx.vpo = q.vpo; nx.n_steps = q.n_steps; nx.ntiles_total = q.cout_p / 16; nx.n_out = nx.n_sel = n_rows[q.level_out];
-                nx.w_bytes = (unsigned)((unsigned long long)q.n_steps * (q.cout_p / 16) * 1024ull);
-                nx.in_bytes = (unsigned)((unsigned long long)n_rows[q.level_in] * B.ld(q.in_buf) * es);
-                LaunchDesc d;
-                describe_launch(nx, dtype, &d);
-                g_next_weights = NextWeights{q.w, q.n_steps, q.cout_p / 16, d.wave_family ? d.nt : 0, d.wmajor ? d.groups : 0};
-            }
-        }
+        const bool dual = o.in2_buf >= 0;           // a BasicBlock's 1x1 shortcut folded into this convolution's reduction
+        ConvHints hints;
+        if (rows_expected && n_rows_dev) hints.rows_expected = rows_expected[o.level_out];
+        if (pf_env && i + 1 < n_ops) hints.next = next_weights(ops[i + 1], n_bufs, T, n_rows, B, dtype, pf_env);
         if (events) PBN_HIP_CHECK(hipEventRecord(events[2 * i], (hipStream_t)stream));
-        g_rows_hint = (hint && hint->armed && n_rows_dev) ? hint->rows[o.level_out] : 0;
-        int rc = PBN_ERR_UNSUPPORTED;
-        if (o.in2_buf >= 0) {           // a BasicBlock's 1x1 shortcut folded into this convolution's reduction
-            if (o.in2_buf >= n_bufs) return PBN_ERR_ARG;
-            const void* in2 = B.at(o.in2_buf, o.in2_col);
-            rc = pbn_spconv_forward_dual(in, B.ld(o.in_buf), n_rows[o.level_in], nbr, K,
-                                         n_rows_dev ? n_rows_dev + o.level_out : nullptr, n_rows[o.level_out], o.w, o.vpo,
-                                         o.n_steps, o.cout_p, o.scale, o.shift, res, o.res_buf >= 0 ? B.ld(o.res_buf) : 0, o.relu,
-                                         out, B.ld(o.out_buf), dtype, 0, splitk_ws, splitk_bytes, in2, B.ld(o.in2_buf),
-                                         n_rows[o.level_out], o.vpo2, stream);
-        } else
-            rc = pbn_spconv_forward(in, B.ld(o.in_buf), n_rows[o.level_in], nbr, K, nullptr,
-                                    n_rows_dev ? n_rows_dev + o.level_out : nullptr, n_rows[o.level_out], o.w, o.vpo,
-                                    o.n_steps, o.cout_p, o.scale, o.shift, res, o.res_buf >= 0 ? B.ld(o.res_buf) : 0,
-                                    o.relu, out, B.ld(o.out_buf), dtype, 0, splitk_ws, splitk_bytes, stream);
-        g_next_weights = NextWeights{nullptr, 0, 0, 0, 0};
+        if (o.in2_buf >= n_bufs) return PBN_ERR_ARG;
+        const int rc = spconv_launch({.in_feat = B.at(o.in_buf, o.in_col), .ld_in = B.ld(o.in_buf), .n_in = n_rows[o.level_in],
+                                      .nbr = m.fwd, .n_offsets = m.K,
+                                      .n_out_dev = n_rows_dev ? n_rows_dev + o.level_out : nullptr, .n_out = n_rows[o.level_out],
+                                      .w_packed = o.w, .vecs_per_offset = o.vpo, .n_steps = o.n_steps, .cout_padded = o.cout_p,
+                                      .scale = o.scale, .shift = o.shift,
+                                      .residual = o.res_buf >= 0 ? B.at(o.res_buf, o.res_col) : nullptr,
+                                      .ld_res = o.res_buf >= 0 ? B.ld(o.res_buf) : 0, .relu = o.relu,
+                                      .out_feat = B.at(o.out_buf, o.out_col), .ld_out = B.ld(o.out_buf), .dtype = dtype,
+                                      .workspace = splitk_ws, .workspace_bytes = splitk_bytes,
+                                      .in2_feat = dual ? B.at(o.in2_buf, o.in2_col) : nullptr, .ld_in2 = dual ? B.ld(o.in2_buf) : 0,
+                                      .n_in2 = dual ? n_rows[o.level_out] : 0, .vecs_second = dual ? o.vpo2 : 0},
+                                     hints, (hipStream_t)stream);
         if (rc != PBN_OK) return rc;
         if (events) PBN_HIP_CHECK(hipEventRecord(events[2 * i + 1], (hipStream_t)stream));
     }
@@ -299,7 +276,6 @@ extern "C" int pbn_unet_forward(const pbn_unet_op* ops, int n_ops, const pbn_une
                                 const int32_t* n_rows, const void* input, int ld_input, const int32_t* const* k3,
                                 const int32_t* k5, const int32_t* const* down, const int32_t* const* up, void* arena,
                                 size_t arena_bytes, int dtype, void* splitk_ws, size_t splitk_bytes, pbn_stream_t stream) {
-    (void)take_rows_hint();
     return unet_forward_impl(ops, n_ops, bufs, n_bufs, n_rows, input, ld_input, k3, k5, down, up, arena, arena_bytes, dtype,
                              splitk_ws, splitk_bytes, stream, nullptr);
 }
@@ -307,14 +283,13 @@ extern "C" int pbn_unet_forward(const pbn_unet_op* ops, int n_ops, const pbn_une
 // capacity form: n_rows are capacities, the rows that exist are n_rows_dev[level] (device); launches are sized by the
 // capacities and every kernel bounds itself by the device-side count
 extern "C" int pbn_unet_forward_dev(const pbn_unet_op* ops, int n_ops, const pbn_unet_buf* bufs, int n_bufs,
-                                    const int32_t* n_rows_cap, const int32_t* n_rows_dev, const void* input, int ld_input,
-                                    const int32_t* const* k3, const int32_t* k5, const int32_t* const* down,
-                                    const int32_t* const* up, void* arena, size_t arena_bytes, int dtype, void* splitk_ws,
-                                    size_t splitk_bytes, pbn_stream_t stream) {
-    const RowsHint hint = take_rows_hint();           // consumed by THIS call whatever it returns
+                                    const int32_t* n_rows_cap, const int32_t* n_rows_dev, const int32_t* rows_expected,
+                                    const void* input, int ld_input, const int32_t* const* k3, const int32_t* k5,
+                                    const int32_t* const* down, const int32_t* const* up, void* arena, size_t arena_bytes,
+                                    int dtype, void* splitk_ws, size_t splitk_bytes, pbn_stream_t stream) {
     if (!n_rows_dev) return PBN_ERR_ARG;
     return unet_forward_impl(ops, n_ops, bufs, n_bufs, n_rows_cap, input, ld_input, k3, k5, down, up, arena, arena_bytes, dtype,
-                             splitk_ws, splitk_bytes, stream, nullptr, n_rows_dev, &hint);
+                             splitk_ws, splitk_bytes, stream, nullptr, n_rows_dev, rows_expected);
 }
 
 // Measurement variant: brackets every op with HIP events on the launching stream, SYNCHRONISES the stream at the end and
@@ -324,7 +299,6 @@ extern "C" int pbn_unet_forward_timed(const pbn_unet_op* ops, int n_ops, const p
                                       const int32_t* k5, const int32_t* const* down, const int32_t* const* up,
                                       void* arena, size_t arena_bytes, int dtype, void* splitk_ws, size_t splitk_bytes,
                                       pbn_stream_t stream, float* op_ms) {
-    (void)take_rows_hint();
     if (!op_ms || n_ops < 1 || n_ops > 4096) return PBN_ERR_ARG;
     hipEvent_t* ev = new hipEvent_t[2 * (size_t)n_ops];
     int made = 0, rc = PBN_OK;

@@ -26,7 +26,6 @@
 // parity configuration (1e-4 vs the oracle); bf16/f16 slabs use v_mfma_f32_16x16x32_{bf16,f16}.
 #include <cmath>
 #include <cstdlib>
-#include <cstring>
 #include "spconv_common.h"
 
 namespace pbn {
@@ -569,100 +568,91 @@ __global__ __launch_bounds__(256) void k_gather_rows(const uint4* __restrict__ i
 
 using namespace pbn;
 
-static int spconv_forward_impl(const void* in_feat, int ld_in, int n_in, const int32_t* nbr, int n_offsets,
-                               const int32_t* row_perm, const int32_t* n_out_dev, int n_out, const void* w_packed,
-                               int vecs_per_offset, int n_steps, int cout_padded, const float* scale,
-                               const float* shift, const void* residual, int ld_res, int relu, void* out_feat,
-                               int ld_out, int dtype, int rows_per_wave, void* workspace, size_t workspace_bytes,
-                               pbn_stream_t stream_, const void* in2_feat, int ld_in2, int n_in2, int vecs_second) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (n_out < 0 || n_in < 0 || n_offsets < 1 || vecs_per_offset < 1 || n_steps < 1 || cout_padded < 16 || (cout_padded & 15))
+namespace {
+
+// The automatic family choice, stated once: the first row that wants the launch gets it, a row that answers PBN_ERR_UNSUPPORTED
+// hands it to the next, and behind the table the workgroup-tile family of this file (id 0) takes everything.  spconv_launch
+// walks it, pbn_spconv_family reports the id of its first wanted row.  launch: cfg 0 = automatic.
+struct Family { int id; bool (*wanted)(const ConvArgs&, int dtype); int (*launch)(const ConvArgs&, int dtype, int cfg, hipStream_t); };
+
+int launch_wave_auto(const ConvArgs& a, int dtype, int, hipStream_t stream) {
+    static const int force_cfg = getenv("PBN_WAVE_CFG") ? atoi(getenv("PBN_WAVE_CFG")) : 0;
+    return launch_wave(a, dtype, force_cfg, stream);
+}
+
+const Family FAMILIES[] = {
+#ifdef PBN_EXPERIMENTS
+    {3, pc_family_wanted, launch_pc},              // pair-compacted (experiments/spconv_pc.hip; PBN_CONV_PC=1 in the experiments library)
+#endif
+    {2, rs_family_wanted, launch_rs},              // wide levels: one tile per CU, weights streamed once per CU (spconv_rs.hip)
+    {1, wave_family_wanted, launch_wave_auto},     // coarse levels: K split over the waves of a workgroup (spconv_wave.hip)
+};
+
+}  // namespace
+
+int pbn::spconv_launch(const ConvCall& c, const ConvHints& hints, hipStream_t stream) {
+    if (c.n_out < 0 || c.n_in < 0 || c.n_offsets < 1 || c.vecs_per_offset < 1 || c.n_steps < 1 || c.cout_padded < 16 || (c.cout_padded & 15))
         return PBN_ERR_ARG;
-    if (!(vecs_per_offset == 1 || vecs_per_offset == 2 || (vecs_per_offset & 3) == 0)) return PBN_ERR_ARG;
-    const int n_main = (n_offsets * vecs_per_offset + 3) / 4;
-    if (in2_feat) {
+    if (!(c.vecs_per_offset == 1 || c.vecs_per_offset == 2 || (c.vecs_per_offset & 3) == 0)) return PBN_ERR_ARG;
+    const int n_main = (c.n_offsets * c.vecs_per_offset + 3) / 4;
+    if (c.in2_feat) {
         // second source: wide rows on both sides, a real map, no processing order; its steps follow the map's (padded by the
         // caller to whole barrier groups of the first source: zero weights behind the real channels)
-        if ((vecs_per_offset & 3) || vecs_second < 4 || (vecs_second & 3) || !nbr || row_perm || n_in2 < n_out) return PBN_ERR_ARG;
-        if (n_steps < n_main + (vecs_second >> 2) || n_steps > n_main + (vecs_second >> 2) + 3) return PBN_ERR_ARG;
-    } else if (n_steps != n_main) return PBN_ERR_ARG;
-    if (!nbr && n_offsets != 1) return PBN_ERR_ARG;
-    if (n_out == 0) return PBN_OK;
-    if (!in_feat || !w_packed || !out_feat) return PBN_ERR_ARG;
-    const int esz = dtype == PBN_F32 ? 4 : 2;
-    if ((ld_in * esz) % 16 || (ld_out * esz) % 8 || (residual && (ld_res * esz) % 8)) return PBN_ERR_ARG;
-    if (((uintptr_t)in_feat | (uintptr_t)w_packed) & 15) return PBN_ERR_ARG;
-    if (in2_feat && ((ld_in2 * esz) % 16 || ((uintptr_t)in2_feat & 15))) return PBN_ERR_ARG;
-    const unsigned long long in2_extent = in2_feat ? (unsigned long long)n_in2 * (unsigned long long)ld_in2 * (unsigned long long)esz : 0ull;
+        if ((c.vecs_per_offset & 3) || c.vecs_second < 4 || (c.vecs_second & 3) || !c.nbr || c.row_perm || c.n_in2 < c.n_out) return PBN_ERR_ARG;
+        if (c.n_steps < n_main + (c.vecs_second >> 2) || c.n_steps > n_main + (c.vecs_second >> 2) + 3) return PBN_ERR_ARG;
+    } else if (c.n_steps != n_main) return PBN_ERR_ARG;
+    if (!c.nbr && c.n_offsets != 1) return PBN_ERR_ARG;
+    if (c.n_out == 0) return PBN_OK;
+    if (!c.in_feat || !c.w_packed || !c.out_feat) return PBN_ERR_ARG;
+    const int dtype = c.dtype, esz = dtype == PBN_F32 ? 4 : 2;
+    if ((c.ld_in * esz) % 16 || (c.ld_out * esz) % 8 || (c.residual && (c.ld_res * esz) % 8)) return PBN_ERR_ARG;
+    if (((uintptr_t)c.in_feat | (uintptr_t)c.w_packed) & 15) return PBN_ERR_ARG;
+    if (c.in2_feat && ((c.ld_in2 * esz) % 16 || ((uintptr_t)c.in2_feat & 15))) return PBN_ERR_ARG;
+    const unsigned long long in2_extent = c.in2_feat ? (unsigned long long)c.n_in2 * (unsigned long long)c.ld_in2 * (unsigned long long)esz : 0ull;
     if (in2_extent >= 0x80000000ull) return PBN_ERR_RANGE;
     // gathers address the slab with 32-bit byte offsets through a buffer resource (k_spconv): a slab or weight block of
     // 2 GiB or more cannot be addressed -- refuse it instead of silently gathering zeros past the limit
-    const unsigned long long in_extent = (unsigned long long)n_in * (unsigned long long)ld_in * (unsigned long long)esz;
-    const unsigned long long w_extent = (unsigned long long)n_steps * (unsigned long long)(cout_padded / 16) * 1024ull;
+    const unsigned long long in_extent = (unsigned long long)c.n_in * (unsigned long long)c.ld_in * (unsigned long long)esz;
+    const unsigned long long w_extent = (unsigned long long)c.n_steps * (unsigned long long)(c.cout_padded / 16) * 1024ull;
     if (in_extent >= 0x80000000ull || w_extent >= 0x80000000ull) return PBN_ERR_RANGE;
-    if (!nbr && n_in < n_out) return PBN_ERR_ARG;   // identity map reads row o of the input
+    if (!c.nbr && c.n_in < c.n_out) return PBN_ERR_ARG;   // identity map reads row o of the input
     ConvArgs a;
     a.in_bytes = (unsigned)in_extent; a.w_bytes = (unsigned)w_extent;
-    a.in = in_feat; a.nbr = nbr; a.row_perm = row_perm; a.n_out_dev = n_out_dev; a.w = w_packed; a.scale = scale;
-    a.shift = shift; a.residual = residual; a.out = out_feat; a.ld_in = ld_in; a.ld_res = ld_res; a.ld_out = ld_out;
-    a.K = n_offsets; a.vpo = vecs_per_offset; a.n_steps = n_steps; a.ntiles_total = cout_padded / 16; a.n_out = n_out;
-    a.relu = relu;
-    a.n_sel = (g_rows_hint > 0 && n_out_dev) ? (g_rows_hint < n_out ? g_rows_hint : n_out) : n_out;
+    a.in = c.in_feat; a.nbr = c.nbr; a.row_perm = c.row_perm; a.n_out_dev = c.n_out_dev; a.w = c.w_packed; a.scale = c.scale;
+    a.shift = c.shift; a.residual = c.residual; a.out = c.out_feat; a.ld_in = c.ld_in; a.ld_res = c.ld_res; a.ld_out = c.ld_out;
+    a.K = c.n_offsets; a.vpo = c.vecs_per_offset; a.n_steps = c.n_steps; a.ntiles_total = c.cout_padded / 16; a.n_out = c.n_out;
+    a.relu = c.relu;
+    a.n_sel = (hints.rows_expected > 0 && c.n_out_dev) ? (hints.rows_expected < c.n_out ? hints.rows_expected : c.n_out) : c.n_out;
     a.ksplit = 1; a.partial = nullptr; a.n_out_pad = 0; a.cg = 1; a.wmajor = 0;
-    a.in2 = in2_feat; a.ld_in2 = ld_in2; a.vpo2 = vecs_second; a.n_main = n_main; a.in2_bytes = (unsigned)in2_extent;
-    // Next-op weight prefetch, measured round 4 on the bench scene: one scene alone the stride-8 / 16
-    // ops gain 0.9 us each (138 convolution ops 3417 -> 3362 us with XCD ownership, 3354 with plain slices), with four scenes
-    // in flight the job LOSES 3-8 % (320 / 315 -> 299 / 289 scenes/s with ownership, 311 plain): the touched weights compete
-    // with the other scenes' working sets for the same L2s and every op reads 1.1 MB more.  Off by default.
-    static const int pf_env = getenv("PBN_CONV_PREFETCH") ? atoi(getenv("PBN_CONV_PREFETCH")) : 0;   // 0 off, 1 with ownership, 2 plain slices
-    a.pf_w = nullptr; a.pf_steps = a.pf_ntt = a.pf_nt = a.pf_groups = 0;
-    if (pf_env && g_next_weights.w) {
-        a.pf_w = g_next_weights.w; a.pf_steps = g_next_weights.steps; a.pf_ntt = g_next_weights.ntt;
-        a.pf_nt = g_next_weights.nt; a.pf_groups = pf_env == 1 ? g_next_weights.groups : 0;
-    }
+    a.in2 = c.in2_feat; a.ld_in2 = c.ld_in2; a.vpo2 = c.vecs_second; a.n_main = n_main; a.in2_bytes = (unsigned)in2_extent;
+    // next-op weight prefetch: what the caller describes is what the workgroups touch (executor.hip decides; null = none)
+    a.pf_w = hints.next.w; a.pf_steps = hints.next.steps; a.pf_ntt = hints.next.ntt; a.pf_nt = hints.next.nt; a.pf_groups = hints.next.groups;
     static const int dbg_env = getenv("PBN_CONV_DBG") ? atoi(getenv("PBN_CONV_DBG")) : 0;
     a.dbg = dbg_env;
-    // coarse levels (and whatever PBN_CONV_FAMILY selects): the wave-autonomous family of spconv_wave.hip -- K split over
-    // the waves of a workgroup instead of over workgroups: no fp32 partial slabs, no second launch
+    int rows_per_wave = c.rows_per_wave;
     if (rows_per_wave >= 10000) {             // explicit configuration of the big-tile families: 10000 + 1000 * form + ... (tests, tuning)
-        const int c = rows_per_wave - 10000;
+        const int cfg = rows_per_wave - 10000;
 #ifdef PBN_EXPERIMENTS
-        if ((c % 100000) / 1000 == 3) return launch_pc(a, dtype, (c / 100000) * 16, stream);   // form 3: pair-compacted (experiments/spconv_pc.hip)
+        if ((cfg % 100000) / 1000 == 3) return launch_pc(a, dtype, (cfg / 100000) * 16, stream);   // form 3: pair-compacted (experiments/spconv_pc.hip)
 #endif
-        return launch_rs(a, dtype, c, stream);
+        return launch_rs(a, dtype, cfg, stream);
     }
     if (rows_per_wave >= 100) return launch_wave(a, dtype, rows_per_wave, stream);   // explicit configuration (tests, tuning)
-#ifdef PBN_EXPERIMENTS
-    // pair-compacted fragments, fp32 output tile in LDS (experiments/spconv_pc.hip; PBN_CONV_PC=1 in the experiments library)
-    if (rows_per_wave == 0 && pc_family_wanted(a, dtype)) {
-        const int rc = launch_pc(a, dtype, 0, stream);
-        if (rc != PBN_ERR_UNSUPPORTED) return rc;
-    }
-#endif
-    // wide levels (round 5): one tile per CU, weights streamed once per CU (spconv_rs.hip)
-    if (rows_per_wave == 0 && rs_family_wanted(a, dtype)) {
-        const int rc = launch_rs(a, dtype, 0, stream);
-        if (rc != PBN_ERR_UNSUPPORTED) return rc;
-    }
-    if (rows_per_wave == 0 && wave_family_wanted(a, dtype)) {
-        static const int force_cfg = getenv("PBN_WAVE_CFG") ? atoi(getenv("PBN_WAVE_CFG")) : 0;
-        const int rc = launch_wave(a, dtype, force_cfg, stream);
-        if (rc != PBN_ERR_UNSUPPORTED) return rc;
-    }
-    float* ws = reinterpret_cast<float*>(workspace);
-    if (((uintptr_t)workspace) & 15) ws = nullptr;
+    if (rows_per_wave == 0)
+        for (const Family& f : FAMILIES)
+            if (f.wanted(a, dtype)) {
+                const int rc = f.launch(a, dtype, 0, stream);
+                if (rc != PBN_ERR_UNSUPPORTED) return rc;
+            }
+    float* ws = reinterpret_cast<float*>(c.workspace);
+    if (((uintptr_t)c.workspace) & 15) ws = nullptr;
     if (rows_per_wave != 16 && rows_per_wave != 32 && rows_per_wave != 64) rows_per_wave = (a.n_sel > 64) ? 32 : 16;
     switch (dtype) {
-        case PBN_F32: return launch_t<float>(a, rows_per_wave, ws, workspace_bytes, stream);
-        case PBN_BF16: return launch_t<__hip_bfloat16>(a, rows_per_wave, ws, workspace_bytes, stream);
-        case PBN_F16: return launch_t<__half>(a, rows_per_wave, ws, workspace_bytes, stream);
+        case PBN_F32: return launch_t<float>(a, rows_per_wave, ws, c.workspace_bytes, stream);
+        case PBN_BF16: return launch_t<__hip_bfloat16>(a, rows_per_wave, ws, c.workspace_bytes, stream);
+        case PBN_F16: return launch_t<__half>(a, rows_per_wave, ws, c.workspace_bytes, stream);
         default: return PBN_ERR_ARG;
     }
-}
-
-namespace pbn {
-thread_local NextWeights g_next_weights = {nullptr, 0, 0, 0, 0};
-thread_local int g_rows_hint = 0;
 }
 
 extern "C" int pbn_spconv_forward(const void* in_feat, int ld_in, int n_in, const int32_t* nbr, int n_offsets,
@@ -670,22 +660,22 @@ extern "C" int pbn_spconv_forward(const void* in_feat, int ld_in, int n_in, cons
                                   int vecs_per_offset, int n_steps, int cout_padded, const float* scale,
                                   const float* shift, const void* residual, int ld_res, int relu, void* out_feat,
                                   int ld_out, int dtype, int rows_per_wave, void* workspace, size_t workspace_bytes,
-                                  pbn_stream_t stream_) {
-    return spconv_forward_impl(in_feat, ld_in, n_in, nbr, n_offsets, row_perm, n_out_dev, n_out, w_packed, vecs_per_offset,
-                               n_steps, cout_padded, scale, shift, residual, ld_res, relu, out_feat, ld_out, dtype,
-                               rows_per_wave, workspace, workspace_bytes, stream_, nullptr, 0, 0, 0);
+                                  pbn_stream_t stream) {
+    return spconv_launch({.in_feat = in_feat, .ld_in = ld_in, .n_in = n_in, .nbr = nbr, .n_offsets = n_offsets, .row_perm = row_perm,
+                          .n_out_dev = n_out_dev, .n_out = n_out, .w_packed = w_packed, .vecs_per_offset = vecs_per_offset,
+                          .n_steps = n_steps, .cout_padded = cout_padded, .scale = scale, .shift = shift, .residual = residual,
+                          .ld_res = ld_res, .relu = relu, .out_feat = out_feat, .ld_out = ld_out, .dtype = dtype,
+                          .rows_per_wave = rows_per_wave, .workspace = workspace, .workspace_bytes = workspace_bytes},
+                         ConvHints{}, (hipStream_t)stream);
 }
 
 // Which kernel family the automatic choice of pbn_spconv_forward gives a launch of this shape (0 workgroup-tile k_spconv,
-// 1 wave-autonomous k_spconv_wave, 2 row-stationary k_spconv_rs): the same predicates, no launch.  For reports (bench.py's family split).
+// 1 wave-autonomous k_spconv_wave, 2 row-stationary k_spconv_rs): the first wanted row of FAMILIES, no launch (bench.py's family split).
 extern "C" int pbn_spconv_family(int n_out, int n_offsets, int vecs_per_offset, int n_steps, int cout_padded, int dtype, int has_map) {
     if (n_out < 0 || n_offsets < 1 || vecs_per_offset < 1 || n_steps < 1 || cout_padded < 16 || (cout_padded & 15)) return PBN_ERR_ARG;
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.nbr = has_map ? reinterpret_cast<const int*>(&a) : nullptr;       // (only tested against null)
-    a.K = n_offsets; a.vpo = vecs_per_offset; a.n_steps = n_steps; a.ntiles_total = cout_padded / 16; a.n_out = a.n_sel = n_out;
-    if (has_map && rs_family_wanted(a, dtype)) return 2;
-    if (wave_family_wanted(a, dtype)) return 1;
+    const ConvArgs a = shape_args(n_out, n_offsets, vecs_per_offset, n_steps, cout_padded, has_map != 0, 0, 0);
+    for (const Family& f : FAMILIES)
+        if (f.wanted(a, dtype)) return f.id;
     return 0;
 }
 
@@ -694,11 +684,15 @@ extern "C" int pbn_spconv_forward_dual(const void* in_feat, int ld_in, int n_in,
                                        int n_steps, int cout_padded, const float* scale, const float* shift,
                                        const void* residual, int ld_res, int relu, void* out_feat, int ld_out, int dtype,
                                        int rows_per_wave, void* workspace, size_t workspace_bytes, const void* in2_feat,
-                                       int ld_in2, int n_in2, int vecs_second, pbn_stream_t stream_) {
+                                       int ld_in2, int n_in2, int vecs_second, pbn_stream_t stream) {
     if (!in2_feat) return PBN_ERR_ARG;
-    return spconv_forward_impl(in_feat, ld_in, n_in, nbr, n_offsets, nullptr, n_out_dev, n_out, w_packed, vecs_per_offset,
-                               n_steps, cout_padded, scale, shift, residual, ld_res, relu, out_feat, ld_out, dtype,
-                               rows_per_wave, workspace, workspace_bytes, stream_, in2_feat, ld_in2, n_in2, vecs_second);
+    return spconv_launch({.in_feat = in_feat, .ld_in = ld_in, .n_in = n_in, .nbr = nbr, .n_offsets = n_offsets, .n_out_dev = n_out_dev,
+                          .n_out = n_out, .w_packed = w_packed, .vecs_per_offset = vecs_per_offset, .n_steps = n_steps,
+                          .cout_padded = cout_padded, .scale = scale, .shift = shift, .residual = residual, .ld_res = ld_res,
+                          .relu = relu, .out_feat = out_feat, .ld_out = ld_out, .dtype = dtype, .rows_per_wave = rows_per_wave,
+                          .workspace = workspace, .workspace_bytes = workspace_bytes, .in2_feat = in2_feat, .ld_in2 = ld_in2,
+                          .n_in2 = n_in2, .vecs_second = vecs_second},
+                         ConvHints{}, (hipStream_t)stream);
 }
 
 #ifdef PBN_CONV_TIMING

@@ -48,11 +48,36 @@ struct ConvArgs {
 
 // what the executor knows about the launch an op will turn into (spconv_wave.hip: describe_launch)
 struct LaunchDesc { int wave_family, nt, groups, wmajor; };
+// the next op's packed weights as this launch's workgroups touch them (prefetch_next_weights): copied into pf_* as they stand
 struct NextWeights { const void* w; int steps, ntt, nt, groups; };
-extern thread_local NextWeights g_next_weights;     // set by the executor around pbn_spconv_forward (spconv.hip)
-// round 5: expected rows of the NEXT convolution call's output level (capacity-planned forwards: n_out is a capacity 1.25 x larger,
-// and choosing families / tile shapes by it picks slower kernels); 0 = none.  Set by the executor around a call, cleared behind it
-extern thread_local int g_rows_hint;
+// One convolution launch, by name: the arguments of pbn_spconv_forward / _dual (include/pbnet_hip.h states their contract).
+// A caller names what it uses; the rest means "none".  A field without a default that a caller forgets is 0 / null: spconv_launch
+// refuses that as PBN_ERR_ARG, except n_out, where 0 rows is a valid launch of nothing.
+struct ConvCall {
+    const void* in_feat; int ld_in; int n_in;                                   // input slab
+    const int32_t* nbr; int n_offsets;                                          // map [n_out, K]; null = identity (K = 1)
+    const int32_t* row_perm = nullptr; const int32_t* n_out_dev = nullptr; int n_out;
+    const void* w_packed; int vecs_per_offset; int n_steps; int cout_padded;
+    const float* scale = nullptr; const float* shift = nullptr; const void* residual = nullptr; int ld_res = 0; int relu = 0;
+    void* out_feat; int ld_out; int dtype; int rows_per_wave = 0;               // rows_per_wave 0 = automatic family and tile
+    void* workspace = nullptr; size_t workspace_bytes = 0;                      // split-K scratch
+    const void* in2_feat = nullptr; int ld_in2 = 0; int n_in2 = 0; int vecs_second = 0;     // second source (the dual form)
+};
+// What a caller knows beyond the launch.  rows_expected: rows of the output level when n_out is a capacity (family, tile shape
+// and split-K follow it, grids the capacity: choosing by a 1.25 x capacity picks slower kernels); 0 = choose by n_out
+struct ConvHints { int rows_expected = 0; NextWeights next = {}; };
+// spconv.hip: validates, chooses the kernel family and launches (what pbn_spconv_forward and _dual do, with hints)
+int spconv_launch(const ConvCall& c, const ConvHints& hints, hipStream_t stream);
+// The ConvArgs the family predicates and describe_launch read, for a launch that does not exist (yet): shape only, the rest
+// zero.  Predicates test `nbr` against null only, so one row without neighbours stands for "there is a map".
+inline ConvArgs shape_args(int n_sel, int K, int vpo, int n_steps, int cout_p, bool has_map, unsigned w_bytes, unsigned in_bytes) {
+    static const int no_neighbour = -1;
+    ConvArgs a{};
+    a.nbr = has_map ? &no_neighbour : nullptr;
+    a.K = K; a.vpo = vpo; a.n_steps = n_steps; a.ntiles_total = cout_p / 16; a.n_out = a.n_sel = n_sel;
+    a.w_bytes = w_bytes; a.in_bytes = in_bytes;
+    return a;
+}
 
 namespace {
 

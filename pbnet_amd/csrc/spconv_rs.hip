@@ -439,7 +439,7 @@ bool rs_family_wanted(const ConvArgs& a, int dtype) {
     static const int env = getenv("PBN_CONV_RS") ? atoi(getenv("PBN_CONV_RS")) : 1;
     static const int min_rows = getenv("PBN_RS_MIN_ROWS") ? atoi(getenv("PBN_RS_MIN_ROWS")) : 20000;
     static const int min_rows2 = getenv("PBN_RS_MIN_ROWS2") ? atoi(getenv("PBN_RS_MIN_ROWS2")) : 40000;
-    if (!env || dtype == PBN_F32 || a.row_perm || a.K > 32 || a.n_sel < min_rows) return false;
+    if (!env || dtype == PBN_F32 || !a.nbr || a.row_perm || a.K > 32 || a.n_sel < min_rows) return false;   // (identity maps stay on the other families)
     const int cg = rs_cg(a);
     if (!cg) return false;
     const int nt = a.ntiles_total;

@@ -2,6 +2,7 @@
 // pbn_unet_train_forward / _backward).  Only sequences the kernels of spconv.hip / spconv_wave.hip (convolutions and
 // their input gradients), bnorm.hip (batch norm with the block tail) and wgrad.hip; no new arithmetic lives here.
 // Mirrors /root/reference/network/Mink.py:291-350 in training mode (MinkowskiEngine's BasicBlock.forward for the stages).
+#include "spconv_common.h"
 #include "unet_plan.h"
 
 using namespace pbn;
@@ -39,9 +40,11 @@ extern "C" int pbn_unet_train_forward(const pbn_train_op* ops, int n_ops, const 
         if (!m.ok) return PBN_ERR_ARG;
         const int n_in = n_rows[o.level_in], n_out = n_rows[o.level_out];
         void* pre = X.at(o.pre_buf);
-        int rc = pbn_spconv_forward(X.at(o.in_buf, o.in_col), X.ld(o.in_buf), n_in, m.fwd, m.K, nullptr, nullptr, n_out,
-                                    o.w, o.vpo, o.n_steps, o.cout_p, nullptr, nullptr, nullptr, 0, 0, pre, X.ld(o.pre_buf), dtype,
-                                    0, splitk_ws, splitk_bytes, stream);
+        int rc = spconv_launch({.in_feat = X.at(o.in_buf, o.in_col), .ld_in = X.ld(o.in_buf), .n_in = n_in, .nbr = m.fwd,
+                                .n_offsets = m.K, .n_out = n_out, .w_packed = o.w, .vecs_per_offset = o.vpo, .n_steps = o.n_steps,
+                                .cout_padded = o.cout_p, .out_feat = pre, .ld_out = X.ld(o.pre_buf), .dtype = dtype,
+                                .workspace = splitk_ws, .workspace_bytes = splitk_bytes},
+                               ConvHints{}, (hipStream_t)stream);
         if (rc != PBN_OK) return rc;
         const void* res = o.res_buf >= 0 ? X.at(o.res_buf, o.res_col) : nullptr;
         rc = pbn_bn_act_train_forward(pre, X.ld(o.pre_buf), n_out, o.cout, dtype, o.gamma, o.beta, o.eps, o.momentum,
@@ -90,10 +93,12 @@ extern "C" int pbn_unet_train_backward(const pbn_train_op* ops, int n_ops, const
         if (o.want_dx) {
             if (!o.w_d || (o.in_buf == 0 && !dinput)) return PBN_ERR_ARG;
             char* dx = G.at(o.in_buf, o.in_col);
-            rc = pbn_spconv_forward(gpre, G.ld(o.pre_buf), n_out, m.bwd, m.K, nullptr, nullptr, n_in, o.w_d, o.vpo_d, o.n_steps_d,
-                                    o.cout_p_d, nullptr, nullptr, o.dx_accumulate ? dx : nullptr,
-                                    o.dx_accumulate ? G.ld(o.in_buf) : 0, 0, dx, G.ld(o.in_buf), dtype, 0, splitk_ws, splitk_bytes,
-                                    stream);
+            rc = spconv_launch({.in_feat = gpre, .ld_in = G.ld(o.pre_buf), .n_in = n_out, .nbr = m.bwd, .n_offsets = m.K, .n_out = n_in,
+                                .w_packed = o.w_d, .vecs_per_offset = o.vpo_d, .n_steps = o.n_steps_d, .cout_padded = o.cout_p_d,
+                                .residual = o.dx_accumulate ? dx : nullptr, .ld_res = o.dx_accumulate ? G.ld(o.in_buf) : 0,
+                                .out_feat = dx, .ld_out = G.ld(o.in_buf), .dtype = dtype, .workspace = splitk_ws,
+                                .workspace_bytes = splitk_bytes},
+                               ConvHints{}, (hipStream_t)stream);
             if (rc != PBN_OK) return rc;
         }
         // 3. weight gradient over the rule pairs of the forward map

@@ -61,7 +61,7 @@ class Capacities(object):
         for k in self.FIELDS:
             setattr(self, k, kw[k])
         # rows EXPECTED per level (the measured ones): the kernels' family / tile choice follows these, the grids the capacities
-        # (round 5: choosing by the 1.25 x capacities picked slower kernels -- pbn_unet_set_rows_hint)
+        # (round 5: choosing by the 1.25 x capacities picked slower kernels -- pbn_unet_forward_dev's rows_expected)
         self.expect = kw.get("expect") or {"lv1": list(self.lv1), "lv2": list(self.lv2), "lv3": list(self.lv3)}
 
     def padded(self, slack=1.25, quantum=256):
@@ -148,10 +148,11 @@ class PlannedForward(object):
         # pool of one captured graph to the next and dangle once the first graph is released
         ws = self._splitk_ws
         vp = ctypes.c_void_p
+        hint = None
         if expect is not None and HINTS:
-            lib.pbn_unet_set_rows_hint((ctypes.c_int32 * 5)(*[max(1, min(int(e), int(c))) for e, c in zip(expect, cap_levels)]))
+            hint = (ctypes.c_int32 * 5)(*[max(1, min(int(e), int(c))) for e, c in zip(expect, cap_levels)])
         N.check(lib.pbn_unet_forward_dev(plan["ops"], plan["n_ops"], plan["bufs"], plan["n_bufs"], n_rows,
-                                         vp(lin.counts.data_ptr()), vp(padded.data_ptr()), cin_p, k3, k5, down, up,
+                                         vp(lin.counts.data_ptr()), hint, vp(padded.data_ptr()), cin_p, k3, k5, down, up,
                                          vp(arena.data_ptr()), nbytes, N.DT[dt], vp(ws.data_ptr()), ws.numel(),
                                          N.current_stream()), "pbn_unet_forward_dev")
         self._level_overflow.append((lin.counts > self._caps_t[id(cap_levels)]).any())
