@@ -346,6 +346,20 @@ int pbn_spconv_wgrad_checked(const void* x, int ld_x, long long n_x_rows, const 
                              const int32_t* in_idx, const int32_t* out_idx, const int32_t* seg_begin, const int32_t* pair_counts,
                              int lists_padded, int segment, int n_pairs_total, int n_offsets, int cin, int cout, float* dw,
                              void* workspace, size_t workspace_bytes, pbn_stream_t stream);
+/* What pbn_spconv_wgrad launches for a call of this shape (csrc/wgrad_plan.h; the launch follows the same function under the
+ * same PBN_WGRAD_* environment, so the answer is the plan of the next launch).  form 0: k_wgrad<T> (f32 MFMA; wa = wb = 0),
+ * 1: k_wgrad_ring<T, wa, wb, identity>; small_level: quarter tiles instead of pair splits; strips = channel-tile strips of
+ * one offset, co_groups of them per input-channel group; splits > 1: partial slabs in the workspace + k_wgrad_reduce;
+ * grid = workgroups of the main launch.  aligned16: both slab bases are 16-byte aligned; identity: no pair lists;
+ * has_workspace: a workspace pointer is passed.  Host code, no HIP call: answers without a GPU.  PBN_ERR_ARG where the
+ * launch refuses the same arguments (sizes < 1, n_pairs_total < 0, unknown dtype, identity with n_offsets != 1); with
+ * n_pairs_total = 0 the launch only zero-fills dw. */
+typedef struct {
+    int32_t form, wa, wb, small_level, strips, co_groups, splits;
+    int64_t grid;
+} pbn_wgrad_plan;
+int pbn_spconv_wgrad_plan(int dtype, int ld_x, int ld_g, int aligned16, int identity, int n_offsets, int n_pairs_total, int cin,
+                          int cout, int has_workspace, size_t workspace_bytes, pbn_wgrad_plan* out);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Capacity-planned inference (csrc/plan.hip): the data-dependent sizes of PBNet.forward stay on the device.  Every buffer

@@ -52,6 +52,12 @@ class UnetOp(ctypes.Structure):
                 ("w", ctypes.c_void_p), ("scale", ctypes.c_void_p), ("shift", ctypes.c_void_p)]
 
 
+class WgradPlan(ctypes.Structure):
+    """pbn_wgrad_plan (include/pbnet_hip.h)."""
+    _fields_ = [("form", c_i32), ("wa", c_i32), ("wb", c_i32), ("small_level", c_i32), ("strips", c_i32),
+                ("co_groups", c_i32), ("splits", c_i32), ("grid", c_i64)]
+
+
 class UnetBuf(ctypes.Structure):
     """pbn_unet_buf (include/pbnet_hip.h)."""
     _fields_ = [("level", c_i32), ("width", c_i32)]
@@ -111,6 +117,8 @@ SIGNATURES = {
                                  c_f32p, c_vp, c_size, c_vp]),
     "pbn_spconv_wgrad_checked": (c_int, [c_vp, c_int, ctypes.c_longlong, c_vp, c_int, ctypes.c_longlong, c_int, c_vp, c_vp, c_i32p,
                                          c_i32p, c_int, c_int, c_int, c_int, c_int, c_int, c_f32p, c_vp, c_size, c_vp]),
+    "pbn_spconv_wgrad_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_size,
+                                      ctypes.POINTER(WgradPlan)]),
     "pbn_gather_rows": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_int, c_vp]),
     "pbn_segment_pool_workspace_bytes": (c_size, [c_int, c_int]),
     "pbn_segment_pool": (c_int, [c_vp, c_int, c_int, c_int, c_i32p, c_int, c_f32p, c_f32p, c_vp, c_size, c_vp]),

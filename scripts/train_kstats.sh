@@ -13,7 +13,7 @@ import csv, sys, collections
 rows = list(csv.DictReader(open('gpurun_out/%s_train_kernel_stats.csv' % sys.argv[1])))
 steps = next(int(r['Calls']) for r in rows if 'k_centers' in r['Name'])
 g = collections.Counter(); gc = collections.Counter()
-keys = ['k_wgrad_ring', 'k_wgrad16', 'k_wgrad_reduce', 'k_wgrad<', 'k_bn_apply', 'k_bn_partial', 'k_bn_stats_final', 'k_bn_bwd_final', 'k_spconv_wave',
+keys = ['k_wgrad_ring', 'k_wgrad_reduce', 'k_wgrad<', 'k_bn_apply', 'k_bn_partial', 'k_bn_stats_final', 'k_bn_bwd_final', 'k_spconv_wave',
         'k_spconv<', 'k_spconv_reduce', 'k_pair', 'copyBuffer', 'fillBuffer', 'FusedAdam', 'at::native', 'rocprim', 'k_kernel_maps', 'k_pack', 'k_centers', 'k_count', 'k_union']
 for r in rows:
     n = r['Name']

@@ -6,13 +6,18 @@ Weight gradient through the C ABI (pbn_spconv_wgrad_checked), so that the dispat
     forced pair splits 1 / 2 / 7 / 64 (k_wgrad_reduce; the split count is read back from the workspace), offsets of
     0 / 1 / step - 1 / step + 1 / ~3000 pairs, n_pairs_total = 0, k_wgrad<T> on fp32 slabs and on 16-bit slabs that are
     misaligned or have ld % 8 != 0, strided x / g views; padded host lists and unpadded device lists whose unused tails
-    hold VALID row indices (reading past a count changes dW); PBN_WGRAD_FORM=16 / 32 in a child process each;
+    hold VALID row indices (reading past a count changes dW); PBN_WGRAD_FORM=32 in a child process;
+  * before every exact case the library is asked what it will launch (pbn_spconv_wgrad_plan, with the call's own arguments
+    and under the call's environment): form, WA, WB, small_level and splits must equal the independent Python statement
+    (tests/wgrad_plan_ref.py), so "this kernel ran" rests on the library's answer, and the partial slabs found in the
+    workspace tie that answer to the launch;
   * dW is written inside a sentinel-filled buffer, nothing around it may change; every call runs twice, bit-identical;
   * bounded mode (|got - ref| <= ulp + 2^-20 S per element) at MinkUNet34C shapes and the bench pyramid's stride-1 map.
 Input gradient through the module path (mod(SparseTensor).backward(gy)) for k3, k5, down, up, 1x1 + bias and linear in
 bf16 / fp16 / fp32, exact mode: x.grad == RNE_T(float64), kernel.grad == float64, bias.grad == the column sums.  The
 batch packer's buffers (training) equal pack_weight byte for byte for every convolution of MinkUNet34C and MinkUNet14A.
 Run with -s for the per-form configuration counts and the worst bounded ratios."""
+import ctypes
 import os
 import subprocess
 import sys
@@ -23,6 +28,7 @@ import torch
 
 import conv_exact as X
 import grad_exact as G
+from wgrad_plan_ref import cdiv, wgrad_plan
 import pbnet_amd.MinkowskiEngine as ME
 from pbnet_amd import _native as N
 from pbnet_amd import synth
@@ -32,51 +38,21 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DT16 = (torch.bfloat16, torch.float16)
-STEP = 32                                   # pairs per step of k_wgrad16 / k_wgrad_ring
+STEP = 32                                   # pairs per step of k_wgrad_ring
 _RAN = {}                                   # form -> configurations run in this process
 _WORST = {}                                 # bounded family -> worst err / bound
 SENT32 = 0x5A5A5A5A
 
 
-def cdiv(a, b):
-    return -(-a // b)
-
-
-def wgrad_plan(dtype, ld_x, ld_g, x_ptr, g_ptr, cin, cout, n_pairs, K, ident, ws_bytes):
-    """pbn_spconv_wgrad's dispatch restated (csrc/wgrad.hip): (form, WA, WB, small_level, splits).  Reads the same
-    environment knobs; PBN_WGRAD_FORM as this process saw it at start."""
-    env = lambda k: int(os.environ[k]) if os.environ.get(k) else 0
-    form_env = env("PBN_WGRAD_FORM")
-    form16 = (form_env != 32 and dtype != torch.float32 and ld_x % 8 == 0 and ld_g % 8 == 0 and ld_x >= (cin + 7) // 8 * 8
-              and ld_g >= (cout + 7) // 8 * 8 and ((x_ptr | g_ptr) & 15) == 0)
-    ring = form16 and form_env != 16
-    wa = wb = 0
-    small = False
-    if form16:
-        cit, cot = cdiv(cin, 16), cdiv(cout, 16)
-        wa = 4 if cit >= 7 else (cit + 1) // 2
-        wb = 4 if cot >= 7 else (cot + 1) // 2
-        small = ring and n_pairs // K < 3000 and cdiv(cit, 2 * wa) * cdiv(cot, 2 * wb) * K < 256
-        maxt = env("PBN_WGRAD_MAXT") or (2 if small else 4)
-        wa, wb = min(wa, maxt), min(wb, maxt)
-        strips = cdiv(cit, 2 * wa) * cdiv(cot, 2 * wb)
-    else:
-        strips = cdiv(cin, 16) * cdiv(cout, 64)
-    want, minp = env("PBN_WGRAD_WGS"), env("PBN_WGRAD_MIN_PAIRS")
-    target = want if want > 0 else (1024 if ring else 2048)
-    min_pairs = minp if minp > 0 else (256 if ring else 512)
-    ppo = n_pairs // K + 1
-    splits = target // (strips * K) + 1
-    splits = min(splits, ppo // min_pairs + 1)
-    n_out = K * cin * cout
-    if ring:
-        splits = min(splits, (32 << 20) // (4 * n_out) + 1)
-    if small and want <= 0:
-        splits = 1
-    splits = min(splits, ws_bytes // (4 * n_out), 64)
-    splits = max(splits, 1)
-    form = ("ring%d%d%s" % (wa, wb, "i" if ident else "")) if ring else ("w16" if form16 else "w32")
-    return form, wa, wb, small, splits
+def library_plan(x, g, K, cin, cout, n_pairs, ident, ws_bytes):
+    """pbn_spconv_wgrad_plan for the call run_exact is about to make -> (form, WA, WB, small_level, splits) in the Python
+    statement's terms."""
+    p = N.WgradPlan()
+    rc = N.lib().pbn_spconv_wgrad_plan(C._DT[x.dtype], x.ld, g.ld, int(((x.ptr() | g.ptr()) & 15) == 0), int(ident), K, n_pairs,
+                                       cin, cout, 1, ws_bytes, ctypes.byref(p))
+    assert rc == 0, rc
+    form = ("ring%d%d%s" % (p.wa, p.wb, "i" if ident else "")) if p.form == 1 else "w32"
+    return form, p.wa, p.wb, bool(p.small_level), p.splits
 
 
 def padded_lists(pairs, segment):
@@ -161,7 +137,11 @@ def run_exact(x, g, pairs, K, cin, cout, label, lists=None, counts=None, padded=
     lib = N.lib()
     wsb = int(lib.pbn_spconv_wgrad_workspace_bytes(K, cin, cout)) if ws_bytes is None else ws_bytes
     npl = n_pairs if n_pairs is not None else (int(lists[3].sum()) if lists is not None else x.rows)
-    form, wa, wb, small, splits = wgrad_plan(x.dtype, x.ld, g.ld, x.ptr(), g.ptr(), cin, cout, npl, K, ident, wsb)
+    assert ident == (lists is None)
+    form, wa, wb, small, splits = library_plan(x, g, K, cin, cout, npl, ident, wsb)
+    twin = wgrad_plan(x.dtype, x.ld, g.ld, x.ptr(), g.ptr(), cin, cout, npl, K, ident, wsb)
+    assert (form, wa, wb, small, splits) == twin, "%s %d->%d K %d %s: the library plans %r, the Python statement %r" % (
+        x.dtype, cin, cout, K, label, (form, wa, wb, small, splits), twin)
     what = "%-8s %-9s %3d->%-3d K %-3d splits %2d%s %s" % (str(x.dtype).replace("torch.", ""), form, cin, cout, K, splits,
                                                            " small" if small else "", label)
     if expect_form is not None:
@@ -358,15 +338,14 @@ def form_cases(form):
             x, g = operands(gen, 3000, 2900, cin, cout, dtype)
             pairs = rand_pairs(gen, (0, 1, 33, 3100, 700), 3000, 2900)
             run_exact(x, g, pairs, 5, cin, cout, "FORM=%s" % form, lists=padded_lists(pairs, 4096), padded=1, segment=4096,
-                      expect_form="w16" if form == "16" else "w32")
+                      expect_form="w32")
             xi, gi = operands(gen, 2000, 2000, cin, cout, dtype)
-            run_exact(xi, gi, None, 1, cin, cout, "FORM=%s identity" % form, ident=True,
-                      expect_form="w16" if form == "16" else "w32")
+            run_exact(xi, gi, None, 1, cin, cout, "FORM=%s identity" % form, ident=True, expect_form="w32")
             ran += 2
     assert ran == 20
 
 
-@pytest.mark.parametrize("form", ["16", "32"])
+@pytest.mark.parametrize("form", ["32"])
 def test_wgrad_static_forms_in_a_child(form):
     code = _FORM_CODE.format(root=ROOT, tests=os.path.join(ROOT, "tests"), form=form)
     env = dict(os.environ, PBN_WGRAD_FORM=form)
