@@ -786,6 +786,46 @@ int pbn_losses_backward(const void* sem_score, int sem_dtype, int sem_ld, const 
                         const double* state, const float* grad_loss, void* g_sem, void* g_offset, void* g_mask, void* g_clt,
                         pbn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Optimizer step and loss meters of the training epoch (csrc/optim.hip; train.py:36-120, :350-357).
+ *
+ * table: a DEVICE array of n_chunks records, built once by the host and reused while the gradient addresses stay put.  A
+ * record covers at most PBN_OPTIM_CHUNK consecutive float32 elements of ONE tensor: its parameter, gradient and state
+ * addresses and the element count; vec = 1 when all its addresses are multiples of 16 (16-byte loads and stores), 0 =
+ * dword accesses.  float32 only; the chunks of one call must not overlap.  One thread owns one element: no atomics, the
+ * same inputs give the same bits on every grid.  Asynchronous, no host synchronisation, no workspace.
+ *
+ * Every operation is ONE float32 operation (no FMA, correctly rounded '/' and sqrtf), in this order; all scalars are
+ * formed by the caller in float64 and rounded to float32 once:
+ *   Adam   g' = g + weight_decay * p                 (coupled, weight_decay != 0)
+ *          p  = p * (1 - lr * weight_decay), g' = g  (decoupled = 1: AdamW)
+ *          m  = m + (g' - m) * one_minus_beta1;  v = v * beta2 + (g' * g') * one_minus_beta2
+ *          d  = sqrtf(v) / bc2_sqrt + eps;       p = p - step_size * (m / d)
+ *          with step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t), t = the step count of the call's tensors
+ *   SGD    g' = g + weight_decay * p (weight_decay != 0);  buf = first ? g' : buf * momentum + g';  p = p - lr * buf
+ * state0 = exp_avg / momentum_buffer, state1 = exp_avg_sq (unused by SGD).  PBN_ERR_ARG before any launch: n_chunks < 0, a
+ * null or misaligned table, a flag outside {0, 1}, a scalar that is not finite, bc2_sqrt <= 0.  n_chunks == 0 is PBN_OK.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define PBN_OPTIM_CHUNK 4096
+typedef struct pbn_optim_chunk_rec {
+    void* param;
+    const void* grad;
+    void* state0;
+    void* state1;
+    int32_t n;
+    int32_t vec;
+} pbn_optim_chunk_rec;
+int pbn_optim_chunk(void);
+int pbn_optim_adam(const void* table, int n_chunks, float lr, float beta1, float one_minus_beta1, float beta2,
+                   float one_minus_beta2, float eps, float weight_decay, float step_size, float bc2_sqrt, int decoupled,
+                   pbn_stream_t stream);
+int pbn_optim_sgd(const void* table, int n_chunks, float lr, float momentum, float weight_decay, int first,
+                  pbn_stream_t stream);
+/* AverageMeter.update (tools/log.py:26-30) for k terms at once: acc f64[3k] = val | sum | count gets val[j] = terms[j],
+ * sum[j] += terms[j] * weights[j], count[j] += weights[j], in float64 (terms f32[k] widened, weights f64[k]).  One launch of
+ * one wave, lane j owns term j; k in [0, 1024]. */
+int pbn_loss_meter_update(const float* terms, const double* weights, double* acc, int k, pbn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

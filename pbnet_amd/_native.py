@@ -229,6 +229,11 @@ SIGNATURES = {
                                    c_f32p, c_vp, c_vp, c_vp, c_size, c_vp]),
     "pbn_losses_backward": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_f32p, c_f32p, c_vp, c_i64, c_int, c_vp, c_int, c_vp,
                                     c_vp, c_i64, c_vp, c_int, c_f32p, c_i64, c_vp, c_f32p, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "pbn_optim_chunk": (c_int, []),
+    "pbn_optim_adam": (c_int, [c_vp, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_float,
+                               c_int, c_vp]),
+    "pbn_optim_sgd": (c_int, [c_vp, c_int, c_float, c_float, c_float, c_int, c_vp]),
+    "pbn_loss_meter_update": (c_int, [c_f32p, c_vp, c_vp, c_int, c_vp]),
 }
 
 PBN_OK, PBN_ERR_ARG, PBN_ERR_WORKSPACE, PBN_ERR_HIP, PBN_ERR_RANGE, PBN_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5

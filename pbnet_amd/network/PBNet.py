@@ -651,7 +651,9 @@ def model_losses(ret, sem_label, ins_label, instance_info, instance_pointnum, xy
 def model_fn(batch, model, epoch, cfg, task="train"):
     """PBNet.py:349-444: forward + losses.  Losses are plain torch on the device by default (model_losses; its arithmetic
     is restated independently in oracle/loss_ref.py and compared in tests/test_losses.py); cfg.native_losses = True
-    computes the same terms and gradients in csrc/losses.hip (pbnet_amd/losses.py, tests/test_losses_native_gpu.py)."""
+    computes the same terms and gradients in csrc/losses.hip (pbnet_amd/losses.py, tests/test_losses_native_gpu.py).
+    cfg.device_meters = True returns the values of visual_dict / meter_dict as 0-dim device tensors instead of Python floats:
+    the call then ends without its read-back (pbnet_amd/train_epoch.py keeps the running sums on the device)."""
     xyz_original = batch["xyz_original"].cuda()
     ins_label = batch["ins"].cuda()
     ret = model(batch["feat_voxel"], batch["xyz_voxel"], xyz_original, batch["v2p_index"], ins_label, epoch, task)
@@ -669,7 +671,10 @@ def model_fn(batch, model, epoch, cfg, task="train"):
         pred = {"sem": sem_pred_p, "offseted_xyz": xyz_original + offset_pred_p}
         # the logged terms in ONE read-back (the reference calls .item() per term: five synchronisations)
         names = ["loss", "semantic_loss", "offset_norm_loss", "offset_dir_loss"] + (["mask_loss"] if epoch > cfg.cluster_epoch else [])
-        host = torch.stack([parts[k].detach().float().reshape(()) for k in names]).tolist()
+        host = torch.stack([parts[k].detach().float().reshape(()) for k in names])
+        # cfg.device_meters: the terms stay on the device as 0-dim views of that one float32 tensor (train_epoch.LossMeter
+        # sums them there); otherwise they come back as Python floats
+        host = host.unbind(0) if getattr(cfg, "device_meters", False) else host.tolist()
         visual_dict = dict(zip(names[:4], host[:4]))
         meter_dict = {k: (v, valid.sum()) for k, v in visual_dict.items()}
         if epoch > cfg.cluster_epoch:

@@ -145,6 +145,74 @@ def run_training(world, rank, dev, dist, steps=5, warmup=2, dtype=None, comm_dty
     return elapsed, t_comm[0] / max(comm_steps, 1), float(loss.detach()), info
 
 
+def run_epoch_driver(rank, dev, steps=5, warmup=2, dtype=None, comm_dtype=None, overlap=True, small=False, blocks=5):
+    """The step of run_training twice, from the same weights on the same batch: the plain loop above (model_fn's default path
+    with its read-back, torch.optim.Adam(fused=True)) and pbnet_amd.train_epoch.TrainEpoch (log_every=0, cfg.device_meters,
+    pbnet_amd.optim.Adam), in alternating blocks of `steps` steps; the figure of each is its median block.  Returns a dict."""
+    import statistics
+    from pbnet_amd import dist as pd, optim as po, synth
+    from pbnet_amd.config import get_config
+    from pbnet_amd.network.PBNet import PBNet, model_fn
+    from pbnet_amd.train_epoch import TrainEpoch
+    dtype = dtype or torch.bfloat16
+    comm_dtype = comm_dtype or torch.float32
+    kw = dict(room=(1.6, 1.3, 1.2), n_boxes=4, pitch=0.03, classes=(17, 10)) if small else {}
+    batch_np, teacher_np, info = synth.make_train_batch(seed=10 + rank, copies=1, **kw)
+    batch = {k: torch.from_numpy(v).to(dev) for k, v in batch_np.items()}
+    batch["feat_voxel"] = batch["feat_voxel"].to(dtype)
+    teacher = {k: torch.from_numpy(v).to(dev) for k, v in teacher_np.items()}
+
+    def make_model(cfg):
+        torch.manual_seed(22)
+        model = PBNet(cfg).to(dev).train()
+        fwd = model.forward
+        model.forward = lambda *a, **k: fwd(*a, teacher=teacher, **k)
+        return model
+
+    cfg_plain = get_config(batch_size=1, cluster_epoch=0)
+    plain = make_model(cfg_plain)
+    opt = torch.optim.Adam(plain.parameters(), lr=1e-3, fused=True)
+    reducer = pd.GradientReducer(plain.parameters(), comm_dtype=comm_dtype, overlap=overlap)
+
+    def plain_step():
+        opt.zero_grad(set_to_none=True)
+        loss, pred, visual, meter = model_fn(batch, plain, 1, cfg_plain, "train")
+        loss.backward()
+        reducer.finish()
+        opt.step()
+
+    cfg_epoch = get_config(batch_size=1, cluster_epoch=0, device_meters=True, lr=1e-3, step_epoch=50, epochs=520)
+    driven = make_model(cfg_epoch)
+    native = po.Adam(driven.parameters(), lr=1e-3)
+    epoch = TrainEpoch(driven, cfg_epoch, 1, native, steps * blocks + warmup, reducer=pd.GradientReducer(
+        driven.parameters(), comm_dtype=comm_dtype, overlap=overlap), log_every=0, save=False)
+
+    def block(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / steps * 1e3
+
+    for _ in range(warmup):
+        plain_step()
+        epoch.step(batch)
+    uploads0 = native.table_uploads
+    times = {"plain_loop": [], "epoch_driver": []}
+    for _ in range(blocks):
+        times["plain_loop"].append(block(plain_step))
+        times["epoch_driver"].append(block(lambda: epoch.step(batch)))
+    averages = epoch.finish()
+    return {"metric": "training step, ms (median of %d alternating blocks of %d steps)" % (blocks, steps),
+            "plain_loop_ms": round(statistics.median(times["plain_loop"]), 3),
+            "epoch_driver_ms": round(statistics.median(times["epoch_driver"]), 3),
+            "plain_loop_blocks_ms": [round(t, 3) for t in times["plain_loop"]],
+            "epoch_driver_blocks_ms": [round(t, 3) for t in times["epoch_driver"]],
+            "optimizer_launches_per_step": native.launches_last_step, "table_uploads_in_timed_steps": native.table_uploads - uploads0,
+            "timed_steps": steps * blocks, "epoch_loss_average": averages["loss"], "points_per_scene": info["n_points"], "small": small}
+
+
 def dry_run(args):
     """The N-rank training entry without a GPU: per-rank seeded data, gradient all-reduce through pbnet_amd.dist
     .GradientReducer (hooks during backward, buckets in reverse registration order, a parameter unused on every rank keeps
@@ -203,6 +271,9 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: gloo, a small dense stand-in model, the SAME GradientReducer / barriers / MAX-over-ranks / "
                          "JSON line (tests/test_launch_cpu.py)")
+    ap.add_argument("--epoch-driver", action="store_true",
+                    help="also run the steps through pbnet_amd.train_epoch.TrainEpoch (log_every=0, device meters, native Adam) in "
+                         "blocks alternating with the plain loop and print both step times (one rank)")
     args = ap.parse_args()
     if args.dry_run:
         return dry_run(args)
@@ -219,6 +290,14 @@ def main():
     else:
         dist.init_process_group("gloo", rank=rank, world_size=world)
     dtypes = {"bf16": torch.bfloat16, "f32": torch.float32}
+    if args.epoch_driver:
+        assert world == 1, "--epoch-driver compares two loops on one rank"
+        res = run_epoch_driver(rank, dev, args.steps, args.warmup, dtypes[args.dtype], dtypes[args.comm_dtype], not args.no_overlap,
+                               args.small)
+        dist.barrier()
+        dist.destroy_process_group()
+        print(json.dumps(res), flush=True)
+        return
     phases = {} if args.phases else None
     e, comm, loss, info = run_training(world, rank, dev, dist, args.steps, args.warmup, dtypes[args.dtype], dtypes[args.comm_dtype],
                                        not args.no_overlap, phases, args.small)
