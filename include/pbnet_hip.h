@@ -478,7 +478,8 @@ int pbn_proposal_rows(const void* mask_score, int ld, float thd, const int64_t* 
  *                           n_pick = unlabelled), first arg-max label per superpoint, refined per-point labels and the
  *                           rebuilt cluster bitsets masks_out[n_pick, words] with their sizes (0 = cluster vanished)
  *   pbn_bitmask_to_dense  : int32[n_rows, n_fold] 0/1 tensor of selected rows (the reference's `clusters`)
- * The greedy NMS between the two (tools/mIOU.py:77-87) runs on the host on a [P, P] matrix, as in the reference. */
+ * The greedy NMS between the two (tools/mIOU.py:77-87) runs on the host on a [P, P] matrix, as in the reference (the device-
+ * resident form below runs it on the device). */
 int pbn_post_words(int n_fold);
 int pbn_proposal_bitmask(const int64_t* proposals_idx, int n_entries, int n_fold, int n_prop, uint32_t* masks,
                          int32_t* counts, pbn_stream_t stream);
@@ -489,6 +490,46 @@ int pbn_superpoint_refine(const uint32_t* masks, const int32_t* pick, int n_pick
                           uint32_t* masks_out, int32_t* counts_out, pbn_stream_t stream);
 int pbn_bitmask_to_dense(const uint32_t* masks, const int32_t* rows, int n_rows, int n_fold, int32_t* dense,
                          pbn_stream_t stream);
+
+/* The device-resident form of the same step: every count lives in a device scalar (n_rows, n_pick, n_keep: int32[1]) and every
+ * table has the capacity n_prop = P, so no call reads anything back, takes a launch argument computed from device data or sizes an
+ * allocation from it.  Called in this order after pbn_proposal_bitmask; P <= pbn_post_max_proposals() (4096: k_post_nms keeps
+ * the survivors' scores, order and suppress flags in LDS), above it PBN_ERR_UNSUPPORTED.
+ *   pbn_post_select           : rows[P] = ascending proposals with clt_score > score_t (fp32 compare) and counts > npoint_t
+ *                               (eval_map.py:74-84), tail -1; writes n_rows and CLEARS status (the first launch of a call)
+ *   pbn_mask_iou_dev          : pbn_mask_iou for the first n_rows entries of rows; iou f32[P, P] with row stride P, entries
+ *                               outside [n_rows, n_rows) are left as they are
+ *   pbn_post_nms              : tools/mIOU.py:77-87 in one workgroup.  Walk order: score descending, among EQUAL scores the
+ *                               LOWER survivor index first (the reference's argsort()[::-1] leaves ties to numpy's sort); a
+ *                               survivor is picked when no earlier pick has iou[pick][it] > nms_t (fp32 `>`).  pick[P] =
+ *                               survivor positions in pick order, pick_rows[P] = their proposal indices, tails -1; n_pick
+ *   pbn_superpoint_refine_dev : pbn_superpoint_refine for the n_pick clusters of pick_rows.  hist int32[n_sp_cap, P + 1] (row
+ *                               stride P + 1, columns 0..n_pick live, bucket n_pick = unlabelled), sp_label int64[n_sp_cap],
+ *                               masks_out uint32[P, words], counts_out int32[P] (0 from row n_pick on).  A superpoint id >=
+ *                               n_sp_cap ORs 1 into status and takes no part (its point keeps -100); nothing is written
+ *                               outside the tables.  Negative ids take no part, as in pbn_superpoint_refine
+ *   pbn_post_compact          : keep[P] = the picked clusters with counts2 > 0 in order (eval_map.py:113-118), tail -1; n_keep;
+ *                               scores_out[k] = clt_score[pick_rows[keep[k]]], semantic_id_out[k] = label_table[pred_sem[first
+ *                               member]] (:63-65; proposals_offset / pred_sem are int64 or int32 per their flag; a missing
+ *                               member or a class outside [0, n_labels) gives -1 and ORs 2 into status), tails 0 / -1;
+ *                               clusters int32[P, n_fold] = the kept bitsets as 0/1 rows, rows from n_keep on zero.
+ *                               PBN_ERR_RANGE when P * n_fold reaches 2^39 elements */
+int pbn_post_max_proposals(void);
+int pbn_post_select(const float* clt_score, const int32_t* counts, int n_prop, float score_t, int npoint_t, int32_t* rows,
+                    int32_t* n_rows, int32_t* status, pbn_stream_t stream);
+int pbn_mask_iou_dev(const uint32_t* masks, const int32_t* rows, const int32_t* n_rows, int n_prop, int n_fold,
+                     const int32_t* counts, float* iou, pbn_stream_t stream);
+int pbn_post_nms(const float* clt_score, const int32_t* rows, const int32_t* n_rows, int n_prop, const float* iou, float nms_t,
+                 int32_t* pick, int32_t* pick_rows, int32_t* n_pick, pbn_stream_t stream);
+int pbn_superpoint_refine_dev(const uint32_t* masks, const int32_t* pick_rows, const int32_t* n_pick, int n_prop, int n_fold,
+                              const int64_t* superpoint, int n_sp_cap, int64_t* seg, int32_t* hist, int64_t* sp_label,
+                              int64_t* seg_refined, uint32_t* masks_out, int32_t* counts_out, int32_t* status,
+                              pbn_stream_t stream);
+int pbn_post_compact(const int32_t* counts2, const int32_t* pick_rows, const int32_t* n_pick, int n_prop, int n_fold,
+                     const float* clt_score, const int64_t* proposals_idx, int n_entries, const void* proposals_offset,
+                     int offset_i64, const void* pred_sem, int sem_i64, int64_t n_sem, const int64_t* label_table, int n_labels,
+                     const uint32_t* masks2, int32_t* keep, float* scores_out, int64_t* semantic_id_out, int32_t* clusters,
+                     int32_t* n_keep, int32_t* status, pbn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * ScanNet AP evaluator, the association step of /root/reference/tools/eval.py:205-250

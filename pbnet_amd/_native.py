@@ -140,6 +140,14 @@ SIGNATURES = {
     "pbn_superpoint_refine": (c_int, [c_vp, c_i32p, c_int, c_int, c_vp, c_int, c_vp, c_i32p, c_vp, c_vp, c_vp, c_i32p,
                                       c_vp]),
     "pbn_bitmask_to_dense": (c_int, [c_vp, c_i32p, c_int, c_int, c_i32p, c_vp]),
+    "pbn_post_max_proposals": (c_int, []),
+    "pbn_post_select": (c_int, [c_f32p, c_i32p, c_int, c_float, c_int, c_i32p, c_i32p, c_i32p, c_vp]),
+    "pbn_mask_iou_dev": (c_int, [c_vp, c_i32p, c_i32p, c_int, c_int, c_i32p, c_f32p, c_vp]),
+    "pbn_post_nms": (c_int, [c_f32p, c_i32p, c_i32p, c_int, c_f32p, c_float, c_i32p, c_i32p, c_i32p, c_vp]),
+    "pbn_superpoint_refine_dev": (c_int, [c_vp, c_i32p, c_i32p, c_int, c_int, c_vp, c_int, c_vp, c_i32p, c_vp, c_vp, c_vp, c_i32p,
+                                          c_i32p, c_vp]),
+    "pbn_post_compact": (c_int, [c_i32p, c_i32p, c_i32p, c_int, c_int, c_f32p, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_i64, c_vp,
+                                 c_int, c_vp, c_i32p, c_f32p, c_vp, c_i32p, c_i32p, c_i32p, c_vp]),
     "pbn_instance_overlap": (c_int, [c_i32p, c_int, c_int, c_i32p, c_int, c_i32p, c_vp]),
     "pbn_rulebook_pair_blocks": (c_int, [c_int]),
     "pbn_bn_workspace_bytes": (c_size, [c_int]),

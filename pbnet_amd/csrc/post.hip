@@ -3,7 +3,9 @@
 // superpoint vote (tools/getins.py:72-98) and the rebuilt cluster masks.  The reference builds dense [P, N] int masks
 // and a [P, P] product with torch.mm; here a proposal is a BITSET over the N/3 folded points (32 points per word), so
 // the IoU matrix is popcounts of ANDs and every step is integer work -- bit-exact by construction.
-// The greedy NMS itself (tools/mIOU.py:77-87: a few hundred scalars) stays on the host, exactly as the reference runs it.
+// In the first form (pbn_mask_iou .. pbn_bitmask_to_dense) the greedy NMS itself (tools/mIOU.py:77-87: a few hundred scalars)
+// stays on the host, exactly as the reference runs it; the device-resident form further down (pbn_post_select ..
+// pbn_post_compact) runs it in one workgroup and keeps every count in a device scalar.
 #include "pbn_common.h"
 
 namespace pbn {
@@ -103,6 +105,259 @@ __global__ __launch_bounds__(TPB) void k_bits_to_dense(const unsigned* __restric
     const int r = (int)(e / n_fold), pt = (int)(e - (long long)r * n_fold);
     const int src = rows ? rows[r] : r;
     dense[e] = (masks[(size_t)src * words + (pt >> 5)] >> (pt & 31)) & 1u;
+}
+
+// ---- the device-resident form (pbn_post_select .. pbn_post_compact) ------------------------------------------------------
+// The same arithmetic with every count (n_rows, n_pick, n_keep) kept in device scalars: grids are sized by the capacity P and
+// work items past the live count leave, so nothing between the first and the last launch waits for the host.
+
+constexpr int POST_MAX_PROPOSALS = 4096;        // k_post_nms keeps score, order and suppress flags of every survivor in LDS
+constexpr int POST_STATUS_SUPERPOINT = 1;       // a superpoint id >= n_sp_cap
+constexpr int POST_STATUS_CLASS = 2;            // a proposal without a first member, or a class outside the label table
+
+// exclusive position of `flag` among the 256 threads of the block, in thread order; *total = flags set.  s_wave: 4 ints.
+__device__ __forceinline__ int block_flag_scan(bool flag, int* s_wave, int* total) {
+    const unsigned long long b = __ballot(flag);
+    const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
+    __syncthreads();                               // the previous round's readers are done with s_wave
+    if (lane == 0) s_wave[wave] = __popcll(b);
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < TPB / 64; ++w) {
+        before += w < wave ? s_wave[w] : 0;
+        all += s_wave[w];
+    }
+    *total = all;
+    return before + __popcll(b & ((1ull << lane) - 1ull));
+}
+
+// rows = ascending proposals with score > score_t (fp32) and count > npoint_t (eval_map.py:74-84); the tail of rows is -1.
+// The first launch of a call: it also clears the status word.
+__global__ __launch_bounds__(TPB) void k_post_select(const float* __restrict__ score, const int* __restrict__ counts, int n_prop,
+                                                    float score_t, int npoint_t, int* __restrict__ rows,
+                                                    int* __restrict__ n_rows, int* __restrict__ status) {
+    __shared__ int s_wave[TPB / 64];
+    int base = 0;
+    for (int p0 = 0; p0 < n_prop; p0 += TPB) {     // uniform trip count: the scan needs whole blocks
+        const int p = p0 + threadIdx.x;
+        const bool flag = p < n_prop && score[p] > score_t && counts[p] > npoint_t;
+        int total;
+        const int pos = block_flag_scan(flag, s_wave, &total);
+        if (flag) rows[base + pos] = p;
+        base += total;
+    }
+    for (int p = base + threadIdx.x; p < n_prop; p += TPB) rows[p] = -1;
+    if (threadIdx.x == 0) { *n_rows = base; *status = 0; }
+}
+
+// k_mask_iou with the row count on the device: a fixed grid of one-wave workgroups strides over the n_rows^2 LIVE pairs, so the
+// cost follows n_rows, not the capacity; table row stride cap; entries outside [n_rows, n_rows) stay
+__global__ __launch_bounds__(64) void k_mask_iou_dev(const unsigned* __restrict__ masks, const int* __restrict__ rows,
+                                                    const int* __restrict__ n_rows_dev, int cap, int words,
+                                                    const int* __restrict__ counts, float* __restrict__ iou) {
+    const int n_rows = min(*n_rows_dev, cap);
+    const int n_pairs = n_rows * n_rows;           // cap <= 4096: fits
+    for (int e = blockIdx.x; e < n_pairs; e += gridDim.x) {      // uniform per wave: one pair per wave and trip
+        const int i = e / n_rows, j = e - i * n_rows;
+        const int ri = rows[i], rj = rows[j];
+        if (ri < 0 || ri >= cap || rj < 0 || rj >= cap) continue;
+        const unsigned* a = masks + (size_t)ri * words;
+        const unsigned* b = masks + (size_t)rj * words;
+        int c = 0;
+        for (int w = threadIdx.x; w < words; w += 64) c += __popc(a[w] & b[w]);
+        c = wave_reduce_add(c);
+        if (threadIdx.x == 0) {
+            const float inter = (float)c;
+            iou[(size_t)i * cap + j] = inter / (((float)counts[ri] + (float)counts[rj]) - inter);
+        }
+    }
+}
+
+// The greedy NMS of tools/mIOU.py:77-87 in one workgroup.  Order: score descending, among equal scores the LOWER survivor
+// index first; rank[i] = #{j : s[j] > s[i] or (s[j] == s[i] and j < i)} is a permutation (scores that passed `> score_t`
+// are not NaN), exact and stable, so the walk is the same on every run.  A survivor is picked when no earlier pick has
+// iou[pick][it] > nms_t (fp32 `>`: an IoU equal to the threshold does not suppress); after a pick every lane marks what that
+// pick suppresses.  pick = survivor positions in pick order, pick_rows = their proposal indices, tails -1.
+__global__ __launch_bounds__(TPB) void k_post_nms(const float* __restrict__ score, const int* __restrict__ rows,
+                                                 const int* __restrict__ n_rows_dev, int cap, const float* __restrict__ iou,
+                                                 float nms_t, int* __restrict__ pick, int* __restrict__ pick_rows,
+                                                 int* __restrict__ n_pick_dev) {
+    __shared__ float s_score[POST_MAX_PROPOSALS];
+    __shared__ unsigned short s_order[POST_MAX_PROPOSALS];
+    __shared__ unsigned char s_supp[POST_MAX_PROPOSALS];
+    const int n = min(*n_rows_dev, cap);
+    for (int i = threadIdx.x; i < n; i += TPB) {
+        const int r = rows[i];
+        s_score[i] = (r >= 0 && r < cap) ? score[r] : -INFINITY;
+        s_order[i] = (unsigned short)i;            // every slot names a survivor even if the ranks were no permutation (NaN)
+        s_supp[i] = 0;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += TPB) {
+        const float si = s_score[i];
+        int rank = 0;
+        for (int j = 0; j < n; ++j) {              // every lane reads the same word: an LDS broadcast
+            const float sj = s_score[j];
+            rank += (sj > si || (sj == si && j < i)) ? 1 : 0;
+        }
+        s_order[rank] = (unsigned short)i;
+    }
+    __syncthreads();
+    int n_pick = 0;
+    for (int k = 0; k < n; ++k) {
+        const int it = s_order[k];
+        if (s_supp[it]) continue;                  // uniform: every thread reads the same flag
+        if (threadIdx.x == 0) {
+            pick[n_pick] = it;
+            pick_rows[n_pick] = rows[it];
+        }
+        ++n_pick;
+        // `it` itself is left alone: a thread that has not read its flag yet must still see it clear
+        const float* row = iou + (size_t)it * cap;
+        for (int j = threadIdx.x; j < n; j += TPB)
+            if (j != it && row[j] > nms_t) s_supp[j] = 1;
+        __syncthreads();
+    }
+    for (int k = n_pick + threadIdx.x; k < cap; k += TPB) {
+        pick[k] = -1;
+        pick_rows[k] = -1;
+    }
+    if (threadIdx.x == 0) *n_pick_dev = n_pick;
+}
+
+// zero what the vote accumulates into: hist columns [0, n_pick] of every row and the n_pick rebuilt bitsets
+__global__ __launch_bounds__(TPB) void k_refine_clear(const int* __restrict__ n_pick_dev, int cap, int n_sp, int words,
+                                                     int* __restrict__ hist, unsigned* __restrict__ masks_out) {
+    const int n_pick = min(*n_pick_dev, cap);
+    const long long n_hist = (long long)n_sp * (n_pick + 1), n_mask = (long long)n_pick * words;
+    const long long step = (long long)gridDim.x * TPB;
+    for (long long e = (long long)blockIdx.x * TPB + threadIdx.x; e < n_hist; e += step) {
+        const long long sp = e / (n_pick + 1);
+        hist[sp * (cap + 1) + (e - sp * (n_pick + 1))] = 0;
+    }
+    for (long long e = (long long)blockIdx.x * TPB + threadIdx.x; e < n_mask; e += step) masks_out[e] = 0u;
+}
+
+__global__ __launch_bounds__(TPB) void k_point_labels_dev(const unsigned* __restrict__ masks, const int* __restrict__ pick_rows,
+                                                         const int* __restrict__ n_pick_dev, int cap, int words, int n_fold,
+                                                         long long* __restrict__ seg) {
+    const int pt = blockIdx.x * TPB + threadIdx.x;
+    if (pt >= n_fold) return;
+    const int n_pick = min(*n_pick_dev, cap);
+    long long lab = -100;
+    for (int c = n_pick - 1; c >= 0; --c)
+        if ((masks[(size_t)pick_rows[c] * words + (pt >> 5)] >> (pt & 31)) & 1u) { lab = c; break; }
+    seg[pt] = lab;
+}
+
+// k_sp_hist on the table hist[n_sp, cap + 1] (bucket n_pick = unlabelled); an id >= n_sp is reported, never counted
+__global__ __launch_bounds__(TPB) void k_sp_hist_dev(const long long* __restrict__ seg, const long long* __restrict__ superpoint,
+                                                    int n, int n_sp, const int* __restrict__ n_pick_dev, int cap,
+                                                    int* __restrict__ hist, int* __restrict__ status) {
+    const int pt = blockIdx.x * TPB + threadIdx.x;
+    if (pt >= n) return;
+    const long long sp = superpoint[pt];
+    if (sp >= n_sp) { atomicOr(status, POST_STATUS_SUPERPOINT); return; }
+    if (sp < 0) return;
+    const int n_label = min(*n_pick_dev, cap);
+    long long l = seg[pt];
+    if (l < 0 || l > n_label) l = n_label;
+    atomicAdd(&hist[(size_t)sp * (cap + 1) + l], 1);
+}
+
+__global__ __launch_bounds__(TPB) void k_sp_argmax_dev(const int* __restrict__ hist, int n_sp, const int* __restrict__ n_pick_dev,
+                                                      int cap, long long* __restrict__ sp_label) {
+    const int sp = blockIdx.x * TPB + threadIdx.x;
+    if (sp >= n_sp) return;
+    const int n_label = min(*n_pick_dev, cap);
+    const int* h = hist + (size_t)sp * (cap + 1);
+    int best = h[0], arg = 0;
+    for (int l = 1; l <= n_label; ++l)
+        if (h[l] > best) { best = h[l]; arg = l; }
+    sp_label[sp] = arg == n_label ? -100 : arg;
+}
+
+__global__ __launch_bounds__(TPB) void k_relabel_points_dev(const long long* __restrict__ sp_label,
+                                                           const long long* __restrict__ superpoint, int n, int n_sp,
+                                                           const int* __restrict__ n_pick_dev, int cap, int words,
+                                                           long long* __restrict__ seg2, unsigned* __restrict__ masks_out) {
+    const int pt = blockIdx.x * TPB + threadIdx.x;
+    if (pt >= n) return;
+    const int n_label = min(*n_pick_dev, cap);
+    const long long sp = superpoint[pt];
+    const long long l = (sp >= 0 && sp < n_sp) ? sp_label[sp] : -100;
+    seg2[pt] = l;
+    if (l >= 0 && l < n_label) atomicOr(&masks_out[(size_t)l * words + (pt >> 5)], 1u << (pt & 31));
+}
+
+// counts[c] = popcount of rebuilt row c for c < n_pick, 0 above (grid = cap rows, one wave each)
+__global__ __launch_bounds__(64) void k_row_popcount_dev(const unsigned* __restrict__ masks, int words,
+                                                        const int* __restrict__ n_rows_dev, int cap, int* __restrict__ counts) {
+    int c = 0;
+    if ((int)blockIdx.x < min(*n_rows_dev, cap)) {
+        const unsigned* row = masks + (size_t)blockIdx.x * words;
+        for (int w = threadIdx.x; w < words; w += 64) c += __popc(row[w]);
+        c = wave_reduce_add(c);
+    }
+    if (threadIdx.x == 0) counts[blockIdx.x] = c;
+}
+
+// keep = the picked clusters that still own a point, in order (eval_map.py:113-118), with their score and the class of the
+// proposal's first member (:63-65) through the label table; tails: keep -1, score 0, class -1
+__global__ __launch_bounds__(TPB) void k_post_compact(const int* __restrict__ counts2, const int* __restrict__ pick_rows,
+                                                     const int* __restrict__ n_pick_dev, int cap, const float* __restrict__ score,
+                                                     const long long* __restrict__ proposals_idx, int n_entries,
+                                                     const void* __restrict__ offsets, int offsets_i64,
+                                                     const void* __restrict__ pred_sem, int sem_i64, long long n_sem,
+                                                     const long long* __restrict__ label_table, int n_labels,
+                                                     int* __restrict__ keep, float* __restrict__ scores_out,
+                                                     long long* __restrict__ sem_out, int* __restrict__ n_keep_dev,
+                                                     int* __restrict__ status) {
+    __shared__ int s_wave[TPB / 64];
+    const int n_pick = min(*n_pick_dev, cap);
+    int base = 0;
+    for (int c0 = 0; c0 < n_pick; c0 += TPB) {
+        const int c = c0 + threadIdx.x;
+        const bool flag = c < n_pick && counts2[c] > 0;
+        int total;
+        const int pos = block_flag_scan(flag, s_wave, &total);
+        if (flag) {
+            const int p = pick_rows[c];
+            const long long e = offsets_i64 ? ((const long long*)offsets)[p] : (long long)((const int*)offsets)[p];
+            long long cls = -1;
+            if (e >= 0 && e < n_entries) {
+                const long long pt = proposals_idx[2 * e + 1];
+                if (pt >= 0 && pt < n_sem) {
+                    const long long s = sem_i64 ? ((const long long*)pred_sem)[pt] : (long long)((const int*)pred_sem)[pt];
+                    if (s >= 0 && s < n_labels) cls = label_table[s];
+                }
+            }
+            if (cls < 0) atomicOr(status, POST_STATUS_CLASS);
+            keep[base + pos] = c;
+            scores_out[base + pos] = score[p];
+            sem_out[base + pos] = cls;
+        }
+        base += total;
+    }
+    for (int k = base + threadIdx.x; k < cap; k += TPB) {
+        keep[k] = -1;
+        scores_out[k] = 0.f;
+        sem_out[k] = -1;
+    }
+    if (threadIdx.x == 0) *n_keep_dev = base;
+}
+
+// k_bits_to_dense over the whole capacity: rows below n_keep are the kept bitsets, the rest zero
+__global__ __launch_bounds__(TPB) void k_bits_to_dense_dev(const unsigned* __restrict__ masks, const int* __restrict__ keep,
+                                                          const int* __restrict__ n_keep_dev, int cap, int words, int n_fold,
+                                                          int* __restrict__ dense) {
+    const long long e = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (e >= (long long)cap * n_fold) return;
+    const int r = (int)(e / n_fold), pt = (int)(e - (long long)r * n_fold);
+    int v = 0;
+    if (r < min(*n_keep_dev, cap)) v = (masks[(size_t)keep[r] * words + (pt >> 5)] >> (pt & 31)) & 1u;
+    dense[e] = v;
 }
 
 // inter[p][gt_index[i]] += 1 for every point i inside prediction p (mask value != 0): the association counts of
@@ -220,6 +475,93 @@ extern "C" int pbn_bitmask_to_dense(const uint32_t* masks, const int32_t* rows, 
     if (!masks || !dense) return PBN_ERR_ARG;
     hipLaunchKernelGGL(k_bits_to_dense, dim3(cdiv((long long)n_rows * n_fold, TPB)), dim3(TPB), 0, stream, masks, rows, n_rows,
                        pbn_post_words(n_fold), n_fold, dense);
+    PBN_LAUNCH_CHECK();
+    return PBN_OK;
+}
+
+extern "C" int pbn_post_max_proposals(void) { return POST_MAX_PROPOSALS; }
+
+extern "C" int pbn_post_select(const float* clt_score, const int32_t* counts, int n_prop, float score_t, int npoint_t,
+                               int32_t* rows, int32_t* n_rows, int32_t* status, pbn_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_prop < 1 || !clt_score || !counts || !rows || !n_rows || !status) return PBN_ERR_ARG;
+    if (n_prop > POST_MAX_PROPOSALS) return PBN_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_post_select, dim3(1), dim3(TPB), 0, stream, clt_score, counts, n_prop, score_t, npoint_t, rows, n_rows,
+                       status);
+    PBN_LAUNCH_CHECK();
+    return PBN_OK;
+}
+
+extern "C" int pbn_mask_iou_dev(const uint32_t* masks, const int32_t* rows, const int32_t* n_rows, int n_prop, int n_fold,
+                                const int32_t* counts, float* iou, pbn_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_prop < 1 || n_fold < 1 || !masks || !rows || !n_rows || !counts || !iou) return PBN_ERR_ARG;
+    if (n_prop > POST_MAX_PROPOSALS) return PBN_ERR_UNSUPPORTED;
+    const long long pairs = (long long)n_prop * n_prop;
+    hipLaunchKernelGGL(k_mask_iou_dev, dim3((unsigned)(pairs < 8192 ? pairs : 8192)), dim3(64), 0, stream, masks, rows, n_rows, n_prop,
+                       pbn_post_words(n_fold), counts, iou);
+    PBN_LAUNCH_CHECK();
+    return PBN_OK;
+}
+
+extern "C" int pbn_post_nms(const float* clt_score, const int32_t* rows, const int32_t* n_rows, int n_prop, const float* iou,
+                            float nms_t, int32_t* pick, int32_t* pick_rows, int32_t* n_pick, pbn_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_prop < 1 || !clt_score || !rows || !n_rows || !iou || !pick || !pick_rows || !n_pick) return PBN_ERR_ARG;
+    if (n_prop > POST_MAX_PROPOSALS) return PBN_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_post_nms, dim3(1), dim3(TPB), 0, stream, clt_score, rows, n_rows, n_prop, iou, nms_t, pick, pick_rows,
+                       n_pick);
+    PBN_LAUNCH_CHECK();
+    return PBN_OK;
+}
+
+extern "C" int pbn_superpoint_refine_dev(const uint32_t* masks, const int32_t* pick_rows, const int32_t* n_pick, int n_prop,
+                                         int n_fold, const int64_t* superpoint, int n_sp_cap, int64_t* seg, int32_t* hist,
+                                         int64_t* sp_label, int64_t* seg_refined, uint32_t* masks_out, int32_t* counts_out,
+                                         int32_t* status, pbn_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_prop < 1 || n_fold < 1 || n_sp_cap < 1) return PBN_ERR_ARG;
+    if (!masks || !pick_rows || !n_pick || !superpoint || !seg || !hist || !sp_label || !seg_refined || !masks_out ||
+        !counts_out || !status)
+        return PBN_ERR_ARG;
+    if (n_prop > POST_MAX_PROPOSALS) return PBN_ERR_UNSUPPORTED;
+    const int words = pbn_post_words(n_fold);
+    const int nb = cdiv(n_fold, TPB);
+    const long long clear_max = (long long)n_sp_cap * (n_prop + 1) > (long long)n_prop * words ? (long long)n_sp_cap * (n_prop + 1)
+                                                                                                : (long long)n_prop * words;
+    const int clear_blocks = (int)(clear_max / TPB + 1 < 2048 ? clear_max / TPB + 1 : 2048);
+    hipLaunchKernelGGL(k_refine_clear, dim3(clear_blocks), dim3(TPB), 0, stream, n_pick, n_prop, n_sp_cap, words, hist, masks_out);
+    hipLaunchKernelGGL(k_point_labels_dev, dim3(nb), dim3(TPB), 0, stream, masks, pick_rows, n_pick, n_prop, words, n_fold,
+                       (long long*)seg);
+    hipLaunchKernelGGL(k_sp_hist_dev, dim3(nb), dim3(TPB), 0, stream, (const long long*)seg, (const long long*)superpoint, n_fold,
+                       n_sp_cap, n_pick, n_prop, hist, status);
+    hipLaunchKernelGGL(k_sp_argmax_dev, dim3(cdiv(n_sp_cap, TPB)), dim3(TPB), 0, stream, hist, n_sp_cap, n_pick, n_prop,
+                       (long long*)sp_label);
+    hipLaunchKernelGGL(k_relabel_points_dev, dim3(nb), dim3(TPB), 0, stream, (const long long*)sp_label,
+                       (const long long*)superpoint, n_fold, n_sp_cap, n_pick, n_prop, words, (long long*)seg_refined, masks_out);
+    hipLaunchKernelGGL(k_row_popcount_dev, dim3(n_prop), dim3(64), 0, stream, masks_out, words, n_pick, n_prop, counts_out);
+    PBN_LAUNCH_CHECK();
+    return PBN_OK;
+}
+
+extern "C" int pbn_post_compact(const int32_t* counts2, const int32_t* pick_rows, const int32_t* n_pick, int n_prop, int n_fold,
+                                const float* clt_score, const int64_t* proposals_idx, int n_entries, const void* proposals_offset,
+                                int offset_i64, const void* pred_sem, int sem_i64, int64_t n_sem, const int64_t* label_table,
+                                int n_labels, const uint32_t* masks2, int32_t* keep, float* scores_out, int64_t* semantic_id_out,
+                                int32_t* clusters, int32_t* n_keep, int32_t* status, pbn_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_prop < 1 || n_fold < 1 || n_entries < 0 || n_sem < 0 || n_labels < 1) return PBN_ERR_ARG;
+    if (!counts2 || !pick_rows || !n_pick || !clt_score || !proposals_idx || !proposals_offset || !pred_sem || !label_table ||
+        !masks2 || !keep || !scores_out || !semantic_id_out || !clusters || !n_keep || !status)
+        return PBN_ERR_ARG;
+    if (n_prop > POST_MAX_PROPOSALS) return PBN_ERR_UNSUPPORTED;
+    if (((long long)n_prop * n_fold + TPB - 1) / TPB > 0x7fffffffLL) return PBN_ERR_RANGE;
+    hipLaunchKernelGGL(k_post_compact, dim3(1), dim3(TPB), 0, stream, counts2, pick_rows, n_pick, n_prop, clt_score,
+                       (const long long*)proposals_idx, n_entries, proposals_offset, offset_i64, pred_sem, sem_i64,
+                       (long long)n_sem, (const long long*)label_table, n_labels, keep, scores_out, (long long*)semantic_id_out,
+                       n_keep, status);
+    hipLaunchKernelGGL(k_bits_to_dense_dev, dim3(cdiv((long long)n_prop * n_fold, TPB)), dim3(TPB), 0, stream, masks2, keep, n_keep,
+                       n_prop, pbn_post_words(n_fold), n_fold, clusters);
     PBN_LAUNCH_CHECK();
     return PBN_OK;
 }

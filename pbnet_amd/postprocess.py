@@ -4,7 +4,11 @@
 `refine_instances` takes exactly what eval_map.py has in hand at line 55 (the `pred` dict of model_fn_eval, the number of
 points of the 3-copy batch and the scene's superpoint ids) and returns what it holds at line 118:
 (clusters i32[C, N/3], cluster_scores [C], cluster_semantic_id i64[C]) on the device.  Masks are bitsets on the device
-(csrc/post.hip); the greedy NMS runs on the host on a [P, P] matrix with the reference's own numpy statements."""
+(csrc/post.hip); the greedy NMS runs on the host on a [P, P] matrix with the reference's own numpy statements.
+
+`refine_instances_device` is the same step without the five host stops of `refine_instances` (the threshold read-back, the IoU
+read-back, `sp.max().item()`, the vanished-cluster read-back and the index uploads): every count stays in a device scalar until
+the caller asks for `.sliced()`."""
 import numpy as np
 import torch
 
@@ -87,3 +91,142 @@ def refine_instances(pred_sem, proposals, clt_scores, point_num, superpoint, cfg
     if return_debug:
         return out + (dict(pointnum=counts, cross_ious=iou, pick=pick, seg=seg, seg_refined=seg2),)
     return out
+
+
+# ---- the device-resident form -------------------------------------------------------------------------------------------
+STATUS_SUPERPOINT_RANGE, STATUS_CLASS_RANGE = 1, 2          # bits of RefinedInstances.status (csrc/post.hip)
+
+
+class PostWorkspace(object):
+    """Every buffer `refine_instances_device` touches, outputs included, sized from capacities (P, n_fold, n_superpoints).
+
+    A call with sizes that fit (`fits`) allocates nothing: it works on leading views of the flat buffers.  The results of a
+    call ALIAS these buffers, so the next call on the same workspace overwrites them.  One workspace per stream."""
+
+    def __init__(self, n_prop, n_fold, n_superpoints, device):
+        p, f, s = max(int(n_prop), 1), max(int(n_fold), 1), max(int(n_superpoints), 1)
+        if p > N.lib().pbn_post_max_proposals():
+            raise ValueError("the device form takes at most %d proposals, got %d" % (N.lib().pbn_post_max_proposals(), p))
+        self.n_prop, self.n_fold, self.n_superpoints = p, f, s
+        self.device = torch.device(device)
+        w = N.lib().pbn_post_words(f)
+        i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=self.device)
+        i64 = lambda n: torch.zeros(n, dtype=torch.int64, device=self.device)
+        self.masks, self.masks2 = i32(p * w), i32(p * w)
+        self.counts, self.counts2, self.rows, self.pick, self.pick_rows, self.keep = (i32(p) for _ in range(6))
+        self.iou = torch.zeros(p * p, dtype=torch.float32, device=self.device)
+        self.seg, self.seg_refined, self.sp_label = i64(f), i64(f), i64(s)
+        self.hist = i32(s * (p + 1))
+        self.scores = torch.zeros(p, dtype=torch.float32, device=self.device)
+        self.semantic_id = i64(p)
+        self.clusters = i32(p * f)
+        self.scalars = i32(4)                                   # n_rows, n_pick, n_keep, status
+        self.label_table = torch.tensor(SEMANTIC_LABEL_IDX, dtype=torch.int64, device=self.device)
+
+    def fits(self, n_prop, n_fold, n_superpoints):
+        return n_prop <= self.n_prop and n_fold <= self.n_fold and n_superpoints <= self.n_superpoints
+
+
+class RefinedInstances(object):
+    """What `refine_instances_device` leaves on the device.  Capacity-sized tensors (P = number of proposals): clusters
+    i32[P, n_fold] (rows from n_keep on are zero), scores f32[P], semantic_id i64[P], pick i32[P] (survivor positions in pick
+    order, tail -1), seg / seg_refined i64[n_fold]; the debug tables pointnum i32[P], rows i32[P], cross_ious f32[P, P] (live in
+    [:n_rows, :n_rows]), pick_rows, keep; the device scalars n_rows, n_pick, n_keep, status (views of `scalars` i32[4]).
+    Nothing here has been read back; `sliced()` is the one method that synchronises -- unless the caller has already read
+    `scalars` back together with other values (ValidationEpoch does) and hands the four integers in: then it only slices."""
+
+    def __init__(self, ws, n_prop, n_fold, views):
+        self.workspace, self.n_prop, self.n_fold = ws, n_prop, n_fold
+        self.clusters, self.scores, self.semantic_id = views["clusters"], views["scores"], views["semantic_id"]
+        self.pick, self.seg, self.seg_refined = views["pick"], views["seg"], views["seg_refined"]
+        self.pointnum, self.rows, self.cross_ious = views["pointnum"], views["rows"], views["cross_ious"]
+        self.pick_rows, self.keep = views["pick_rows"], views["keep"]
+        self.scalars = ws.scalars
+        self.n_rows, self.n_pick, self.n_keep, self.status = (ws.scalars[i] for i in range(4))
+
+    def sliced(self, scalars=None):
+        """(clusters i32[n_keep, n_fold], scores [n_keep], semantic_id i64[n_keep]): exactly what `refine_instances` returns.
+        One read-back of the four scalars, unless the caller has made it already and passes the four values.  ValueError when
+        the status word is set (a superpoint id >= n_superpoints, or a proposal whose class cannot be looked up)."""
+        n_rows, n_pick, n_keep, status = (int(v) for v in (self.scalars.tolist() if scalars is None else scalars))
+        if status & STATUS_SUPERPOINT_RANGE:
+            raise ValueError("a superpoint id is >= n_superpoints: pass the scene's real superpoint count (or leave the default)")
+        if status & STATUS_CLASS_RANGE:
+            raise ValueError("a kept proposal has no first member, or its predicted class is outside the label table")
+        return self.clusters[:n_keep], self.scores[:n_keep], self.semantic_id[:n_keep]
+
+
+def refine_instances_device(pred_sem, proposals, clt_scores, point_num, superpoint, cfg, n_superpoints=None, workspace=None):
+    """`refine_instances` without a host read-back, a host-computed launch argument or an allocation sized from device data
+    between its first and its last launch: thresholds, mask IoU, greedy NMS, superpoint vote and compaction are fourteen launches
+    whose counts (n_rows, n_pick, n_keep) stay in device scalars.  Returns a `RefinedInstances`; `.sliced()` gives the host
+    form's triple.  The call can be captured in a graph and enqueued ahead of the previous scene's read-back.
+
+    Tie rule of the NMS: score descending, among equal scores the lower survivor index first.  The host form inherits the tie
+    order of numpy's (unstable) argsort; the two agree whenever the surviving scores are distinct.
+
+    `superpoint` must be a device int64 tensor of n_fold ids (a numpy array is uploaded once by the caller, not here).
+    `n_superpoints` bounds the ids from above and sizes the vote table [n_superpoints, P + 1] int32; the default n_fold is always
+    enough (an id can never exceed the number of points) but makes that table n_fold x (P + 1): a loader that knows the scene's
+    superpoint count should pass it.  An id >= n_superpoints sets bit 1 of `status` (and `.sliced()` raises); nothing is written
+    out of bounds.  `workspace`: a `PostWorkspace` that fits (P, n_fold, n_superpoints) -- a call with one allocates nothing
+    (given float32 scores and contiguous inputs); None allocates a fresh one.  At most 4096 proposals."""
+    proposals_idx, proposals_offset = proposals[0], proposals[1]
+    N.require_cuda(proposals_idx, proposals_offset, pred_sem, clt_scores, superpoint)
+    if superpoint.dtype != torch.int64:
+        raise TypeError("superpoint must be an int64 device tensor, got %s" % superpoint.dtype)
+    for name, t in (("proposals_offset", proposals_offset), ("pred_sem", pred_sem)):
+        if t.dtype not in (torch.int32, torch.int64):
+            raise TypeError("%s must be int32 or int64, got %s" % (name, t.dtype))
+    dev = proposals_idx.device
+    lib = N.lib()
+    st = N.current_stream()
+    n_fold = int(point_num) // 3
+    n_prop = int(proposals_offset.shape[0]) - 1
+    if n_fold < 1 or int(superpoint.numel()) < n_fold:
+        raise ValueError("superpoint holds %d ids for %d folded points" % (superpoint.numel(), n_fold))
+    n_sp = n_fold if n_superpoints is None else int(n_superpoints)
+    if n_sp < 1:
+        raise ValueError("n_superpoints must be positive, got %d" % n_sp)
+    ws = workspace
+    if ws is None:
+        ws = PostWorkspace(n_prop, n_fold, n_sp, dev)
+    elif not ws.fits(n_prop, n_fold, n_sp):
+        raise ValueError("workspace (%d, %d, %d) does not fit (%d, %d, %d)" % (ws.n_prop, ws.n_fold, ws.n_superpoints, n_prop,
+                                                                              n_fold, n_sp))
+    p = max(n_prop, 0)
+    words = lib.pbn_post_words(n_fold)
+    views = dict(clusters=ws.clusters[:p * n_fold].view(p, n_fold), scores=ws.scores[:p], semantic_id=ws.semantic_id[:p],
+                 pick=ws.pick[:p], pick_rows=ws.pick_rows[:p], keep=ws.keep[:p], rows=ws.rows[:p], pointnum=ws.counts[:p],
+                 cross_ious=ws.iou[:p * p].view(p, p), seg=ws.seg[:n_fold], seg_refined=ws.seg_refined[:n_fold])
+    res = RefinedInstances(ws, p, n_fold, views)
+    if p == 0:
+        ws.scalars.zero_()
+        return res
+    clt_score = clt_scores.view(-1)
+    clt_score = clt_score if clt_score.dtype == torch.float32 else clt_score.float()
+    pidx = proposals_idx.contiguous()
+    off, sem, sp = proposals_offset.contiguous(), pred_sem.contiguous(), superpoint.contiguous()
+    n_rows, n_pick, n_keep, status = (_elem_ptr(ws.scalars, i) for i in range(4))
+    N.check(lib.pbn_proposal_bitmask(N.ptr(pidx), int(pidx.shape[0]), n_fold, p, N.ptr(ws.masks), N.ptr(ws.counts), st),
+            "pbn_proposal_bitmask")
+    N.check(lib.pbn_post_select(N.ptr(clt_score), N.ptr(ws.counts), p, float(cfg.TEST_SCORE_THRESH), int(cfg.TEST_NPOINT_THRESH),
+                                N.ptr(ws.rows), n_rows, status, st), "pbn_post_select")
+    N.check(lib.pbn_mask_iou_dev(N.ptr(ws.masks), N.ptr(ws.rows), n_rows, p, n_fold, N.ptr(ws.counts), N.ptr(ws.iou), st),
+            "pbn_mask_iou_dev")
+    N.check(lib.pbn_post_nms(N.ptr(clt_score), N.ptr(ws.rows), n_rows, p, N.ptr(ws.iou), float(cfg.TEST_NMS_THRESH),
+                             N.ptr(ws.pick), N.ptr(ws.pick_rows), n_pick, st), "pbn_post_nms")
+    N.check(lib.pbn_superpoint_refine_dev(N.ptr(ws.masks), N.ptr(ws.pick_rows), n_pick, p, n_fold, N.ptr(sp), n_sp, N.ptr(ws.seg),
+                                          N.ptr(ws.hist), N.ptr(ws.sp_label), N.ptr(ws.seg_refined), N.ptr(ws.masks2),
+                                          N.ptr(ws.counts2), status, st), "pbn_superpoint_refine_dev")
+    N.check(lib.pbn_post_compact(N.ptr(ws.counts2), N.ptr(ws.pick_rows), n_pick, p, n_fold, N.ptr(clt_score), N.ptr(pidx),
+                                 int(pidx.shape[0]), N.ptr(off), int(off.dtype == torch.int64), N.ptr(sem),
+                                 int(sem.dtype == torch.int64), int(sem.numel()), N.ptr(ws.label_table),
+                                 int(ws.label_table.numel()), N.ptr(ws.masks2), N.ptr(ws.keep), N.ptr(ws.scores),
+                                 N.ptr(ws.semantic_id), N.ptr(ws.clusters), n_keep, status, st), "pbn_post_compact")
+    return res
+
+
+def _elem_ptr(t, i):
+    """Address of element i of a contiguous tensor."""
+    return N.c_vp(t.data_ptr() + i * t.element_size())

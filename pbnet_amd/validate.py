@@ -1,7 +1,8 @@
 """The validation epoch of /root/reference/train.py:123-304 (`eval_epoch`) on this package: semantic mIoU / mAcc / allAcc
 (`tools/mIOU.py:18-31` intersectionAndUnionGPU, train.py:133-149,279-283), the mask-branch accuracies All / Tp / Tf
-(train.py:152-168) and the AP of the instance branch (train.py:171-253,286-288 = postprocess.refine_instances +
-evaluate.*), as meters whose counters are int64 and live on the device (csrc/metrics.hip).
+(train.py:152-168) and the AP of the instance branch (train.py:171-253,286-288 = postprocess.refine_instances, or
+with cfg.device_post its device-resident form, + evaluate.*), as meters whose counters are int64 and live on the device
+(csrc/metrics.hip).
 
 What changes against the reference is where the counting happens and in what type, not what is counted:
 
@@ -298,6 +299,8 @@ class ValidationEpoch(object):
         self.model_fn = _default_model_fn if model_fn is None else model_fn
         self.gt, self.logger, self.writer, self.reduce, self.progress = gt, logger, writer, reduce, progress
         self.cluster = self.epoch > cfg.cluster_epoch
+        self.device_post = bool(getattr(cfg, "device_post", False))     # absent = off: postprocess.refine_instances
+        self._post_ws = self._sup_pin = self._sup_dev = None
         self.semantic = SemanticMeter(cfg.sem_num, -100, device=device)
         self.mask = MaskAccuracyMeter(0.5)
         self.am_dict, self.visual_keys, self.matches = {}, set(), {}
@@ -320,6 +323,49 @@ class ValidationEpoch(object):
             return self.gt(name)
         return os.path.join(self.gt, name + ".txt")
 
+    @staticmethod
+    def _read_weights(weights, scalars):
+        """The loss-meter weights that are device scalars (and, with them, the int32 scalars of the device post-processing) in
+        ONE read-back: (weights as Python floats, scalars as ints)."""
+        dev_w = [w.detach().double().reshape(()) for w in weights if torch.is_tensor(w)]
+        parts = ([torch.stack(dev_w)] if dev_w else []) + ([scalars.double()] if scalars is not None else [])
+        host = torch.cat(parts).tolist() if parts else []
+        return host[:len(dev_w)], [int(v) for v in host[len(dev_w):]]
+
+    def _upload_ids(self, ids, dev):
+        """Host superpoint ids -> device int64 through a pinned staging buffer and an asynchronous copy (a copy from pageable
+        memory would hold the host until it is done).  Both buffers grow only; the staging buffer is free again by the next
+        step because every step ends in a read-back."""
+        n = int(ids.shape[0])
+        if self._sup_pin is None or self._sup_pin.numel() < n or self._sup_dev.device != dev:
+            self._sup_pin = torch.empty(n, dtype=torch.int64).pin_memory()
+            self._sup_dev = torch.empty(n, dtype=torch.int64, device=dev)
+        self._sup_pin[:n].copy_(torch.from_numpy(np.ascontiguousarray(ids).reshape(-1)))
+        self._sup_dev[:n].copy_(self._sup_pin[:n], non_blocking=True)
+        return self._sup_dev[:n]
+
+    def _refine_on_device(self, pred, point_num, sup, meter_dict):
+        """cfg.device_post: postprocess.refine_instances_device; n_keep and the status word travel with the loss-meter weights."""
+        from .postprocess import PostWorkspace, refine_instances_device
+        dev = pred["sem"].device
+        n_fold = point_num // 3
+        n_sp = None
+        if not (torch.is_tensor(sup) and sup.is_cuda):          # host ids: their bound costs no device read-back
+            sup = np.asarray(sup)
+            n_sp = int(sup.max()) + 1 if sup.size else 1
+            sup = self._upload_ids(sup, dev)
+        elif sup.dtype != torch.int64:
+            sup = sup.long()
+        need = (int(pred["proposals"][1].shape[0]) - 1, n_fold, n_fold if n_sp is None else n_sp)
+        ws = self._post_ws
+        if ws is None or ws.device != dev or not ws.fits(*need):
+            grown = need if ws is None else (max(need[0], ws.n_prop), max(need[1], ws.n_fold), max(need[2], ws.n_superpoints))
+            ws = self._post_ws = PostWorkspace(grown[0], grown[1], grown[2], dev)
+        res = refine_instances_device(pred["sem"], pred["proposals"], pred["clt_scores"], point_num, sup, self.cfg,
+                                      n_superpoints=n_sp, workspace=ws)
+        host_w, scalars = self._read_weights([meter_dict[k][1] for k in meter_dict], res.scalars)
+        return res.sliced(scalars), host_w
+
     def step(self, batch):
         from . import evaluate
         from .postprocess import refine_instances
@@ -330,6 +376,7 @@ class ValidationEpoch(object):
         with torch.no_grad():
             loss, pred, visual_dict, meter_dict = self.model_fn(batch, self.model, self.epoch, self.cfg, task="eval")
             self.steps += 1
+            host_w = None
             # train.py:144-149
             sem_label = torch.as_tensor(batch["sem"]).to(pred["sem"].device)
             self.semantic.update(pred["sem"], sem_label if sem_label.dtype in _LABEL_DTYPES else sem_label.long())
@@ -339,8 +386,12 @@ class ValidationEpoch(object):
                 # train.py:171-253
                 name = fn[0]
                 point_num = int(batch["xyz_original"].shape[0])
-                clusters, scores, sem_id = refine_instances(pred["sem"], pred["proposals"], pred["clt_scores"], point_num,
-                                                            batch["sup"], self.cfg)
+                if self.device_post:
+                    refined, host_w = self._refine_on_device(pred, point_num, batch["sup"], meter_dict)
+                    clusters, scores, sem_id = refined
+                else:
+                    clusters, scores, sem_id = refine_instances(pred["sem"], pred["proposals"], pred["clt_scores"], point_num,
+                                                                batch["sup"], self.cfg)
                 if clusters.shape[0] == 0:
                     # train.py:217-219: the `continue` sits ABOVE the loss-meter update (:258-261), so a scene without
                     # clusters is missing from the loss averages too; kept
@@ -352,8 +403,9 @@ class ValidationEpoch(object):
             # train.py:258-261 on Python floats; the weights are device scalars: one read-back for all of them
             keys = list(meter_dict)
             weights = [meter_dict[k][1] for k in keys]
-            dev_w = [w.detach().double().reshape(()) for w in weights if torch.is_tensor(w)]
-            host_w = iter(torch.stack(dev_w).tolist() if dev_w else [])
+            if host_w is None:
+                host_w = self._read_weights(weights, None)[0]
+            host_w = iter(host_w)
             for k, w in zip(keys, weights):
                 v = meter_dict[k][0]
                 self.am_dict.setdefault(k, AverageMeter()).update(float(v), next(host_w) if torch.is_tensor(w) else float(w))
