@@ -548,6 +548,54 @@ int pbn_instance_overlap(const int32_t* masks, int n_pred, int n_pts, const int3
                          pbn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The same association without a host stop (csrc/apassoc.hip; pbnet_amd/evaluate.py AssociationLog).  Capacities (p_cap,
+ * u_cap, id_cap, n_inst_cap, log_words) come from the host; the live counts n_keep and n_gt are device scalars.  Grids are
+ * sized by capacity or fixed and striding, work past a live count leaves, only integer atomics are used (bit-identical from
+ * run to run) and nothing waits for the host.  Status bits are ORed into a device word; pbn_ap_record_append consumes it.
+ *   pbn_gt_encode_dev        : get_val_gt.py:26-37.  sem / ins: int32 or int64 [n_pts] per their flag; first int32[n_inst_cap]
+ *                              is working memory (lowest point index per instance, by atomicMin); ids int32[n_pts] =
+ *                              label_table[sem of that point] * 1000 + instance + 1 (semantic -100 = class 0), 0 where
+ *                              ins < 0.  An instance id >= n_inst_cap ORs INSTANCE_CAP, a semantic label other than -100
+ *                              outside [0, n_labels) ORs SEMANTIC_RANGE; such points get id 0, nothing is written out of bounds
+ *   pbn_gt_index_dev         : np.unique(ids, return_inverse=True) through a direct table int32[id_cap] (id_cap <= 2^20, above
+ *                              it PBN_ERR_UNSUPPORTED): cleared, filled with the vertex count per id, then walked in ascending
+ *                              id order by one workgroup: uid[u_cap], gt_vert[u_cap], n_gt, table[id] = the id's slot;
+ *                              gt_index[i] = table[ids[i]].  An id < 0 or >= id_cap ORs ID_RANGE and its point gets -1; more
+ *                              than u_cap distinct ids OR ID_COUNT, the ids past the capacity get no slot (index -1) and n_gt
+ *                              = u_cap.  ids: int32 or int64 per its flag
+ *   pbn_instance_overlap_dev : pbn_instance_overlap on clusters int32[p_cap, n_pts] for the rows p < min(*n_keep, p_cap)
+ *                              (n_keep NULL = all rows) and the bins g < min(*n_gt, u_cap); inter int32[p_cap, u_cap] with row
+ *                              stride u_cap, cleared over that live rectangle only, the rest left as it is.  LDS histogram for
+ *                              u_cap <= 8192, global atomics above.  p_cap <= 65535; p_cap * u_cap < 2^31
+ *   pbn_ap_record_append     : appends one scene's record to log int32[log_words].  state int32[8] = used | wanted |
+ *                              n_records | overflow | offset of the last record (-1 = not written) | spare, zeroed by the
+ *                              caller before the first scene.  A single thread sizes the record from n_keep and n_gt, always
+ *                              advances `wanted`, and when the record fits and nothing overflowed before advances `used`,
+ *                              writes the header and publishes the offset; otherwise it sets `overflow`, which is sticky.  A
+ *                              striding grid then writes the body.  Record: header[PBN_AP_RECORD_HEADER] = magic | scene_tag |
+ *                              n_keep | n_gt | n_pts | status (*post_status, NULL = 0, ORed with *assoc_status, which is
+ *                              cleared) | record words | 0; then uid[n_gt] | gt_vert[n_gt] | label_id[n_keep] (semantic_id
+ *                              int64 narrowed; a value that does not fit ORs LABEL_RANGE into the record) | conf[n_keep] as
+ *                              float32 bit patterns | inter[n_keep, n_gt] row-major.  n_keep == 0: the header only */
+#define PBN_AP_RECORD_MAGIC 0x41504c47
+#define PBN_AP_RECORD_HEADER 8
+#define PBN_AP_STATUS_ID_RANGE 4          /* bits 1 and 2 are the post-processing's (pbn_post_compact) */
+#define PBN_AP_STATUS_ID_COUNT 8
+#define PBN_AP_STATUS_LABEL_RANGE 16
+#define PBN_AP_STATUS_INSTANCE_CAP 32
+#define PBN_AP_STATUS_SEMANTIC_RANGE 64
+int pbn_gt_encode_dev(const void* sem, int sem_i64, const void* ins, int ins_i64, int n_pts, const int32_t* label_table,
+                      int n_labels, int32_t* first, int n_inst_cap, int32_t* ids, int32_t* status, pbn_stream_t stream);
+int pbn_gt_index_dev(const void* ids, int ids_i64, int n_pts, int32_t* table, int id_cap, int32_t* uid, int32_t* gt_vert,
+                     int u_cap, int32_t* n_gt, int32_t* gt_index, int32_t* status, pbn_stream_t stream);
+int pbn_instance_overlap_dev(const int32_t* clusters, const int32_t* n_keep, int p_cap, int n_pts, const int32_t* gt_index,
+                             const int32_t* n_gt, int u_cap, int32_t* inter, pbn_stream_t stream);
+int pbn_ap_record_append(int32_t* state, int32_t* log, int64_t log_words, int scene_tag, const int32_t* n_keep, int p_cap,
+                         const int32_t* n_gt, int u_cap, int n_pts, const int32_t* post_status, int32_t* assoc_status,
+                         const int32_t* uid, const int32_t* gt_vert, const int64_t* semantic_id, const float* conf,
+                         const int32_t* inter, pbn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * One-call sub-pipelines (csrc/executor.hip): they only sequence the entry points above.
  *
  * pbn_coords_build: everything a MinkUNet needs from one coordinate lineage -- de-duplication, the four coarser

@@ -149,6 +149,11 @@ SIGNATURES = {
     "pbn_post_compact": (c_int, [c_i32p, c_i32p, c_i32p, c_int, c_int, c_f32p, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_i64, c_vp,
                                  c_int, c_vp, c_i32p, c_f32p, c_vp, c_i32p, c_i32p, c_i32p, c_vp]),
     "pbn_instance_overlap": (c_int, [c_i32p, c_int, c_int, c_i32p, c_int, c_i32p, c_vp]),
+    "pbn_gt_encode_dev": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_i32p, c_int, c_i32p, c_int, c_i32p, c_i32p, c_vp]),
+    "pbn_gt_index_dev": (c_int, [c_vp, c_int, c_int, c_i32p, c_int, c_i32p, c_i32p, c_int, c_i32p, c_i32p, c_i32p, c_vp]),
+    "pbn_instance_overlap_dev": (c_int, [c_i32p, c_i32p, c_int, c_int, c_i32p, c_i32p, c_int, c_i32p, c_vp]),
+    "pbn_ap_record_append": (c_int, [c_i32p, c_i32p, c_i64, c_int, c_i32p, c_int, c_i32p, c_int, c_int, c_i32p, c_i32p, c_i32p,
+                                     c_i32p, c_vp, c_f32p, c_i32p, c_vp]),
     "pbn_rulebook_pair_blocks": (c_int, [c_int]),
     "pbn_bn_workspace_bytes": (c_size, [c_int]),
     "pbn_bn_train_forward": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_f32p, c_f32p, ctypes.c_float, ctypes.c_float, c_f32p,

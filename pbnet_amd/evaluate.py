@@ -11,6 +11,9 @@ What changes against the reference is the data model, not the numbers:
 * a scene's matches are a `SceneMatches` record of flat arrays instead of dicts of dicts of copies;
   `to_reference()` / `from_reference()` convert to and from the reference's layout so either evaluator accepts either.
 * matching is the reference's greedy rule run on arrays; the precision/recall integration is vectorised.
+* `AssociationLog` is the association without a host stop (csrc/apassoc.hip): ids numbered and tables filled on the device, one
+  compact record per scene in an epoch log that `collect()` reads back once and `decode_association_log` turns into the same
+  `SceneMatches`.
 
 Everything here except the overlap table is host bookkeeping on a few hundred integers, as in the reference."""
 import numpy as np
@@ -157,10 +160,16 @@ def assign_instances_for_scan(scene_name, pred_info, gt, device=None):
     inter_all, uid = overlap_table(pred_info["mask"], gt_ids, device)
     label_id = np.asarray(pred_info["label_id"].cpu() if torch.is_tensor(pred_info["label_id"]) else pred_info["label_id"])
     conf = np.asarray(pred_info["conf"].cpu() if torch.is_tensor(pred_info["conf"]) else pred_info["conf"])
+    counts_all = np.bincount(np.searchsorted(uid, np.asarray(gt_ids).astype(np.int64).reshape(-1)), minlength=uid.shape[0])
+    return matches_from_table(scene_name, inter_all, uid, counts_all, label_id, conf)
+
+
+def matches_from_table(scene_name, inter_all, uid, counts_all, label_id, conf):
+    """The host tail of tools/eval.py:205-250 on a scene's integer tables: `inter_all` int[P, U] overlap counts against the
+    ascending unique ids `uid` [U] with their vertex counts `counts_all` [U]; `label_id` / `conf` [P].  Returns a SceneMatches."""
     # ground-truth instances: ids of benchmark classes (getins.py:59-70; 0 = unannotated never qualifies)
     uid_class = np.array([_CLASS_OF_ID.get(int(u // 1000), -1) for u in uid], np.int64)
     g_cols = np.nonzero((uid != 0) & (uid_class >= 0))[0]
-    counts_all = np.bincount(np.searchsorted(uid, np.asarray(gt_ids).astype(np.int64).reshape(-1)), minlength=uid.shape[0])
     void_cols = uid_class < 0                                                     # :217 (id 0 included: 0 // 1000 = 0)
     # predictions: benchmark label and at least MIN_REGION_SIZE vertices (:219-229), numbered in input order
     vert_all = inter_all.sum(1)
@@ -171,6 +180,164 @@ def assign_instances_for_scan(scene_name, pred_info, gt, device=None):
     return SceneMatches(scene_name, uid_class[g_cols], uid[g_cols], counts_all[g_cols].astype(np.int64), pred_class_all[keep],
                         np.arange(keep.shape[0], dtype=np.int64), label_id[keep].astype(np.int64), vert_all[keep],
                         inter_all[keep][:, void_cols].sum(1), conf[keep], inter)
+
+
+# ------------------------------------------------------------------------------- association without a host stop
+# One record per scene in an int32 log (include/pbnet_hip.h, pbn_ap_record_append): header[8] = magic | scene tag | n_keep |
+# n_gt | n_pts | status | record words | 0, then uid[n_gt] | gt_vert[n_gt] | label_id[n_keep] | conf[n_keep] (float32 bits) |
+# inter[n_keep, n_gt]; a scene without clusters is its header alone.
+AP_RECORD_MAGIC, AP_RECORD_HEADER = 0x41504c47, 8
+AP_STATUS = ((1, "a superpoint id is >= n_superpoints"),
+             (2, "a kept proposal has no first member, or its predicted class is outside the label table"),
+             (4, "a ground-truth id is negative or >= id_cap"),
+             (8, "the scene has more than u_cap distinct ground-truth ids"),
+             (16, "a prediction's label id does not fit 32 bits"),
+             (32, "an instance label is >= n_inst_cap"),
+             (64, "a semantic label other than -100 is outside the label table"))
+AP_STATUS_ID_RANGE, AP_STATUS_ID_COUNT, AP_STATUS_LABEL_RANGE, AP_STATUS_INSTANCE_CAP, AP_STATUS_SEMANTIC_RANGE = 4, 8, 16, 32, 64
+
+
+def decode_association_log(words, names):
+    """Walk the records of an association log (int32 words as `AssociationLog` leaves them; `names[tag]` = scene name).
+    Returns ({scene: SceneMatches} in log order, [names of the scenes without a cluster]): a record with n_keep == 0 yields no
+    entry, as train.py:217-219 skips such a scene (tools/eval.py would count its ground-truth instances as misses: run
+    assign_instances_for_scan for those names where that is wanted).  ValueError with the scene's name and the reason for any status bit."""
+    words = np.ascontiguousarray(words, dtype=np.int32).reshape(-1)
+    matches, dropped, pos, end = {}, [], 0, int(words.shape[0])
+    while pos < end:
+        if end - pos < AP_RECORD_HEADER or int(words[pos]) != AP_RECORD_MAGIC:
+            raise ValueError("the association log has no record header at word %d" % pos)
+        tag, n_keep, n_gt, n_pts, status, size = (int(v) for v in words[pos + 1:pos + 7])
+        scene = names[tag] if 0 <= tag < len(names) else "<scene tag %d>" % tag
+        want = AP_RECORD_HEADER + (2 * n_gt + 2 * n_keep + n_keep * n_gt if n_keep else 0)
+        if n_keep < 0 or n_gt < 0 or size != want or pos + size > end:
+            raise ValueError("%s: the record at word %d is malformed (n_keep %d, n_gt %d, %d words, %d left)"
+                             % (scene, pos, n_keep, n_gt, size, end - pos))
+        reasons = [text for bit, text in AP_STATUS if status & bit]
+        if status & ~sum(bit for bit, _ in AP_STATUS):
+            reasons.append("unknown status bits 0x%x" % status)
+        if reasons:
+            raise ValueError("%s: %s" % (scene, "; ".join(reasons)))
+        if n_keep == 0:
+            dropped.append(scene)
+        else:
+            body = words[pos + AP_RECORD_HEADER:pos + size]
+            uid, vert = body[:n_gt].astype(np.int64), body[n_gt:2 * n_gt].astype(np.int64)
+            label_id = body[2 * n_gt:2 * n_gt + n_keep].astype(np.int64)
+            conf = body[2 * n_gt + n_keep:2 * n_gt + 2 * n_keep].copy().view(np.float32)
+            inter_all = body[2 * n_gt + 2 * n_keep:].astype(np.int64).reshape(n_keep, n_gt)
+            matches[scene] = matches_from_table(scene, inter_all, uid, vert, label_id, conf)
+        pos += size
+    return matches, dropped
+
+
+class AssociationLog(object):
+    """The association of an epoch's scenes on the device: `append` enqueues ground-truth numbering (pbn_gt_index_dev), the
+    overlap table of capacity-shaped clusters (pbn_instance_overlap_dev) and one record into the epoch log
+    (pbn_ap_record_append); `collect` is the single read-back.  Neither `append` nor `append_refined` synchronises, and neither
+    allocates once the buffers fit (given int32 clusters, float32 scores and int64 label ids, all contiguous): the work buffers
+    grow only, as postprocess.PostWorkspace; the log and its state never move.  One log per stream.
+
+    Capacities: `p_cap` prediction rows and `n_pts_cap` points (both grow on demand), `u_cap` distinct ground-truth ids per
+    scene, `id_cap` the bound on an id (ScanNet: NYU40 * 1000 + instance + 1 < 41 000; at most 2^20), `n_inst_cap` the bound on
+    an instance label of a (sem, ins) pair (default u_cap), `log_words` the int32 words of the epoch log."""
+
+    def __init__(self, p_cap, n_pts_cap, u_cap=1024, id_cap=65536, log_words=4 << 20, device=None, n_inst_cap=None):
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.u_cap, self.id_cap, self.log_words = int(u_cap), int(id_cap), int(log_words)
+        self.n_inst_cap = self.u_cap if n_inst_cap is None else int(n_inst_cap)
+        if self.u_cap < 1 or self.n_inst_cap < 1 or self.log_words < 0 or not 1 <= self.id_cap <= (1 << 20):
+            raise ValueError("u_cap and n_inst_cap must be positive, log_words >= 0 and id_cap in [1, 2^20]; got %d, %d, %d, %d"
+                             % (self.u_cap, self.n_inst_cap, self.log_words, self.id_cap))
+        i32 = lambda n: torch.zeros(max(int(n), 1), dtype=torch.int32, device=self.device)            # noqa: E731
+        self.state, self.log = i32(8), i32(self.log_words)
+        self.scalars = i32(2)                                         # n_gt | association status
+        self.table, self.first = i32(self.id_cap), i32(self.n_inst_cap)
+        self.uid, self.gt_vert = i32(self.u_cap), i32(self.u_cap)
+        self.label_table = torch.tensor(SEMANTIC_LABEL_IDX, dtype=torch.int32, device=self.device)
+        self.p_cap = self.n_pts_cap = 0
+        self.inter = self.gt_index = self.ids = None
+        self._grow(p_cap, n_pts_cap)
+        self.names = []
+
+    def _grow(self, p_cap, n_pts_cap):
+        p, n = max(int(p_cap), self.p_cap, 1), max(int(n_pts_cap), self.n_pts_cap, 1)
+        if p * self.u_cap >= 1 << 31:
+            raise ValueError("p_cap * u_cap must stay below 2^31, got %d * %d" % (p, self.u_cap))
+        if self.inter is None or p > self.p_cap:
+            self.inter = torch.zeros(p * self.u_cap, dtype=torch.int32, device=self.device)
+        if self.gt_index is None or n > self.n_pts_cap:
+            self.gt_index = torch.zeros(n, dtype=torch.int32, device=self.device)
+            self.ids = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.p_cap, self.n_pts_cap = p, n
+
+    def reset(self):
+        """Forget the epoch: one fill, no synchronisation."""
+        self.state.zero_()
+        self.names = []
+
+    @staticmethod
+    def _labels(t, what, n):
+        if not torch.is_tensor(t) or t.dtype not in (torch.int32, torch.int64) or t.dim() != 1 or int(t.shape[0]) != n:
+            raise ValueError("%s must be an int32 or int64 device vector of %d entries" % (what, n))
+        N.require_cuda(t)
+        return t if n == 0 or t.stride(0) == 1 else t.contiguous()
+
+    def append(self, name, clusters, scores, semantic_id, n_keep, status, gt):
+        """Enqueue one scene.  `clusters` int32 [P, N] (non-zero = inside; rows from n_keep on are never read), `scores` f32 [P],
+        `semantic_id` i64 [P], `n_keep` a device int32 scalar or None = all P rows, `status` the post-processing's device status
+        word or None, `gt` a device id vector [N] (int32 / int64) or a (sem, ins) pair of device label vectors [N]."""
+        N.require_cuda(clusters, scores, semantic_id, n_keep, status)
+        if clusters.dim() != 2:
+            raise ValueError("clusters must be [P, N], got %s" % (tuple(clusters.shape),))
+        p, n = int(clusters.shape[0]), int(clusters.shape[1])
+        if int(scores.numel()) != p or int(semantic_id.numel()) != p:
+            raise ValueError("%d cluster rows, %d scores, %d label ids" % (p, scores.numel(), semantic_id.numel()))
+        for t, what in ((n_keep, "n_keep"), (status, "status")):
+            if t is not None and (t.dtype != torch.int32 or t.numel() != 1):
+                raise TypeError("%s must be a device int32 scalar" % what)
+        if p > self.p_cap or n > self.n_pts_cap:
+            self._grow(p, n)
+        clusters = clusters if clusters.dtype == torch.int32 else (clusters != 0).to(torch.int32)
+        clusters = clusters.contiguous()
+        scores = (scores if scores.dtype == torch.float32 else scores.float()).reshape(-1).contiguous()
+        semantic_id = (semantic_id if semantic_id.dtype == torch.int64 else semantic_id.long()).reshape(-1).contiguous()
+        lib, st = N.lib(), N.current_stream()
+        n_gt, assoc = _word_ptr(self.scalars, 0), _word_ptr(self.scalars, 1)
+        if isinstance(gt, (tuple, list)):
+            sem, ins = self._labels(gt[0], "sem", n), self._labels(gt[1], "ins", n)
+            N.check(lib.pbn_gt_encode_dev(N.ptr(sem), int(sem.dtype == torch.int64), N.ptr(ins), int(ins.dtype == torch.int64), n,
+                                          N.ptr(self.label_table), int(self.label_table.numel()), N.ptr(self.first),
+                                          self.n_inst_cap, N.ptr(self.ids), assoc, st), "pbn_gt_encode_dev")
+            ids = self.ids
+        else:
+            ids = self._labels(gt, "gt", n)
+        N.check(lib.pbn_gt_index_dev(N.ptr(ids), int(ids.dtype == torch.int64), n, N.ptr(self.table), self.id_cap, N.ptr(self.uid),
+                                     N.ptr(self.gt_vert), self.u_cap, n_gt, N.ptr(self.gt_index), assoc, st), "pbn_gt_index_dev")
+        N.check(lib.pbn_instance_overlap_dev(N.ptr(clusters), N.ptr(n_keep), p, n, N.ptr(self.gt_index), n_gt, self.u_cap,
+                                             N.ptr(self.inter), st), "pbn_instance_overlap_dev")
+        N.check(lib.pbn_ap_record_append(N.ptr(self.state), N.ptr(self.log), self.log_words, len(self.names), N.ptr(n_keep), p,
+                                         n_gt, self.u_cap, n, N.ptr(status), assoc, N.ptr(self.uid), N.ptr(self.gt_vert),
+                                         N.ptr(semantic_id), N.ptr(scores), N.ptr(self.inter), st), "pbn_ap_record_append")
+        self.names.append(name)
+
+    def append_refined(self, name, refined, gt):
+        """`append` on what postprocess.refine_instances_device left: its capacity-sized views and device scalars."""
+        self.append(name, refined.clusters, refined.scores, refined.semantic_id, refined.n_keep, refined.status, gt)
+
+    def collect(self):
+        """The single read-back of the epoch: the state block, then the used part of the log.  Returns what
+        `decode_association_log` returns; RuntimeError when a record did not fit, with the word count the epoch wanted."""
+        used, wanted, n_records, overflow = self.state[:4].tolist()
+        if overflow:
+            raise RuntimeError("the association log overflowed: %d of %d scenes fit in log_words = %d, the epoch wanted %d words"
+                               % (n_records, len(self.names), self.log_words, wanted))
+        return decode_association_log(self.log[:used].cpu().numpy(), self.names)
+
+
+def _word_ptr(t, i):
+    """Address of element i of a contiguous tensor."""
+    return N.c_vp(t.data_ptr() + i * t.element_size())
 
 
 # ----------------------------------------------------------------------------------------------------------- AP

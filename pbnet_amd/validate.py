@@ -291,16 +291,27 @@ class ValidationEpoch(object):
     `model_fn` is called as model_fn(batch, model, epoch, cfg, task='eval') and may be wrapped by the caller (teacher
     forcing, a DDP module).  `gt`: a val_gt directory (one `<scene>.txt` per scene), a callable scene name -> ids, or None =
     evaluate.encode_gt_ids of the batch's own first-copy labels.  `reduce=True` sums the meters over the ranks and merges the
-    per-scene matches on rank 0 when a process group exists; the reference logs rank 0's shard only (`reduce=False`)."""
+    per-scene matches on rank 0 when a process group exists; the reference logs rank 0's shard only (`reduce=False`).
+
+    `cfg.device_ap` (needs `cfg.device_post`): the tail of a step -- post-processing, AP association, loss averages -- reads
+    nothing back and allocates nothing once its buffers fit.  Each scene appends one record to an `evaluate.AssociationLog`
+    (`ap_log_words` int32 words) and the loss terms go to a `train_epoch.LossMeter`, both gated on the device by n_keep > 0;
+    `finish()` reads the log and the meter once.  One visible difference: the `no cluster` lines (same text, same count) are
+    printed by `finish()`, not by the step that met the scene.  `progress=True` still works but reads n_keep and the meters
+    back every step, which gives up the point of the mode."""
 
     def __init__(self, model, cfg, epoch, model_fn=None, gt=None, logger=None, writer=None, reduce=True, device=None,
-                 progress=False):
+                 progress=False, ap_log_words=4 << 20):
         self.model, self.cfg, self.epoch = model, cfg, int(epoch)
         self.model_fn = _default_model_fn if model_fn is None else model_fn
         self.gt, self.logger, self.writer, self.reduce, self.progress = gt, logger, writer, reduce, progress
         self.cluster = self.epoch > cfg.cluster_epoch
         self.device_post = bool(getattr(cfg, "device_post", False))     # absent = off: postprocess.refine_instances
-        self._post_ws = self._sup_pin = self._sup_dev = None
+        self.device_ap = bool(getattr(cfg, "device_ap", False))         # absent = off: evaluate.assign_instances_for_scan
+        if self.device_ap and not self.device_post:
+            raise ValueError("cfg.device_ap needs cfg.device_post: the association reads what refine_instances_device leaves")
+        self._post_ws, self._staging, self._empty_buf = None, {}, None
+        self._ap_log, self._ap_log_words, self._loss_meter, self._meter_in = None, int(ap_log_words), None, None
         self.semantic = SemanticMeter(cfg.sem_num, -100, device=device)
         self.mask = MaskAccuracyMeter(0.5)
         self.am_dict, self.visual_keys, self.matches = {}, set(), {}
@@ -332,17 +343,27 @@ class ValidationEpoch(object):
         host = torch.cat(parts).tolist() if parts else []
         return host[:len(dev_w)], [int(v) for v in host[len(dev_w):]]
 
-    def _upload_ids(self, ids, dev):
-        """Host superpoint ids -> device int64 through a pinned staging buffer and an asynchronous copy (a copy from pageable
-        memory would hold the host until it is done).  Both buffers grow only; the staging buffer is free again by the next
-        step because every step ends in a read-back."""
+    def _upload_ids(self, ids, dev, slot="sup"):
+        """Host ids -> device int64 through a pinned staging buffer and an asynchronous copy (a copy from pageable memory would
+        hold the host until it is done).  One pair of buffers per `slot` (superpoint ids, ground-truth ids, ...), growing only.
+        A staging buffer is written again only after the copy that last read it: the event recorded behind that copy is waited
+        for first.  Every forward reads something back after the previous step's copies were enqueued, so the wait finds
+        the event done; it is there for a caller whose model_fn does not."""
+        ids = np.ascontiguousarray(ids).reshape(-1)
         n = int(ids.shape[0])
-        if self._sup_pin is None or self._sup_pin.numel() < n or self._sup_dev.device != dev:
-            self._sup_pin = torch.empty(n, dtype=torch.int64).pin_memory()
-            self._sup_dev = torch.empty(n, dtype=torch.int64, device=dev)
-        self._sup_pin[:n].copy_(torch.from_numpy(np.ascontiguousarray(ids).reshape(-1)))
-        self._sup_dev[:n].copy_(self._sup_pin[:n], non_blocking=True)
-        return self._sup_dev[:n]
+        st = self._staging.get(slot)
+        if st is None or st[0].numel() < n or st[1].device != dev:
+            st = self._staging[slot] = [torch.empty(max(n, 1), dtype=torch.int64).pin_memory(),
+                                        torch.empty(max(n, 1), dtype=torch.int64, device=dev), None]
+        pin, out, copied = st
+        if copied is not None:
+            copied.synchronize()
+        pin[:n].copy_(torch.from_numpy(ids))
+        out[:n].copy_(pin[:n], non_blocking=True)
+        if copied is None:
+            copied = st[2] = torch.cuda.Event()
+        copied.record()
+        return out[:n]
 
     def _refine_on_device(self, pred, point_num, sup, meter_dict):
         """cfg.device_post: postprocess.refine_instances_device; n_keep and the status word travel with the loss-meter weights."""
@@ -363,8 +384,69 @@ class ValidationEpoch(object):
             ws = self._post_ws = PostWorkspace(grown[0], grown[1], grown[2], dev)
         res = refine_instances_device(pred["sem"], pred["proposals"], pred["clt_scores"], point_num, sup, self.cfg,
                                       n_superpoints=n_sp, workspace=ws)
+        if self.device_ap:                                       # cfg.device_ap: nothing is read back, _associate_on_device goes on
+            return res, None
         host_w, scalars = self._read_weights([meter_dict[k][1] for k in meter_dict], res.scalars)
         return res.sliced(scalars), host_w
+
+    def _device_gt(self, name, batch, n_fold, sem_dev, dev):
+        """cfg.device_ap: the scene's ground truth as device tensors -- the id vector, or with gt=None the (sem, ins) pair of the
+        first copy that pbn_gt_encode_dev turns into ids.  Host arrays go through the pinned staging path, once per scene."""
+        from . import evaluate
+        if self.gt is None:
+            ins = batch["ins"]
+            if torch.is_tensor(ins) and ins.is_cuda:
+                ins = ins[:n_fold] if ins.dtype in _LABEL_DTYPES else ins[:n_fold].long()
+            else:
+                ins = self._upload_ids((ins.numpy() if torch.is_tensor(ins) else np.asarray(ins))[:n_fold], dev, "ins")
+            sem = sem_dev.reshape(-1)[:n_fold]
+            return (sem if sem.dtype in _LABEL_DTYPES else sem.long()), ins
+        ids = self.gt(name) if callable(self.gt) else os.path.join(self.gt, name + ".txt")
+        if isinstance(ids, (str, bytes)) or hasattr(ids, "__fspath__"):
+            ids = evaluate.load_gt_ids(ids)
+        if torch.is_tensor(ids) and ids.is_cuda:
+            return ids if ids.dtype in _LABEL_DTYPES else ids.long()
+        return self._upload_ids(ids.numpy() if torch.is_tensor(ids) else np.asarray(ids), dev, "gt")
+
+    def _associate_on_device(self, name, refined, gt):
+        """cfg.device_ap: one record of the epoch's association log; the log's work buffers follow the post-processing's."""
+        from . import evaluate
+        ws = self._post_ws
+        if self._ap_log is None:
+            self._ap_log = evaluate.AssociationLog(ws.n_prop, ws.n_fold, log_words=self._ap_log_words, device=ws.device)
+        self._ap_log.append_refined(name, refined, gt)
+
+    def _empty(self, dev):
+        """cfg.device_ap: the bool [1] that holds a step's `n_keep <= 0`, allocated once."""
+        if self._empty_buf is None or self._empty_buf.device != dev:
+            self._empty_buf = torch.zeros(1, dtype=torch.bool, device=dev)
+        return self._empty_buf
+
+    def _meter_on_device(self, meter_dict, empty, dev):
+        """cfg.device_ap: train.py:258-261 on a train_epoch.LossMeter.  `empty` (device bool [1] = `n_keep <= 0`, or None) keeps
+        a scene without clusters out of the averages (train.py:217-219): term and weight both become 0 -- a NaN term times a
+        zero weight would still be NaN.  Terms and weights are staged into two vectors allocated with the meter, so a step
+        allocates nothing; a host number travels as a launch argument, not as a copy."""
+        from .train_epoch import LossMeter
+        keys = list(meter_dict)
+        if self._loss_meter is None:
+            self._loss_meter = LossMeter(keys, device=dev)
+            self._meter_in = (torch.zeros(len(keys), dtype=torch.float32, device=dev),
+                              torch.zeros(len(keys), dtype=torch.float64, device=dev))
+        elif self._loss_meter.names != keys:
+            raise ValueError("the logged terms changed within the epoch: %s, then %s" % (self._loss_meter.names, keys))
+
+        terms, weights = self._meter_in
+        for i, k in enumerate(keys):                            # in place: a device scalar is copied, a host number filled in
+            for buf, v in ((terms, meter_dict[k][0]), (weights, meter_dict[k][1])):
+                if torch.is_tensor(v) and v.is_cuda:
+                    buf[i].copy_(v.detach().reshape(()))
+                else:
+                    buf[i].fill_(float(v))
+        if empty is not None:                                   # torch.where(n_keep > 0, x, 0), in place
+            terms.masked_fill_(empty, 0.0)
+            weights.masked_fill_(empty, 0.0)
+        self._loss_meter.update(terms, weights)
 
     def step(self, batch):
         from . import evaluate
@@ -376,7 +458,7 @@ class ValidationEpoch(object):
         with torch.no_grad():
             loss, pred, visual_dict, meter_dict = self.model_fn(batch, self.model, self.epoch, self.cfg, task="eval")
             self.steps += 1
-            host_w = None
+            host_w = empty = None
             # train.py:144-149
             sem_label = torch.as_tensor(batch["sem"]).to(pred["sem"].device)
             self.semantic.update(pred["sem"], sem_label if sem_label.dtype in _LABEL_DTYPES else sem_label.long())
@@ -386,20 +468,36 @@ class ValidationEpoch(object):
                 # train.py:171-253
                 name = fn[0]
                 point_num = int(batch["xyz_original"].shape[0])
-                if self.device_post:
-                    refined, host_w = self._refine_on_device(pred, point_num, batch["sup"], meter_dict)
-                    clusters, scores, sem_id = refined
+                if self.device_ap:
+                    # the whole tail stays on the device: n_keep == 0 (train.py:217-219) is a header-only record and a closed gate
+                    refined, _ = self._refine_on_device(pred, point_num, batch["sup"], meter_dict)
+                    n_fold = point_num // 3
+                    self._associate_on_device(name, refined, self._device_gt(name, batch, n_fold, sem_label, sem_label.device))
+                    empty = torch.le(refined.n_keep.reshape(1), 0, out=self._empty(sem_label.device))
                 else:
-                    clusters, scores, sem_id = refine_instances(pred["sem"], pred["proposals"], pred["clt_scores"], point_num,
-                                                                batch["sup"], self.cfg)
-                if clusters.shape[0] == 0:
-                    # train.py:217-219: the `continue` sits ABOVE the loss-meter update (:258-261), so a scene without
-                    # clusters is missing from the loss averages too; kept
-                    print("no cluster")
-                    self.no_cluster += 1
-                    return pred
-                self.matches[name] = evaluate.assign_instances_for_scan(
-                    name, dict(conf=scores, label_id=sem_id, mask=clusters), self._gt_ids(name, batch, point_num // 3))
+                    if self.device_post:
+                        refined, host_w = self._refine_on_device(pred, point_num, batch["sup"], meter_dict)
+                        clusters, scores, sem_id = refined
+                    else:
+                        clusters, scores, sem_id = refine_instances(pred["sem"], pred["proposals"], pred["clt_scores"],
+                                                                    point_num, batch["sup"], self.cfg)
+                    if clusters.shape[0] == 0:
+                        # train.py:217-219: the `continue` sits ABOVE the loss-meter update (:258-261), so a scene without
+                        # clusters is missing from the loss averages too; kept
+                        print("no cluster")
+                        self.no_cluster += 1
+                        return pred
+                    self.matches[name] = evaluate.assign_instances_for_scan(
+                        name, dict(conf=scores, label_id=sem_id, mask=clusters), self._gt_ids(name, batch, point_num // 3))
+            self.visual_keys.update(visual_dict)
+            if self.device_ap:
+                self._meter_on_device(meter_dict, empty, pred["sem"].device)
+                # two read-backs per step are the price of the line; as in the host form, a scene without clusters logs none
+                if self.progress and not (empty is not None and bool(empty)):
+                    val, avg = self._loss_meter.read()["loss"]
+                    self._info("iter: {} loss: {:.4f}({:.4f}) Accuracy {accuracy:.4f} ".format(
+                        self.steps, val, avg, accuracy=self.semantic.accuracy_val()))
+                return pred
             # train.py:258-261 on Python floats; the weights are device scalars: one read-back for all of them
             keys = list(meter_dict)
             weights = [meter_dict[k][1] for k in keys]
@@ -409,7 +507,6 @@ class ValidationEpoch(object):
             for k, w in zip(keys, weights):
                 v = meter_dict[k][0]
                 self.am_dict.setdefault(k, AverageMeter()).update(float(v), next(host_w) if torch.is_tensor(w) else float(w))
-            self.visual_keys.update(visual_dict)
             if self.progress:
                 self._info("iter: {} loss: {:.4f}({:.4f}) Accuracy {accuracy:.4f} ".format(
                     self.steps, self.am_dict["loss"].val, self.am_dict["loss"].avg, accuracy=self.semantic.accuracy_val()))
@@ -421,6 +518,19 @@ class ValidationEpoch(object):
         from . import dist as pdist, evaluate
         world = tdist.get_world_size() if (tdist.is_available() and tdist.is_initialized()) else 1
         rank = tdist.get_rank() if world > 1 else 0
+        if self.device_ap:
+            # the epoch's two read-backs: the association log (records in step order) and the loss meter
+            if self._ap_log is not None:
+                self.matches, dropped = self._ap_log.collect()
+                self.no_cluster = len(dropped)
+                for _ in dropped:
+                    print("no cluster")
+            self.am_dict = {}
+            if self._loss_meter is not None and self.steps > self.no_cluster:      # no counted scene: no meter, as the host form
+                _, total, count = self._loss_meter.raw().tolist()
+                for k, s, c in zip(self._loss_meter.names, total, count):
+                    meter = self.am_dict[k] = AverageMeter()
+                    meter.sum, meter.count = s, c
         matches, am = self.matches, {k: (m.sum, m.count) for k, m in self.am_dict.items()}
         if world > 1 and self.reduce:
             self.semantic.all_reduce()
