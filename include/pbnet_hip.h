@@ -31,6 +31,10 @@ enum {
 /* element types of feature slabs */
 enum { PBN_F32 = 0, PBN_BF16 = 1, PBN_F16 = 2 };
 
+/* Scenes (batch elements) of one merged forward: the bound of pbn_sem_argmax_table's population table, of pbn_scene_table
+ * and of pbnet_amd/serving.py's max_batch. */
+#define PBN_MAX_SCENES 8
+
 const char* pbn_version(void);
 /* hipError_t of the last failing HIP call on this thread, as int (0 = none). */
 int pbn_last_hip_error(void);
@@ -530,6 +534,47 @@ int pbn_post_compact(const int32_t* counts2, const int32_t* pick_rows, const int
                      int offset_i64, const void* pred_sem, int sem_i64, int64_t n_sem, const int64_t* label_table, int n_labels,
                      const uint32_t* masks2, int32_t* keep, float* scores_out, int64_t* semantic_id_out, int32_t* clusters,
                      int32_t* n_keep, int32_t* status, pbn_stream_t stream);
+
+/* The batched, segmented form (csrc/post_batch.hip): the post-processing of ONE merged forward over all its scenes, without
+ * the TTA fold and without a dense [P, n] table.  Every proposal of a merged forward lies in one scene (PBNet.py:167-176); the
+ * scene of a proposal is the scene of its first member.  The scene table is host data known at merge time and travels by value:
+ *   n_scenes B in [1, PBN_MAX_SCENES]; point_start[0] = 0 <= ... <= point_start[B] = n_points_total (scene j owns the points
+ *   point_start[j] .. point_start[j + 1] of the merged arrays); sp_start likewise over the flat vote table: scene j's superpoint
+ *   capacity is sp_start[j + 1] - sp_start[j], 0 = the scene brings no superpoints and is refined as if every point were its own
+ *   (the vote is skipped).  `superpoint` int64[n_points_total] holds scene-LOCAL ids and is never read on the rows of a scene
+ *   without superpoints (NULL when no scene has any).
+ * Per scene the steps are those of pbn_post_select .. pbn_post_compact with the same tie rule (score descending, lower position in
+ * the scene's own ascending survivor list first); bitsets are over point - point_start[scene] with a row pitch of
+ * pbn_post_words(largest scene).  clt_score has element type score_dtype (PBN_F32 / PBN_BF16 / PBN_F16) and is compared in fp32.
+ * Outputs (B = n_scenes, P = n_prop):
+ *   point_instance int32[n_points_total] : scene-local number of the kept instance that owns the point, or -100
+ *   scores f32[B, P], semantic_id int64[B, P], npoints int32[B, P] : scene j's kept instances in pick order in the first n_keep[j]
+ *                                          entries of row j; tails 0 / -1 / 0
+ *   scalars int32[2 * B]                 : n_keep[B], then status[B] (bit 1: a superpoint id >= the scene's capacity -- the id
+ *                                          takes no part and writes nothing; bit 2: a kept proposal's class is outside the label
+ *                                          table), per scene
+ * pbn_post_batch_workspace_bytes sizes the workspace for (P, n_points_total, B, sp_start[B]) and, when layout is not NULL, reports
+ * where the tables lie in it (byte offsets; votes int32[sp_total, P + 1], rows / pick_rows / counts2 / renumber int32[B, P],
+ * n_rows / n_pick int32[PBN_MAX_SCENES], seg / seg_refined int32[n_points_total], masks uint32[P, words(n_points_total)], iou
+ * f32[P, P]: scene j's block starts at row sum(n_rows[:j]), row stride P).  0 for sizes outside the supported range.
+ * pbn_post_batch: thirteen launches, no read-back, no allocation, no launch argument computed from device data.  n_prop = 0 is
+ * served (every point -100, n_keep and status 0).  PBN_ERR_UNSUPPORTED above pbn_post_max_proposals() proposals, PBN_ERR_ARG for
+ * a scene table that is not as stated, PBN_ERR_WORKSPACE for a workspace that is too small -- all before any launch. */
+typedef struct pbn_scene_table {
+    int32_t n_scenes;
+    int32_t point_start[PBN_MAX_SCENES + 1];
+    int32_t sp_start[PBN_MAX_SCENES + 1];
+} pbn_scene_table;
+typedef struct pbn_post_batch_layout {
+    int64_t masks, counts, prop_scene, score, rows, pick_rows, n_rows, n_pick, iou, votes, sp_label, seg, seg_refined, counts2,
+        renumber, total_bytes;
+} pbn_post_batch_layout;
+size_t pbn_post_batch_workspace_bytes(int n_prop, int n_points_total, int n_scenes, int n_sp_total, pbn_post_batch_layout* layout);
+int pbn_post_batch(const int64_t* proposals_idx, int n_entries, const void* proposals_offset, int offset_i64, int n_prop,
+                   const void* clt_score, int score_dtype, const void* pred_sem, int sem_i64, int n_points_total,
+                   pbn_scene_table scenes, const int64_t* superpoint, float score_t, int npoint_t, float nms_t,
+                   const int64_t* label_table, int n_labels, int32_t* point_instance, float* scores, int64_t* semantic_id,
+                   int32_t* npoints, int32_t* scalars, void* workspace, size_t workspace_bytes, pbn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * ScanNet AP evaluator, the association step of /root/reference/tools/eval.py:205-250

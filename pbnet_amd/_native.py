@@ -89,6 +89,20 @@ class PairLists(ctypes.Structure):
                 ("counts", ctypes.c_void_p), ("segment", c_i32), ("n_pairs_estimate", c_i32)]
 
 
+MAX_SCENES = 8                        # PBN_MAX_SCENES (include/pbnet_hip.h): scenes of one merged forward
+
+
+class SceneTable(ctypes.Structure):
+    """pbn_scene_table (include/pbnet_hip.h)."""
+    _fields_ = [("n_scenes", c_i32), ("point_start", c_i32 * (MAX_SCENES + 1)), ("sp_start", c_i32 * (MAX_SCENES + 1))]
+
+
+class PostBatchLayout(ctypes.Structure):
+    """pbn_post_batch_layout (include/pbnet_hip.h)."""
+    _fields_ = [(k, c_i64) for k in ("masks", "counts", "prop_scene", "score", "rows", "pick_rows", "n_rows", "n_pick", "iou",
+                                     "votes", "sp_label", "seg", "seg_refined", "counts2", "renumber", "total_bytes")]
+
+
 # name -> (restype, argtypes); must list every symbol of include/pbnet_hip.h (tests/test_abi.py checks this)
 SIGNATURES = {
     "pbn_version": (ctypes.c_char_p, []),
@@ -148,6 +162,9 @@ SIGNATURES = {
                                           c_i32p, c_vp]),
     "pbn_post_compact": (c_int, [c_i32p, c_i32p, c_i32p, c_int, c_int, c_f32p, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_i64, c_vp,
                                  c_int, c_vp, c_i32p, c_f32p, c_vp, c_i32p, c_i32p, c_i32p, c_vp]),
+    "pbn_post_batch_workspace_bytes": (c_size, [c_int, c_int, c_int, c_int, ctypes.POINTER(PostBatchLayout)]),
+    "pbn_post_batch": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_int, c_int, SceneTable, c_vp, c_float, c_int,
+                               c_float, c_vp, c_int, c_i32p, c_f32p, c_vp, c_i32p, c_i32p, c_vp, c_size, c_vp]),
     "pbn_instance_overlap": (c_int, [c_i32p, c_int, c_int, c_i32p, c_int, c_i32p, c_vp]),
     "pbn_gt_encode_dev": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_i32p, c_int, c_i32p, c_int, c_i32p, c_i32p, c_vp]),
     "pbn_gt_index_dev": (c_int, [c_vp, c_int, c_int, c_i32p, c_int, c_i32p, c_i32p, c_int, c_i32p, c_i32p, c_i32p, c_vp]),

@@ -7,11 +7,12 @@
 // stays on the host, exactly as the reference runs it; the device-resident form further down (pbn_post_select ..
 // pbn_post_compact) runs it in one workgroup and keeps every count in a device scalar.
 #include "pbn_common.h"
+#include "post_dev.h"
 
 namespace pbn {
 namespace {
 
-constexpr int TPB = 256;
+constexpr int TPB = POST_TPB;
 
 // bit (point % n_fold) of row proposal: eval_map.py:67-70 (the three rotated copies fold onto one index range)
 __global__ __launch_bounds__(TPB) void k_set_bits(const long long* __restrict__ proposals_idx, int n_entries, int n_fold,
@@ -110,27 +111,6 @@ __global__ __launch_bounds__(TPB) void k_bits_to_dense(const unsigned* __restric
 // ---- the device-resident form (pbn_post_select .. pbn_post_compact) ------------------------------------------------------
 // The same arithmetic with every count (n_rows, n_pick, n_keep) kept in device scalars: grids are sized by the capacity P and
 // work items past the live count leave, so nothing between the first and the last launch waits for the host.
-
-constexpr int POST_MAX_PROPOSALS = 4096;        // k_post_nms keeps score, order and suppress flags of every survivor in LDS
-constexpr int POST_STATUS_SUPERPOINT = 1;       // a superpoint id >= n_sp_cap
-constexpr int POST_STATUS_CLASS = 2;            // a proposal without a first member, or a class outside the label table
-
-// exclusive position of `flag` among the 256 threads of the block, in thread order; *total = flags set.  s_wave: 4 ints.
-__device__ __forceinline__ int block_flag_scan(bool flag, int* s_wave, int* total) {
-    const unsigned long long b = __ballot(flag);
-    const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
-    __syncthreads();                               // the previous round's readers are done with s_wave
-    if (lane == 0) s_wave[wave] = __popcll(b);
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < TPB / 64; ++w) {
-        before += w < wave ? s_wave[w] : 0;
-        all += s_wave[w];
-    }
-    *total = all;
-    return before + __popcll(b & ((1ull << lane) - 1ull));
-}
 
 // rows = ascending proposals with score > score_t (fp32) and count > npoint_t (eval_map.py:74-84); the tail of rows is -1.
 // The first launch of a call: it also clears the status word.

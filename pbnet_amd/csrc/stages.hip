@@ -288,7 +288,7 @@ __global__ __launch_bounds__(TPB) void k_sem_argmax_table(const T* __restrict__ 
                                                          const int* __restrict__ batch, int nb, int n,
                                                          long long* __restrict__ sem_pred, T* __restrict__ sem_prob,
                                                          int* __restrict__ table, int* __restrict__ block_hist) {
-    __shared__ int s_tab[SEL_MAX_CLASSES * 8];
+    __shared__ int s_tab[SEL_MAX_CLASSES * PBN_MAX_SCENES];
     __shared__ int s_cls[SEL_MAX_CLASSES];
     for (int e = threadIdx.x; e < n_cls * nb; e += TPB) s_tab[e] = 0;
     if (threadIdx.x < n_cls) s_cls[threadIdx.x] = 0;
@@ -728,7 +728,7 @@ extern "C" int pbn_sem_argmax_table(const void* score, int ld, int n_cls, const 
                                     int64_t* sem_pred, void* sem_prob, int32_t* table, int32_t* block_hist,
                                     pbn_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (n < 0 || n_cls < 1 || n_cls > SEL_MAX_CLASSES || nb < 1 || nb > 8 || ld < n_cls || !table) return PBN_ERR_ARG;
+    if (n < 0 || n_cls < 1 || n_cls > SEL_MAX_CLASSES || nb < 1 || nb > PBN_MAX_SCENES || ld < n_cls || !table) return PBN_ERR_ARG;
     { const int frc_ = fill_bytes(table, 0, sizeof(int) * (size_t)n_cls * nb, stream); if (frc_ != PBN_OK) return frc_; }
     if (n == 0) return PBN_OK;
     if (!score || !sem_pred || !block_hist) return PBN_ERR_ARG;

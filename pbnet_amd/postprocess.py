@@ -8,7 +8,10 @@ points of the 3-copy batch and the scene's superpoint ids) and returns what it h
 
 `refine_instances_device` is the same step without the five host stops of `refine_instances` (the threshold read-back, the IoU
 read-back, `sp.max().item()`, the vanished-cluster read-back and the index uploads): every count stays in a device scalar until
-the caller asks for `.sliced()`."""
+the caller asks for `.sliced()`.
+
+`refine_batch_device` is the device-resident form for ALL scenes of one merged forward (pbnet_amd/serving.py), without the TTA
+fold: one pass with a scene axis (csrc/post_batch.hip), the masks as one label per point, one read-back of n_keep[B] / status[B]."""
 import numpy as np
 import torch
 
@@ -230,3 +233,185 @@ def refine_instances_device(pred_sem, proposals, clt_scores, point_num, superpoi
 def _elem_ptr(t, i):
     """Address of element i of a contiguous tensor."""
     return N.c_vp(t.data_ptr() + i * t.element_size())
+
+
+# ---- the batched form: all scenes of one merged forward (csrc/post_batch.hip) ------------------------------------------------
+MAX_SCENES = N.MAX_SCENES
+
+
+def scene_table(point_starts, sp_starts):
+    """The by-value launch argument of pbn_post_batch from two host lists of B + 1 ascending starts (host data, no tensor)."""
+    b = len(point_starts) - 1
+    if not 1 <= b <= MAX_SCENES or len(sp_starts) != b + 1:
+        raise ValueError("a merged forward holds 1..%d scenes, got %d (and %d superpoint starts)" % (MAX_SCENES, b, len(sp_starts)))
+    t = N.SceneTable()
+    t.n_scenes = b
+    for j in range(b + 1):
+        t.point_start[j], t.sp_start[j] = int(point_starts[j]), int(sp_starts[j])
+    return t
+
+
+class PostBatchWorkspace(object):
+    """Every buffer `refine_batch_device` touches, outputs included, sized from capacities: proposals of the merged forward,
+    its points, its scenes and the sum of the scenes' superpoint capacities.  A call that fits allocates nothing; its results
+    ALIAS these buffers, so the next call on the same workspace overwrites them.  One workspace per stream."""
+
+    def __init__(self, n_prop, n_points_total, n_scenes, n_superpoints_total, device):
+        p, n, b, s = max(int(n_prop), 1), max(int(n_points_total), 1), int(n_scenes), max(int(n_superpoints_total), 0)
+        lib = N.lib()
+        if p > lib.pbn_post_max_proposals():
+            raise ValueError("the device form takes at most %d proposals, got %d" % (lib.pbn_post_max_proposals(), p))
+        if not 1 <= b <= MAX_SCENES:
+            raise ValueError("a merged forward holds 1..%d scenes, got %d" % (MAX_SCENES, b))
+        self.n_prop, self.n_points_total, self.n_scenes, self.n_superpoints_total = p, n, b, s
+        self.device = torch.device(device)
+        self.nbytes = int(lib.pbn_post_batch_workspace_bytes(p, n, b, s, None))
+        mk = lambda k, dt: torch.zeros(k, dtype=dt, device=self.device)
+        self.buffer = mk(self.nbytes, torch.uint8)
+        self.point_instance, self.superpoint = mk(n, torch.int32), mk(n, torch.int64)
+        self.scores, self.semantic_id, self.npoints = mk(b * p, torch.float32), mk(b * p, torch.int64), mk(b * p, torch.int32)
+        self.scalars = mk(2 * MAX_SCENES, torch.int32)
+        self.label_table = torch.tensor(SEMANTIC_LABEL_IDX, dtype=torch.int64, device=self.device)
+
+    def fits(self, n_prop, n_points_total, n_scenes, n_superpoints_total):
+        return (n_prop <= self.n_prop and n_points_total <= self.n_points_total and n_scenes <= self.n_scenes
+                and n_superpoints_total <= self.n_superpoints_total)
+
+    def grown_for(self, n_prop, n_points_total, n_scenes, n_superpoints_total):
+        """A workspace that fits both this one's capacities and the given sizes (this one when it already does)."""
+        if self.fits(n_prop, n_points_total, n_scenes, n_superpoints_total):
+            return self
+        return PostBatchWorkspace(max(n_prop, self.n_prop), max(n_points_total, self.n_points_total), max(n_scenes, self.n_scenes),
+                                  max(n_superpoints_total, self.n_superpoints_total), self.device)
+
+
+class RefinedBatch(object):
+    """What `refine_batch_device` leaves on the device for the B scenes of a merged forward with P proposals:
+    point_instance i32[N_total] (scene-local kept-instance number or -100), scores f32[B, P], semantic_id i64[B, P],
+    npoints i32[B, P] (row j: scene j's kept instances in pick order, then 0 / -1 / 0), scalars i32[2 B] = n_keep[B], status[B].
+    Nothing has been read back; `scene` / `dense` synchronise only when the caller does not hand the scalars in."""
+
+    def __init__(self, ws, n_prop, point_starts, sp_starts):
+        self.workspace, self.n_prop, self.point_starts, self.sp_starts = ws, n_prop, list(point_starts), list(sp_starts)
+        self.n_scenes = b = len(point_starts) - 1
+        n = self.point_starts[-1]
+        self.point_instance = ws.point_instance[:n]
+        self.scores, self.semantic_id, self.npoints = (t[:b * n_prop].view(b, n_prop) for t in (ws.scores, ws.semantic_id, ws.npoints))
+        self.scalars = ws.scalars[:2 * b]
+
+    def table(self, name):
+        """Debug view of one internal table of the last call (names and shapes: pbn_post_batch_layout); float32 for `iou`."""
+        lay = N.PostBatchLayout()
+        N.lib().pbn_post_batch_workspace_bytes(max(self.n_prop, 1), self.point_starts[-1], self.n_scenes, self.sp_starts[-1], lay)
+        names = [f[0] for f in N.PostBatchLayout._fields_]
+        lo, hi = getattr(lay, name), getattr(lay, names[names.index(name) + 1])
+        return self.workspace.buffer[lo:hi].view(torch.float32 if name == "iou" else torch.int32)
+
+    def _counts(self, j, scalars):
+        sc = [int(v) for v in (self.scalars.tolist() if scalars is None else scalars)]
+        n_keep, status = sc[j], sc[self.n_scenes + j]
+        if status & STATUS_SUPERPOINT_RANGE:
+            raise ValueError("scene %d: a superpoint id is >= the scene's n_superpoints" % j)
+        if status & STATUS_CLASS_RANGE:
+            raise ValueError("scene %d: a kept proposal's predicted class is outside the label table" % j)
+        return n_keep
+
+    def scene(self, j, scalars=None):
+        """Scene j's instances: dict(point_instance i32[n_j], scores [k_j], semantic_id i64[k_j], npoints i32[k_j]).  ValueError
+        when scene j's status word is set.  `scalars`: the 2 B integers of `.scalars` if the caller has read them back already."""
+        k = self._counts(j, scalars)
+        return dict(point_instance=self.point_instance[self.point_starts[j]:self.point_starts[j + 1]], scores=self.scores[j, :k],
+                    semantic_id=self.semantic_id[j, :k], npoints=self.npoints[j, :k])
+
+    def dense(self, j, scalars=None):
+        """The reference's cluster table of scene j, int32[k_j, n_j], materialised on request."""
+        k = self._counts(j, scalars)
+        pi = self.point_instance[self.point_starts[j]:self.point_starts[j + 1]]
+        return (pi[None, :] == torch.arange(k, dtype=torch.int32, device=pi.device)[:, None]).to(torch.int32)
+
+
+def refine_merged_device(sem_pred_p, proposals, clt_scores, point_starts, sp_starts, superpoint, cfg, workspace=None):
+    """`refine_batch_device` on ids that are already merged: `superpoint` int64[N_total] (scene-local ids; rows of scenes with
+    sp_starts[j + 1] == sp_starts[j] are never read; None when no scene has superpoints)."""
+    proposals_idx, proposals_offset = proposals[0], proposals[1]
+    N.require_cuda(proposals_idx, proposals_offset, sem_pred_p, clt_scores, superpoint)
+    if proposals_idx.dtype != torch.int64:
+        raise TypeError("proposals_idx must be int64, got %s" % proposals_idx.dtype)
+    for name, t in (("proposals_offset", proposals_offset), ("sem_pred_p", sem_pred_p)):
+        if t.dtype not in (torch.int32, torch.int64):
+            raise TypeError("%s must be int32 or int64, got %s" % (name, t.dtype))
+    if clt_scores.dtype not in N.DT:
+        raise TypeError("clt_scores must be float32, bfloat16 or float16, got %s" % clt_scores.dtype)
+    table = scene_table(point_starts, sp_starts)
+    b, n_total, n_sp_total = table.n_scenes, int(point_starts[-1]), int(sp_starts[-1])
+    if int(sem_pred_p.numel()) != n_total:
+        raise ValueError("sem_pred_p holds %d points, the scene table %d" % (sem_pred_p.numel(), n_total))
+    if n_sp_total > 0:
+        if superpoint is None or superpoint.dtype != torch.int64 or int(superpoint.numel()) < n_total:
+            raise ValueError("superpoint must be an int64 device tensor of %d ids" % n_total)
+    n_prop = max(int(proposals_offset.shape[0]) - 1, 0)
+    lib = N.lib()
+    if n_prop > lib.pbn_post_max_proposals():
+        raise ValueError("the device form takes at most %d proposals, got %d" % (lib.pbn_post_max_proposals(), n_prop))
+    ws = workspace
+    if ws is None:
+        ws = PostBatchWorkspace(n_prop, n_total, b, n_sp_total, proposals_idx.device)
+    elif not ws.fits(n_prop, n_total, b, n_sp_total):
+        raise ValueError("workspace (%d, %d, %d, %d) does not fit (%d, %d, %d, %d)" % (
+            ws.n_prop, ws.n_points_total, ws.n_scenes, ws.n_superpoints_total, n_prop, n_total, b, n_sp_total))
+    res = RefinedBatch(ws, n_prop, point_starts, sp_starts)
+    pidx, off, sem, clt = proposals_idx.contiguous(), proposals_offset.contiguous(), sem_pred_p.contiguous(), clt_scores.contiguous()
+    sp = None if n_sp_total == 0 else superpoint.contiguous()
+    N.check(lib.pbn_post_batch(N.ptr(pidx), int(pidx.shape[0]), N.ptr(off), int(off.dtype == torch.int64), n_prop, N.ptr(clt),
+                               N.DT[clt.dtype], N.ptr(sem), int(sem.dtype == torch.int64), n_total, table, N.ptr(sp),
+                               float(cfg.TEST_SCORE_THRESH), int(cfg.TEST_NPOINT_THRESH), float(cfg.TEST_NMS_THRESH),
+                               N.ptr(ws.label_table), int(ws.label_table.numel()), N.ptr(ws.point_instance), N.ptr(ws.scores),
+                               N.ptr(ws.semantic_id), N.ptr(ws.npoints), N.ptr(ws.scalars), N.ptr(ws.buffer), ws.nbytes,
+                               N.current_stream()), "pbn_post_batch")
+    return res
+
+
+def superpoint_starts(point_starts, has_superpoints, n_superpoints=None):
+    """sp_start of the scene table: scene j's vote slice holds n_superpoints[j] rows (default: its point count), 0 without ids."""
+    starts = [0]
+    for j, has in enumerate(has_superpoints):
+        cap = 0
+        if has:
+            cap = int(point_starts[j + 1] - point_starts[j]) if n_superpoints is None or n_superpoints[j] is None else int(n_superpoints[j])
+            if cap < 1:
+                raise ValueError("scene %d: n_superpoints must be positive, got %d" % (j, cap))
+        starts.append(starts[-1] + cap)
+    return starts
+
+
+def refine_batch_device(sem_pred_p, proposals, clt_scores, point_starts, superpoints, cfg, n_superpoints=None, workspace=None):
+    """The post-processing of eval_map.py:55-123 for every scene of ONE merged forward (pbnet_amd/serving.py), without the TTA
+    fold: thirteen launches for all scenes, every count in a device scalar, no host stop.  Returns a `RefinedBatch`.
+
+    sem_pred_p [N_total], proposals (idx int64[M, 2], offset [P + 1]) and clt_scores [P] are the merged forward's own results;
+    point_starts: the B + 1 host integers `merge_scenes` returns.  `superpoints`: B entries, each an int64 device tensor of the
+    scene's ids or None (that scene is refined as if every point were its own superpoint; the vote is skipped).  `n_superpoints`:
+    per-scene upper bounds of the ids (default: the scene's point count); an id at or above its scene's bound sets that scene's
+    status and `.scene(j)` raises for that scene alone.  Same tie rule and limits as `refine_instances_device`."""
+    b = len(point_starts) - 1
+    superpoints = [None] * b if superpoints is None else list(superpoints)
+    if len(superpoints) != b:
+        raise ValueError("%d superpoint entries for %d scenes" % (len(superpoints), b))
+    sp_starts = superpoint_starts(point_starts, [s is not None for s in superpoints], n_superpoints)
+    n_total, n_prop = int(point_starts[-1]), max(int(proposals[1].shape[0]) - 1, 0)
+    ws = workspace
+    if ws is None:
+        ws = PostBatchWorkspace(n_prop, n_total, b, sp_starts[-1], proposals[0].device)
+    merged = None
+    if sp_starts[-1] > 0:
+        if n_total > ws.n_points_total:
+            raise ValueError("workspace holds %d points, the batch %d" % (ws.n_points_total, n_total))
+        merged = ws.superpoint
+        for j, s in enumerate(superpoints):
+            if s is None:
+                continue
+            N.require_cuda(s)
+            if s.dtype != torch.int64 or int(s.numel()) != point_starts[j + 1] - point_starts[j]:
+                raise ValueError("scene %d: superpoints must be %d int64 ids" % (j, point_starts[j + 1] - point_starts[j]))
+            merged[point_starts[j]:point_starts[j + 1]].copy_(s.view(-1))
+    return refine_merged_device(sem_pred_p, proposals, clt_scores, point_starts, sp_starts, merged, cfg, workspace=ws)

@@ -13,6 +13,11 @@ the property this module rests on: a merged forward returns, for every scene, th
     res = fut.result()                   # dict(sem_pred_p [N], proposals (idx [M,2], offset [P+1]), clt_scores [P]) of THAT scene
     server.close()
 
+With `SceneServer(..., refine=cfg)` a scene's result is what `eval_map.py` ends with instead of proposals: the merged forward's
+post-processing runs once for all its scenes (`postprocess.refine_batch_device`, csrc/post_batch.hip) in place of `split_results`,
+and `res["instances"]` is dict(point_instance [N], scores [K], semantic_id [K], npoints [K]).  A scene may then carry `sup`
+(int64 device superpoint ids) and `n_superpoints` (their upper bound).
+
 `merge_scenes` / `split_results` are the two pure functions; `SceneServer` is the small scheduler around them: F worker threads,
 each with its own HIP stream (create the server FIRST in a process: the runtime maps a process's first streams to distinct
 hardware queues), each taking up to `max_batch` waiting scenes per forward -- it never waits for a batch to fill:
@@ -24,11 +29,39 @@ from concurrent.futures import Future
 
 import torch
 
+from . import postprocess
+from ._native import MAX_SCENES
 
-def merge_scenes(scenes, teachers=None):
+
+def merge_superpoints(scenes, point_starts):
+    """The superpoint side of a merged batch: (ids int64 [N_total] or None, sp_starts [B + 1]).  Scene j's ids stay scene-local
+    and vote in rows sp_starts[j] : sp_starts[j + 1] of one flat table; a scene without `sup` gets an empty slice (and zeros in
+    the merged ids, which are never read).  Host arithmetic and one concatenation; None when no scene brings ids."""
+    has = [s.get("sup") is not None for s in scenes]
+    sp_starts = postprocess.superpoint_starts(point_starts, has, [s.get("n_superpoints") for s in scenes])
+    if not any(has):
+        return None, sp_starts
+    parts = []
+    for j, s in enumerate(scenes):
+        n = point_starts[j + 1] - point_starts[j]
+        if has[j]:
+            if s["sup"].dtype != torch.int64 or int(s["sup"].numel()) != n:
+                raise ValueError("scene %d: `sup` must hold %d int64 ids" % (j, n))
+            parts.append(s["sup"].view(-1))
+        else:
+            parts.append(torch.zeros(n, dtype=torch.int64, device=s["xyz_original"].device))
+    return (parts[0] if len(parts) == 1 else torch.cat(parts)), sp_starts
+
+
+def merge_scenes(scenes, teachers=None, with_superpoints=False):
     """B scenes -> one batch: scene j becomes batch element j (the batch column of its voxel coordinates is overwritten), voxel
     and point arrays are concatenated in scene order, `v2p_index` is shifted by the voxels in front.  Returns (batch, teacher or
-    None, point_starts [B + 1] -- the rows of xyz_original / sem_pred_p that belong to scene j are point_starts[j] : [j + 1])."""
+    None, point_starts [B + 1] -- the rows of xyz_original / sem_pred_p that belong to scene j are point_starts[j] : [j + 1]).
+    with_superpoints: a fourth element, `merge_superpoints(scenes, point_starts)` -- with point_starts the scene table of
+    `postprocess.refine_merged_device`."""
+    if with_superpoints:
+        batch, teacher, starts = merge_scenes(scenes, teachers)
+        return batch, teacher, starts, merge_superpoints(scenes, starts)
     if len(scenes) == 1:                                  # a lone scene: nothing to concatenate
         s = scenes[0]
         xv = s["xyz_voxel"].clone()
@@ -108,10 +141,17 @@ def split_results(ret, point_starts):
 class SceneServer(object):
     """F forwards in flight x up to B scenes per forward.  `submit` returns a Future; `close` drains the queue."""
 
-    def __init__(self, model, max_batch=4, forwards_in_flight=2, device=None, epoch=1, split=True, streams=None):
-        """streams: the HIP streams of the workers (default: `forwards_in_flight` new ones; a process that already owns its
+    def __init__(self, model, max_batch=4, forwards_in_flight=2, device=None, epoch=1, split=True, streams=None, refine=None,
+                 paused=False):
+        """refine: an object with TEST_SCORE_THRESH, TEST_NPOINT_THRESH and TEST_NMS_THRESH -- every scene's result is then
+        dict(sem_pred_p, instances) (module docstring); a scene whose superpoint ids or classes are out of range gets a ValueError
+        on its own future, its batch-mates their results.  None (default): the raw forward results, as before.
+        paused: the workers start with `start()`, so scenes can be queued before the first forward is cut.
+        streams: the HIP streams of the workers (default: `forwards_in_flight` new ones; a process that already owns its
         in-flight streams passes them: streams created later can share a hardware queue -- DESIGN.md section 5, round 5 item 6b)."""
-        self.model, self.max_batch, self.epoch, self.split = model, int(max_batch), epoch, split
+        if not 1 <= int(max_batch) <= MAX_SCENES:
+            raise ValueError("max_batch must be in 1..%d (the batch axis of the forward's tables), got %r" % (MAX_SCENES, max_batch))
+        self.model, self.max_batch, self.epoch, self.split, self.refine = model, int(max_batch), epoch, split, refine
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self._q = queue.Queue()
         self._closed = False
@@ -120,6 +160,16 @@ class SceneServer(object):
         self._lock = threading.Lock()
         self._streams = list(streams) if streams is not None else [torch.cuda.Stream(self.device) for _ in range(int(forwards_in_flight))]
         self._threads = [threading.Thread(target=self._worker, args=(st,), daemon=True) for st in self._streams]
+        self._started = False
+        if not paused:
+            self.start()
+
+    def start(self):
+        """Start the workers of a server created with paused=True (no effect on a running one)."""
+        with self._lock:
+            if self._started:
+                return
+            self._started = True
         for t in self._threads:
             t.start()
 
@@ -134,6 +184,7 @@ class SceneServer(object):
 
     def close(self):
         self._closed = True
+        self.start()                        # a paused server still serves what was queued
         for _ in self._threads:
             self._q.put(None)
         for t in self._threads:
@@ -156,8 +207,28 @@ class SceneServer(object):
             items.append(nxt)
         return items
 
+    def _refined(self, ret, starts, sup, ws):
+        """Post-process the merged result for all its scenes; one read-back.  Returns (per-scene results or exceptions, workspace).
+        The outputs are copied out of the worker's workspace: the next forward of this worker overwrites it."""
+        n_prop = max(int(ret["proposals"][1].shape[0]) - 1, 0)
+        sizes = (n_prop, starts[-1], len(starts) - 1, sup[1][-1])
+        ws = postprocess.PostBatchWorkspace(*sizes, device=self.device) if ws is None else ws.grown_for(*sizes)
+        rb = postprocess.refine_merged_device(ret["sem_pred_p"], ret["proposals"], ret["clt_scores"], starts, sup[1], sup[0],
+                                              self.refine, workspace=ws)
+        rb.point_instance, rb.scores, rb.semantic_id, rb.npoints = (t.clone() for t in (rb.point_instance, rb.scores,
+                                                                                        rb.semantic_id, rb.npoints))
+        scalars = rb.scalars.tolist()                                   # the one read-back (it also waits for the forward)
+        res = []
+        for j in range(len(starts) - 1):
+            try:
+                res.append(dict(sem_pred_p=ret["sem_pred_p"][starts[j]:starts[j + 1]], instances=rb.scene(j, scalars)))
+            except ValueError as e:
+                res.append(e)
+        return res, ws
+
     def _worker(self, stream):
         torch.cuda.set_device(self.device)
+        ws = None                               # this worker's post-processing workspace (refine), grown when a batch does not fit
         with torch.cuda.stream(stream):
             while True:
                 items = self._take()
@@ -167,17 +238,26 @@ class SceneServer(object):
                 try:
                     for it in items:
                         stream.wait_event(it[3])
-                    batch, teacher, starts = merge_scenes([it[0] for it in items], [it[1] for it in items])
+                    merged = merge_scenes([it[0] for it in items], [it[1] for it in items], with_superpoints=self.refine is not None)
+                    batch, teacher, starts, sup = merged if self.refine is not None else merged + (None,)
                     with torch.no_grad():
                         ret = self.model(batch["feat_voxel"], batch["xyz_voxel"], batch["xyz_original"], batch["v2p_index"], None,
                                          self.epoch, "test", teacher=teacher, n_batch=len(items))
-                    res = split_results(ret, starts) if self.split else [dict(ret, point_starts=starts, scene=j) for j in range(len(items))]
+                    if self.refine is not None and "proposals" in ret:
+                        res, ws = self._refined(ret, starts, sup, ws)
+                    elif self.split:
+                        res = split_results(ret, starts)
+                    else:
+                        res = [dict(ret, point_starts=starts, scene=j) for j in range(len(items))]
                     stream.synchronize()
                     with self._lock:
                         self.forwards += 1
                         self.scenes += len(items)
                     for f, r in zip(futs, res):
-                        f.set_result(r)
+                        if isinstance(r, BaseException):
+                            f.set_exception(r)
+                        else:
+                            f.set_result(r)
                 except BaseException as e:      # noqa: BLE001 -- the exception belongs to the callers that wait on the futures
                     for f in futs:
                         if not f.done():
