@@ -576,6 +576,35 @@ int pbn_post_batch(const int64_t* proposals_idx, int n_entries, const void* prop
                    const int64_t* label_table, int n_labels, int32_t* point_instance, float* scores, int64_t* semantic_id,
                    int32_t* npoints, int32_t* scalars, void* workspace, size_t workspace_bytes, pbn_stream_t stream);
 
+/* The same pass WITH the TTA fold: the merged forward holds `copies` rotated copies of every scene (eval_map.py:48-70,
+ * dataset_preprocess.py:308-385: three copies as a batch of 3), and the proposals of all copies of a scene are refined together
+ * over the scene's n_j points, exactly as post.hip's single-scene device form does with n_fold = n_j.  The table is over FOLDED
+ * points:
+ *   n_scenes B >= 1, copies >= 1, B * copies <= PBN_MAX_SCENES (the merged forward's batch elements); point_start[0] = 0 <= ... <=
+ *   point_start[B]; scene j has n_j = point_start[j + 1] - point_start[j] points and occupies the merged (unfolded) points
+ *   copies * point_start[j] .. copies * point_start[j + 1], copy after copy, as valMerge concatenates them; n_points_merged =
+ *   copies * point_start[B].  sp_start as in pbn_scene_table.
+ * A proposal belongs to the scene of its first member (merged numbering).  A member's bit is (pt - copies * point_start[j]) % n_j:
+ * a member in another copy of the proposal's scene is folded in like any other (eval_map.py:67), a member outside the scene is
+ * dropped; duplicate bits after the fold are harmless (atomicOr, sizes from popcount).  Everything else is over folded points:
+ * superpoint int64[point_start[B]] (one id per folded point), point_instance int32[point_start[B]], scores / semantic_id / npoints
+ * [B, P], scalars = n_keep[B], status[B], and the workspace is pbn_post_batch_workspace_bytes(P, point_start[B], B, sp_start[B]).
+ * The class of a kept instance is pred_sem at its UNFOLDED first member through the label table (eval_map.py:64 reads it before the
+ * fold), so pred_sem holds n_points_merged entries.  Same tie rule, status bits, proposal limit and launch count (thirteen) as
+ * pbn_post_batch, integer atomics only; copies = 1 is pbn_post_batch, byte for byte.  PBN_ERR_ARG for a table that is not as
+ * stated, before any launch. */
+typedef struct pbn_tta_table {
+    int32_t n_scenes;
+    int32_t copies;
+    int32_t point_start[PBN_MAX_SCENES + 1];
+    int32_t sp_start[PBN_MAX_SCENES + 1];
+} pbn_tta_table;
+int pbn_post_batch_tta(const int64_t* proposals_idx, int n_entries, const void* proposals_offset, int offset_i64, int n_prop,
+                       const void* clt_score, int score_dtype, const void* pred_sem, int sem_i64, int n_points_merged,
+                       pbn_tta_table units, const int64_t* superpoint, float score_t, int npoint_t, float nms_t,
+                       const int64_t* label_table, int n_labels, int32_t* point_instance, float* scores, int64_t* semantic_id,
+                       int32_t* npoints, int32_t* scalars, void* workspace, size_t workspace_bytes, pbn_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * ScanNet AP evaluator, the association step of /root/reference/tools/eval.py:205-250
  * (`assign_instances_for_scan`).  The reference counts, for every (prediction, ground-truth instance) pair, the points

@@ -97,6 +97,12 @@ class SceneTable(ctypes.Structure):
     _fields_ = [("n_scenes", c_i32), ("point_start", c_i32 * (MAX_SCENES + 1)), ("sp_start", c_i32 * (MAX_SCENES + 1))]
 
 
+class TtaTable(ctypes.Structure):
+    """pbn_tta_table (include/pbnet_hip.h)."""
+    _fields_ = [("n_scenes", c_i32), ("copies", c_i32), ("point_start", c_i32 * (MAX_SCENES + 1)),
+                ("sp_start", c_i32 * (MAX_SCENES + 1))]
+
+
 class PostBatchLayout(ctypes.Structure):
     """pbn_post_batch_layout (include/pbnet_hip.h)."""
     _fields_ = [(k, c_i64) for k in ("masks", "counts", "prop_scene", "score", "rows", "pick_rows", "n_rows", "n_pick", "iou",
@@ -165,6 +171,8 @@ SIGNATURES = {
     "pbn_post_batch_workspace_bytes": (c_size, [c_int, c_int, c_int, c_int, ctypes.POINTER(PostBatchLayout)]),
     "pbn_post_batch": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_int, c_int, SceneTable, c_vp, c_float, c_int,
                                c_float, c_vp, c_int, c_i32p, c_f32p, c_vp, c_i32p, c_i32p, c_vp, c_size, c_vp]),
+    "pbn_post_batch_tta": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_int, c_int, TtaTable, c_vp, c_float, c_int,
+                                   c_float, c_vp, c_int, c_i32p, c_f32p, c_vp, c_i32p, c_i32p, c_vp, c_size, c_vp]),
     "pbn_instance_overlap": (c_int, [c_i32p, c_int, c_int, c_i32p, c_int, c_i32p, c_vp]),
     "pbn_gt_encode_dev": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_i32p, c_int, c_i32p, c_int, c_i32p, c_i32p, c_vp]),
     "pbn_gt_index_dev": (c_int, [c_vp, c_int, c_int, c_i32p, c_int, c_i32p, c_i32p, c_int, c_i32p, c_i32p, c_i32p, c_vp]),

@@ -1,5 +1,8 @@
 // post_batch.hip -- the post-processing of post.hip's device-resident form for ALL scenes of one merged forward
-// (pbnet_amd/serving.py): the same per-scene arithmetic with a scene axis, no TTA fold and no dense [P, n] table.
+// (pbnet_amd/serving.py): the same per-scene arithmetic with a scene axis and no dense [P, n] table.  pbn_post_batch has no TTA
+// fold; pbn_post_batch_tta folds the `copies` copies of every scene onto one, and is the same thirteen launches: the scene table
+// and every working table are over FOLDED points, and only three kernels see unfolded numbering (k_pb_scene_of, k_pb_set_bits,
+// the first-member class lookup of k_pb_compact) -- through fold_of_point, of which copies = 1 is pbn_post_batch.
 //   * the scene table (point ranges and vote-table ranges of the B <= PBN_MAX_SCENES scenes) is a launch argument, by value;
 //   * a proposal belongs to the scene of its first member; its bitset is over point - point_start[scene], row pitch = words of
 //     the largest scene;
@@ -39,6 +42,27 @@ __device__ __forceinline__ SceneRef scene_of_point(const pbn_scene_table& T, lon
     return r;
 }
 
+struct FoldRef { int scene, local; };
+
+// merged UNFOLDED point `pt` -> (scene, folded scene-local point).  Scene j's `copies` copies lie one after the other in
+// copies * point_start[j] .. copies * point_start[j + 1]; the fold is (pt - copies * point_start[j]) % n_j, taken with copies - 1
+// conditional subtractions (no division).  scene -1: the point lies in no scene.  copies = 1: scene_of_point and pt - point_base.
+__device__ __forceinline__ FoldRef fold_of_point(const pbn_scene_table& T, int copies, long long pt) {
+    int scene = 0, base = T.point_start[0], n = T.point_start[1] - T.point_start[0];
+#pragma unroll
+    for (int j = 1; j < PBN_MAX_SCENES; ++j)
+        if (j < T.n_scenes && pt >= (long long)copies * T.point_start[j]) {
+            scene = j;
+            base = T.point_start[j];
+            n = T.point_start[j + 1] - T.point_start[j];
+        }
+    if (pt < (long long)copies * T.point_start[0] || pt >= (long long)copies * table_at(T.point_start, T.n_scenes))
+        return FoldRef{-1, 0};
+    int local = (int)(pt - (long long)copies * base);              // < copies * n_j <= the merged point count: an int
+    for (int c = 1; c < copies; ++c) local -= local >= n ? n : 0;
+    return FoldRef{scene, local};
+}
+
 // the scene whose vote slice holds table row `row` (0 <= row < sp_start[B]); slices of capacity 0 are stepped over
 __device__ __forceinline__ int scene_of_vote_row(const pbn_scene_table& T, int row) {
     int s = 0;
@@ -51,35 +75,35 @@ __device__ __forceinline__ long long load_index(const void* p, int is_i64, long 
     return is_i64 ? ((const long long*)p)[i] : (long long)((const int*)p)[i];
 }
 
-// prop_scene[p] = scene of the first member (-1: no first member, or it lies in no scene); score[p] = clt_score[p] as fp32
+// prop_scene[p] = scene of the first member, in unfolded numbering (-1: no first member, or it lies in no scene); score[p] = clt_score[p] as fp32
 __global__ __launch_bounds__(TPB) void k_pb_scene_of(const long long* __restrict__ proposals_idx, int n_entries,
                                                     const void* __restrict__ offsets, int offsets_i64, int n_prop,
                                                     const void* __restrict__ clt_score, int score_dtype, pbn_scene_table T,
-                                                    int* __restrict__ prop_scene, float* __restrict__ score) {
+                                                    int copies, int* __restrict__ prop_scene, float* __restrict__ score) {
     const int p = blockIdx.x * TPB + threadIdx.x;
     if (p >= n_prop) return;
     const long long e0 = load_index(offsets, offsets_i64, p), e1 = load_index(offsets, offsets_i64, p + 1);
     int scene = -1;
-    if (e0 >= 0 && e0 < e1 && e1 <= n_entries) scene = scene_of_point(T, proposals_idx[2 * e0 + 1]).scene;
+    if (e0 >= 0 && e0 < e1 && e1 <= n_entries) scene = fold_of_point(T, copies, proposals_idx[2 * e0 + 1]).scene;
     prop_scene[p] = scene;
     score[p] = score_dtype == PBN_F32    ? ((const float*)clt_score)[p]
                : score_dtype == PBN_BF16 ? __bfloat162float(((const __hip_bfloat16*)clt_score)[p])
                                          : __half2float(((const __half*)clt_score)[p]);
 }
 
-// bit (point - point_start[scene]) of row proposal; a member outside its proposal's scene is dropped
+// bit (folded scene-local point) of row proposal: a member in another copy of the proposal's scene folds onto the same bits
+// (eval_map.py:67); a member outside its proposal's scene is dropped
 __global__ __launch_bounds__(TPB) void k_pb_set_bits(const long long* __restrict__ proposals_idx, int n_entries, int n_prop,
-                                                    const int* __restrict__ prop_scene, pbn_scene_table T, int pitch,
+                                                    const int* __restrict__ prop_scene, pbn_scene_table T, int copies, int pitch,
                                                     unsigned* __restrict__ masks) {
     const int e = blockIdx.x * TPB + threadIdx.x;
     if (e >= n_entries) return;
     const long long p = proposals_idx[2 * (size_t)e + 0];
     if (p < 0 || p >= n_prop) return;
     const int scene = prop_scene[p];
-    const SceneRef r = scene_of_point(T, proposals_idx[2 * (size_t)e + 1]);
+    const FoldRef r = fold_of_point(T, copies, proposals_idx[2 * (size_t)e + 1]);
     if (scene < 0 || r.scene != scene) return;
-    const int local = (int)(proposals_idx[2 * (size_t)e + 1] - r.point_base);
-    atomicOr(&masks[(size_t)p * pitch + (local >> 5)], 1u << (local & 31));
+    atomicOr(&masks[(size_t)p * pitch + (r.local >> 5)], 1u << (r.local & 31));
 }
 
 // counts[p] = popcount of row p (one wave per row)
@@ -290,7 +314,8 @@ __global__ __launch_bounds__(TPB) void k_pb_relabel(const int* __restrict__ sp_l
 
 // k_post_compact per scene (workgroup = scene): the picks that still own a point, in pick order, renumbered from 0
 // (renumber[scene, pick] = new number or -1); per kept instance its score, the class of the proposal's first member through the
-// label table and its point count; tails: score 0, class -1, count 0; n_keep[scene]
+// label table and its point count; tails: score 0, class -1, count 0; n_keep[scene].  The first member is looked up UNFOLDED
+// (eval_map.py:64 reads the class before the fold): pred_sem holds n_points = copies * (folded points) labels
 __global__ __launch_bounds__(TPB) void k_pb_compact(const int* __restrict__ counts2, const int* __restrict__ pick_rows,
                                                    const int* __restrict__ n_pick_dev, int cap, const float* __restrict__ score,
                                                    const long long* __restrict__ proposals_idx, int n_entries,
@@ -406,18 +431,25 @@ extern "C" size_t pbn_post_batch_workspace_bytes(int n_prop, int n_points_total,
     return (size_t)L.total_bytes;
 }
 
-extern "C" int pbn_post_batch(const int64_t* proposals_idx, int n_entries, const void* proposals_offset, int offset_i64, int n_prop,
-                              const void* clt_score, int score_dtype, const void* pred_sem, int sem_i64, int n_points_total,
-                              pbn_scene_table scenes, const int64_t* superpoint, float score_t, int npoint_t, float nms_t,
-                              const int64_t* label_table, int n_labels, int32_t* point_instance, float* scores,
-                              int64_t* semantic_id, int32_t* npoints, int32_t* scalars, void* workspace, size_t workspace_bytes,
-                              pbn_stream_t stream_) {
+namespace pbn {
+namespace {
+
+// Both entries.  `scenes` is over FOLDED points; the merged arrays the proposals and pred_sem index hold n_points_merged =
+// copies * scenes.point_start[B] points (copies = 1: pbn_post_batch).
+int post_batch_run(const int64_t* proposals_idx, int n_entries, const void* proposals_offset, int offset_i64, int n_prop,
+                   const void* clt_score, int score_dtype, const void* pred_sem, int sem_i64, int n_points_merged,
+                   const pbn_scene_table& scenes, int copies, const int64_t* superpoint, float score_t, int npoint_t, float nms_t,
+                   const int64_t* label_table, int n_labels, int32_t* point_instance, float* scores, int64_t* semantic_id,
+                   int32_t* npoints, int32_t* scalars, void* workspace, size_t workspace_bytes, pbn_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     const int B = scenes.n_scenes;
-    if (n_prop < 0 || n_entries < 0 || n_points_total < 1 || n_labels < 1 || B < 1 || B > PBN_MAX_SCENES) return PBN_ERR_ARG;
+    if (n_prop < 0 || n_entries < 0 || n_points_merged < 1 || n_labels < 1 || B < 1 || B > PBN_MAX_SCENES) return PBN_ERR_ARG;
+    if (copies < 1 || (long long)B * copies > PBN_MAX_SCENES) return PBN_ERR_ARG;
     if (n_prop > POST_MAX_PROPOSALS) return PBN_ERR_UNSUPPORTED;
     if (score_dtype != PBN_F32 && score_dtype != PBN_BF16 && score_dtype != PBN_F16) return PBN_ERR_ARG;
-    if (scenes.point_start[0] != 0 || scenes.sp_start[0] != 0 || scenes.point_start[B] != n_points_total) return PBN_ERR_ARG;
+    if (scenes.point_start[0] != 0 || scenes.sp_start[0] != 0 || (long long)copies * scenes.point_start[B] != n_points_merged)
+        return PBN_ERR_ARG;
+    const int n_points_total = scenes.point_start[B];          // folded: what every table below is over
     int largest = 0;
     for (int j = 0; j < B; ++j) {
         if (scenes.point_start[j + 1] < scenes.point_start[j] || scenes.sp_start[j + 1] < scenes.sp_start[j]) return PBN_ERR_ARG;
@@ -461,10 +493,10 @@ extern "C" int pbn_post_batch(const int64_t* proposals_idx, int n_entries, const
 
     { const int frc_ = fill_bytes(masks, 0, sizeof(uint32_t) * (size_t)n_prop * pitch, stream); if (frc_ != PBN_OK) return frc_; }
     hipLaunchKernelGGL(k_pb_scene_of, dim3(cdiv(n_prop, TPB)), dim3(TPB), 0, stream, pidx, n_entries, proposals_offset, offset_i64,
-                       n_prop, clt_score, score_dtype, scenes, prop_scene, score);
+                       n_prop, clt_score, score_dtype, scenes, copies, prop_scene, score);
     if (n_entries > 0)
         hipLaunchKernelGGL(k_pb_set_bits, dim3(cdiv(n_entries, TPB)), dim3(TPB), 0, stream, pidx, n_entries, n_prop, prop_scene,
-                           scenes, pitch, masks);
+                           scenes, copies, pitch, masks);
     hipLaunchKernelGGL(k_pb_popcount, dim3(n_prop), dim3(64), 0, stream, masks, pitch, counts);
     hipLaunchKernelGGL(k_pb_select, dim3(B), dim3(TPB), 0, stream, score, counts, prop_scene, n_prop, score_t, npoint_t, rows,
                        n_rows, status);
@@ -484,10 +516,42 @@ extern "C" int pbn_post_batch(const int64_t* proposals_idx, int n_entries, const
     hipLaunchKernelGGL(k_pb_relabel, dim3(nb_points), dim3(TPB), 0, stream, sp_label, (const long long*)superpoint, seg, n_pick,
                        n_prop, n_points_total, scenes, seg_refined, counts2);
     hipLaunchKernelGGL(k_pb_compact, dim3(B), dim3(TPB), 0, stream, counts2, pick_rows, n_pick, n_prop, score, pidx, n_entries,
-                       proposals_offset, offset_i64, pred_sem, sem_i64, n_points_total, (const long long*)label_table, n_labels,
+                       proposals_offset, offset_i64, pred_sem, sem_i64, n_points_merged, (const long long*)label_table, n_labels,
                        renumber, scores, (long long*)semantic_id, npoints, n_keep, status);
     hipLaunchKernelGGL(k_pb_point_instance, dim3(nb_points), dim3(TPB), 0, stream, seg_refined, renumber, n_prop, n_points_total,
                        scenes, point_instance);
     PBN_LAUNCH_CHECK();
     return PBN_OK;
+}
+
+}  // namespace
+}  // namespace pbn
+
+extern "C" int pbn_post_batch(const int64_t* proposals_idx, int n_entries, const void* proposals_offset, int offset_i64, int n_prop,
+                              const void* clt_score, int score_dtype, const void* pred_sem, int sem_i64, int n_points_total,
+                              pbn_scene_table scenes, const int64_t* superpoint, float score_t, int npoint_t, float nms_t,
+                              const int64_t* label_table, int n_labels, int32_t* point_instance, float* scores,
+                              int64_t* semantic_id, int32_t* npoints, int32_t* scalars, void* workspace, size_t workspace_bytes,
+                              pbn_stream_t stream) {
+    return post_batch_run(proposals_idx, n_entries, proposals_offset, offset_i64, n_prop, clt_score, score_dtype, pred_sem, sem_i64,
+                          n_points_total, scenes, 1, superpoint, score_t, npoint_t, nms_t, label_table, n_labels, point_instance,
+                          scores, semantic_id, npoints, scalars, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pbn_post_batch_tta(const int64_t* proposals_idx, int n_entries, const void* proposals_offset, int offset_i64,
+                                  int n_prop, const void* clt_score, int score_dtype, const void* pred_sem, int sem_i64,
+                                  int n_points_merged, pbn_tta_table units, const int64_t* superpoint, float score_t, int npoint_t,
+                                  float nms_t, const int64_t* label_table, int n_labels, int32_t* point_instance, float* scores,
+                                  int64_t* semantic_id, int32_t* npoints, int32_t* scalars, void* workspace,
+                                  size_t workspace_bytes, pbn_stream_t stream) {
+    if (units.n_scenes < 1 || units.n_scenes > PBN_MAX_SCENES) return PBN_ERR_ARG;
+    pbn_scene_table folded;
+    folded.n_scenes = units.n_scenes;
+    for (int j = 0; j <= PBN_MAX_SCENES; ++j) {
+        folded.point_start[j] = units.point_start[j];
+        folded.sp_start[j] = units.sp_start[j];
+    }
+    return post_batch_run(proposals_idx, n_entries, proposals_offset, offset_i64, n_prop, clt_score, score_dtype, pred_sem, sem_i64,
+                          n_points_merged, folded, units.copies, superpoint, score_t, npoint_t, nms_t, label_table, n_labels,
+                          point_instance, scores, semantic_id, npoints, scalars, workspace, workspace_bytes, stream);
 }

@@ -11,7 +11,11 @@ read-back, `sp.max().item()`, the vanished-cluster read-back and the index uploa
 the caller asks for `.sliced()`.
 
 `refine_batch_device` is the device-resident form for ALL scenes of one merged forward (pbnet_amd/serving.py), without the TTA
-fold: one pass with a scene axis (csrc/post_batch.hip), the masks as one label per point, one read-back of n_keep[B] / status[B]."""
+fold: one pass with a scene axis (csrc/post_batch.hip), the masks as one label per point, one read-back of n_keep[B] / status[B].
+
+`refine_tta_merged_device` is that pass WITH the fold, for a merged forward that holds `copies` rotated copies of every scene (the
+reference's evaluation unit, eval_map.py:48-70): the proposals of all copies of a scene are refined together over the scene's own
+points (pbn_post_batch_tta).  Scene table, working tables and results are over folded points."""
 import numpy as np
 import torch
 
@@ -335,13 +339,7 @@ def refine_merged_device(sem_pred_p, proposals, clt_scores, point_starts, sp_sta
     sp_starts[j + 1] == sp_starts[j] are never read; None when no scene has superpoints)."""
     proposals_idx, proposals_offset = proposals[0], proposals[1]
     N.require_cuda(proposals_idx, proposals_offset, sem_pred_p, clt_scores, superpoint)
-    if proposals_idx.dtype != torch.int64:
-        raise TypeError("proposals_idx must be int64, got %s" % proposals_idx.dtype)
-    for name, t in (("proposals_offset", proposals_offset), ("sem_pred_p", sem_pred_p)):
-        if t.dtype not in (torch.int32, torch.int64):
-            raise TypeError("%s must be int32 or int64, got %s" % (name, t.dtype))
-    if clt_scores.dtype not in N.DT:
-        raise TypeError("clt_scores must be float32, bfloat16 or float16, got %s" % clt_scores.dtype)
+    _check_merged_inputs(proposals_idx, proposals_offset, sem_pred_p, clt_scores)
     table = scene_table(point_starts, sp_starts)
     b, n_total, n_sp_total = table.n_scenes, int(point_starts[-1]), int(sp_starts[-1])
     if int(sem_pred_p.numel()) != n_total:
@@ -368,6 +366,74 @@ def refine_merged_device(sem_pred_p, proposals, clt_scores, point_starts, sp_sta
                                N.ptr(ws.label_table), int(ws.label_table.numel()), N.ptr(ws.point_instance), N.ptr(ws.scores),
                                N.ptr(ws.semantic_id), N.ptr(ws.npoints), N.ptr(ws.scalars), N.ptr(ws.buffer), ws.nbytes,
                                N.current_stream()), "pbn_post_batch")
+    return res
+
+
+def tta_table(point_starts, sp_starts, copies):
+    """The by-value launch argument of pbn_post_batch_tta from two host lists of B + 1 ascending starts over FOLDED points and the
+    number of copies of every scene in the merged forward (B * copies batch elements, at most MAX_SCENES)."""
+    b, copies = len(point_starts) - 1, int(copies)
+    if copies < 1:
+        raise ValueError("copies must be at least 1, got %d" % copies)
+    if len(sp_starts) != b + 1:
+        raise ValueError("%d point starts, %d superpoint starts" % (len(point_starts), len(sp_starts)))
+    if b < 1 or b * copies > MAX_SCENES:
+        raise ValueError("a merged forward holds 1..%d batch elements, got %d scenes x %d copies" % (MAX_SCENES, b, copies))
+    t = N.TtaTable()
+    t.n_scenes, t.copies = b, copies
+    for j in range(b + 1):
+        t.point_start[j], t.sp_start[j] = int(point_starts[j]), int(sp_starts[j])
+    return t
+
+
+def _check_merged_inputs(proposals_idx, proposals_offset, sem_pred_p, clt_scores):
+    """The dtype checks both merged entries make."""
+    if proposals_idx.dtype != torch.int64:
+        raise TypeError("proposals_idx must be int64, got %s" % proposals_idx.dtype)
+    for name, t in (("proposals_offset", proposals_offset), ("sem_pred_p", sem_pred_p)):
+        if t.dtype not in (torch.int32, torch.int64):
+            raise TypeError("%s must be int32 or int64, got %s" % (name, t.dtype))
+    if clt_scores.dtype not in N.DT:
+        raise TypeError("clt_scores must be float32, bfloat16 or float16, got %s" % clt_scores.dtype)
+
+
+def refine_tta_merged_device(sem_pred_p, proposals, clt_scores, point_starts, sp_starts, superpoint, cfg, copies=3, workspace=None):
+    """`refine_merged_device` with the TTA fold (pbn_post_batch_tta): the merged forward holds `copies` copies of each of its B
+    scenes (B * copies <= MAX_SCENES batch elements, scene j's copies one after the other).  `point_starts` / `sp_starts`: B + 1
+    host integers over FOLDED points; sem_pred_p holds copies * point_starts[-1] labels (the class of an instance is read at its
+    unfolded first member, eval_map.py:64); `superpoint` int64[point_starts[-1]], one scene-local id per folded point (None when no
+    scene has any).  Returns a `RefinedBatch` over folded points: scene j's point_instance has n_j entries.  Thirteen launches for
+    all scenes, no host stop; `workspace`: a `PostBatchWorkspace` sized by folded points."""
+    proposals_idx, proposals_offset = proposals[0], proposals[1]
+    N.require_cuda(proposals_idx, proposals_offset, sem_pred_p, clt_scores, superpoint)
+    _check_merged_inputs(proposals_idx, proposals_offset, sem_pred_p, clt_scores)
+    table = tta_table(point_starts, sp_starts, copies)
+    b, n_total, n_sp_total = table.n_scenes, int(point_starts[-1]), int(sp_starts[-1])
+    n_merged = table.copies * n_total
+    if int(sem_pred_p.numel()) != n_merged:
+        raise ValueError("sem_pred_p holds %d points, the table %d x %d" % (sem_pred_p.numel(), table.copies, n_total))
+    if n_sp_total > 0:
+        if superpoint is None or superpoint.dtype != torch.int64 or int(superpoint.numel()) < n_total:
+            raise ValueError("superpoint must be an int64 device tensor of %d ids" % n_total)
+    n_prop = max(int(proposals_offset.shape[0]) - 1, 0)
+    lib = N.lib()
+    if n_prop > lib.pbn_post_max_proposals():
+        raise ValueError("the device form takes at most %d proposals, got %d" % (lib.pbn_post_max_proposals(), n_prop))
+    ws = workspace
+    if ws is None:
+        ws = PostBatchWorkspace(n_prop, n_total, b, n_sp_total, proposals_idx.device)
+    elif not ws.fits(n_prop, n_total, b, n_sp_total):
+        raise ValueError("workspace (%d, %d, %d, %d) does not fit (%d, %d, %d, %d)" % (
+            ws.n_prop, ws.n_points_total, ws.n_scenes, ws.n_superpoints_total, n_prop, n_total, b, n_sp_total))
+    res = RefinedBatch(ws, n_prop, point_starts, sp_starts)
+    pidx, off, sem, clt = proposals_idx.contiguous(), proposals_offset.contiguous(), sem_pred_p.contiguous(), clt_scores.contiguous()
+    sp = None if n_sp_total == 0 else superpoint.contiguous()
+    N.check(lib.pbn_post_batch_tta(N.ptr(pidx), int(pidx.shape[0]), N.ptr(off), int(off.dtype == torch.int64), n_prop, N.ptr(clt),
+                                   N.DT[clt.dtype], N.ptr(sem), int(sem.dtype == torch.int64), n_merged, table, N.ptr(sp),
+                                   float(cfg.TEST_SCORE_THRESH), int(cfg.TEST_NPOINT_THRESH), float(cfg.TEST_NMS_THRESH),
+                                   N.ptr(ws.label_table), int(ws.label_table.numel()), N.ptr(ws.point_instance), N.ptr(ws.scores),
+                                   N.ptr(ws.semantic_id), N.ptr(ws.npoints), N.ptr(ws.scalars), N.ptr(ws.buffer), ws.nbytes,
+                                   N.current_stream()), "pbn_post_batch_tta")
     return res
 
 

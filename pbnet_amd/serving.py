@@ -18,6 +18,12 @@ post-processing runs once for all its scenes (`postprocess.refine_batch_device`,
 and `res["instances"]` is dict(point_instance [N], scores [K], semantic_id [K], npoints [K]).  A scene may then carry `sup`
 (int64 device superpoint ids) and `n_superpoints` (their upper bound).
 
+With `SceneServer(..., refine=cfg, tta=3)` what is submitted is the reference's evaluation unit (eval_map.py:48-70): the three rotated
+copies of a scene as a batch of 3, as `DeviceMerge.val_merge([id])` or `synth.make_val_batch(copies=3)` build it.  Up to
+MAX_SCENES // 3 = 2 waiting units share one forward (6 batch elements), the post-processing folds every unit's copies onto the
+scene's own points (`postprocess.refine_tta_merged_device`), and `res["instances"]["point_instance"]` has one entry per point of
+the scene, `res["sem_pred_p"]` the unit's 3 n labels.
+
 `merge_scenes` / `split_results` are the two pure functions; `SceneServer` is the small scheduler around them: F worker threads,
 each with its own HIP stream (create the server FIRST in a process: the runtime maps a process's first streams to distinct
 hardware queues), each taking up to `max_batch` waiting scenes per forward -- it never waits for a batch to fill:
@@ -86,6 +92,44 @@ def merge_scenes(scenes, teachers=None, with_superpoints=False):
     return batch, teacher, starts
 
 
+def merge_tta_units(units, copies=3, teachers=None):
+    """B test-time-augmentation units -> one batch of B * copies batch elements.  A unit is one scene as valMerge builds it:
+    `copies` rotated copies one after the other -- xyz_voxel with batch column 0 .. copies - 1, feat_voxel, xyz_original
+    [copies * n, 3], v2p_index [copies * n], optionally `sup` (int64 [n], one id per point of the scene) and `n_superpoints`.
+    Unit j's batch column becomes copies * j + c, `v2p_index` is shifted by the voxels in front.  Returns (batch, point_starts,
+    (superpoint ids int64 [N_folded] or None, sp_starts)) with point_starts the B + 1 starts over FOLDED points (unit j owns the
+    merged points copies * point_starts[j] : copies * point_starts[j + 1]) -- the table of `postprocess.refine_tta_merged_device`.
+    `teachers`: one dict per unit or None for all; the merged one is batch["teacher"] (None without)."""
+    copies = int(copies)
+    if copies < 1 or not 1 <= len(units) * copies <= MAX_SCENES:
+        raise ValueError("a merged forward holds 1..%d batch elements, got %d units x %d copies" % (MAX_SCENES, len(units), copies))
+    teachers = [None] * len(units) if teachers is None else list(teachers)
+    if len(teachers) != len(units) or len({t is None for t in teachers}) > 1:
+        raise ValueError("teachers must be given for every unit of a merged forward or for none")
+    vox, feat, xyz, v2p, starts = [], [], [], [], [0]
+    nv = 0
+    for j, u in enumerate(units):
+        n_all = int(u["xyz_original"].shape[0])
+        if n_all % copies or int(u["v2p_index"].shape[0]) != n_all:
+            raise ValueError("unit %d: %d points (%d v2p entries) are not %d copies of one scene" % (j, n_all, u["v2p_index"].shape[0],
+                                                                                                  copies))
+        xv = u["xyz_voxel"].clone()
+        if j:
+            xv[:, 0] += copies * j
+        vox.append(xv)
+        feat.append(u["feat_voxel"])
+        xyz.append(u["xyz_original"])
+        v2p.append(u["v2p_index"] + nv if nv else u["v2p_index"])
+        nv += int(xv.shape[0])
+        starts.append(starts[-1] + n_all // copies)
+    one = len(units) == 1
+    batch = {"xyz_voxel": vox[0] if one else torch.cat(vox), "feat_voxel": feat[0] if one else torch.cat(feat),
+             "xyz_original": xyz[0] if one else torch.cat(xyz), "v2p_index": v2p[0] if one else torch.cat(v2p), "teacher": None}
+    if teachers[0] is not None:
+        batch["teacher"] = teachers[0] if one else {k: torch.cat([t[k] for t in teachers]) for k in teachers[0]}
+    return batch, starts, merge_superpoints(units, starts)
+
+
 def split_results(ret, point_starts):
     """The merged forward's results -> one result per scene, in the reference's own output form (`proposals_idx` rows are
     (proposal, point) with the proposal numbered from 0 and the point index local to the scene; `proposals_offset` starts at 0).
@@ -141,17 +185,31 @@ def split_results(ret, point_starts):
 class SceneServer(object):
     """F forwards in flight x up to B scenes per forward.  `submit` returns a Future; `close` drains the queue."""
 
-    def __init__(self, model, max_batch=4, forwards_in_flight=2, device=None, epoch=1, split=True, streams=None, refine=None,
-                 paused=False):
+    def __init__(self, model, max_batch=None, forwards_in_flight=2, device=None, epoch=1, split=True, streams=None, refine=None,
+                 paused=False, tta=None):
         """refine: an object with TEST_SCORE_THRESH, TEST_NPOINT_THRESH and TEST_NMS_THRESH -- every scene's result is then
         dict(sem_pred_p, instances) (module docstring); a scene whose superpoint ids or classes are out of range gets a ValueError
         on its own future, its batch-mates their results.  None (default): the raw forward results, as before.
         paused: the workers start with `start()`, so scenes can be queued before the first forward is cut.
         streams: the HIP streams of the workers (default: `forwards_in_flight` new ones; a process that already owns its
-        in-flight streams passes them: streams created later can share a hardware queue -- DESIGN.md section 5, round 5 item 6b)."""
-        if not 1 <= int(max_batch) <= MAX_SCENES:
-            raise ValueError("max_batch must be in 1..%d (the batch axis of the forward's tables), got %r" % (MAX_SCENES, max_batch))
-        self.model, self.max_batch, self.epoch, self.split, self.refine = model, int(max_batch), epoch, split, refine
+        in-flight streams passes them: streams created later can share a hardware queue -- DESIGN.md section 5, round 5 item 6b).
+        max_batch: scenes (with tta: units) per forward at most; default 4, with tta min(4, MAX_SCENES // tta).
+        tta: copies per submitted unit (the reference evaluates with 3).  `submit` then takes a unit (`merge_tta_units`), a forward
+        holds up to MAX_SCENES // tta units, and a unit's result is dict(sem_pred_p [tta * n], instances over the scene's n
+        points), the copies folded in the post-processing -- which is why tta needs refine.  None (default): as before."""
+        if tta is not None:
+            if refine is None:
+                raise ValueError("tta needs refine: the copies are folded in the post-processing")
+            if not 1 <= int(tta) <= MAX_SCENES:
+                raise ValueError("tta must be in 1..%d (the batch axis of the forward's tables), got %r" % (MAX_SCENES, tta))
+            tta = int(tta)
+        most = MAX_SCENES if tta is None else MAX_SCENES // tta
+        if max_batch is None:
+            max_batch = min(4, most)
+        if not 1 <= int(max_batch) <= most:
+            raise ValueError("max_batch must be in 1..%d (the batch axis of the forward's tables%s), got %r" % (
+                most, "" if tta is None else ", %d copies per unit" % tta, max_batch))
+        self.model, self.max_batch, self.epoch, self.split, self.refine, self.tta = model, int(max_batch), epoch, split, refine, tta
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self._q = queue.Queue()
         self._closed = False
@@ -213,18 +271,34 @@ class SceneServer(object):
         n_prop = max(int(ret["proposals"][1].shape[0]) - 1, 0)
         sizes = (n_prop, starts[-1], len(starts) - 1, sup[1][-1])
         ws = postprocess.PostBatchWorkspace(*sizes, device=self.device) if ws is None else ws.grown_for(*sizes)
-        rb = postprocess.refine_merged_device(ret["sem_pred_p"], ret["proposals"], ret["clt_scores"], starts, sup[1], sup[0],
-                                              self.refine, workspace=ws)
+        c = 1 if self.tta is None else self.tta     # with tta `starts` are over folded points and unit j holds c copies of them
+        if self.tta is None:
+            rb = postprocess.refine_merged_device(ret["sem_pred_p"], ret["proposals"], ret["clt_scores"], starts, sup[1], sup[0],
+                                                  self.refine, workspace=ws)
+        else:
+            rb = postprocess.refine_tta_merged_device(ret["sem_pred_p"], ret["proposals"], ret["clt_scores"], starts, sup[1], sup[0],
+                                                      self.refine, copies=c, workspace=ws)
         rb.point_instance, rb.scores, rb.semantic_id, rb.npoints = (t.clone() for t in (rb.point_instance, rb.scores,
                                                                                         rb.semantic_id, rb.npoints))
         scalars = rb.scalars.tolist()                                   # the one read-back (it also waits for the forward)
         res = []
         for j in range(len(starts) - 1):
             try:
-                res.append(dict(sem_pred_p=ret["sem_pred_p"][starts[j]:starts[j + 1]], instances=rb.scene(j, scalars)))
+                res.append(dict(sem_pred_p=ret["sem_pred_p"][c * starts[j]:c * starts[j + 1]], instances=rb.scene(j, scalars)))
             except ValueError as e:
                 res.append(e)
         return res, ws
+
+    def _forward_tta(self, items, ws):
+        """One merged forward of up to MAX_SCENES // tta units; returns (per-unit results or exceptions, workspace)."""
+        t = self.tta
+        batch, starts, sup = merge_tta_units([it[0] for it in items], t, [it[1] for it in items])
+        with torch.no_grad():
+            ret = self.model(batch["feat_voxel"], batch["xyz_voxel"], batch["xyz_original"], batch["v2p_index"], None, self.epoch,
+                             "test", teacher=batch["teacher"], n_batch=t * len(items))
+        if "proposals" in ret:
+            return self._refined(ret, starts, sup, ws)
+        return [dict(sem_pred_p=ret["sem_pred_p"][t * starts[j]:t * starts[j + 1]]) for j in range(len(items))], ws
 
     def _worker(self, stream):
         torch.cuda.set_device(self.device)
@@ -238,17 +312,21 @@ class SceneServer(object):
                 try:
                     for it in items:
                         stream.wait_event(it[3])
-                    merged = merge_scenes([it[0] for it in items], [it[1] for it in items], with_superpoints=self.refine is not None)
-                    batch, teacher, starts, sup = merged if self.refine is not None else merged + (None,)
-                    with torch.no_grad():
-                        ret = self.model(batch["feat_voxel"], batch["xyz_voxel"], batch["xyz_original"], batch["v2p_index"], None,
-                                         self.epoch, "test", teacher=teacher, n_batch=len(items))
-                    if self.refine is not None and "proposals" in ret:
-                        res, ws = self._refined(ret, starts, sup, ws)
-                    elif self.split:
-                        res = split_results(ret, starts)
+                    if self.tta is not None:
+                        res, ws = self._forward_tta(items, ws)
                     else:
-                        res = [dict(ret, point_starts=starts, scene=j) for j in range(len(items))]
+                        merged = merge_scenes([it[0] for it in items], [it[1] for it in items],
+                                              with_superpoints=self.refine is not None)
+                        batch, teacher, starts, sup = merged if self.refine is not None else merged + (None,)
+                        with torch.no_grad():
+                            ret = self.model(batch["feat_voxel"], batch["xyz_voxel"], batch["xyz_original"], batch["v2p_index"], None,
+                                             self.epoch, "test", teacher=teacher, n_batch=len(items))
+                        if self.refine is not None and "proposals" in ret:
+                            res, ws = self._refined(ret, starts, sup, ws)
+                        elif self.split:
+                            res = split_results(ret, starts)
+                        else:
+                            res = [dict(ret, point_starts=starts, scene=j) for j in range(len(items))]
                     stream.synchronize()
                     with self._lock:
                         self.forwards += 1
