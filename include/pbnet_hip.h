@@ -605,6 +605,47 @@ int pbn_post_batch_tta(const int64_t* proposals_idx, int n_entries, const void* 
                        const int64_t* label_table, int n_labels, int32_t* point_instance, float* scores, int64_t* semantic_id,
                        int32_t* npoints, int32_t* scalars, void* workspace, size_t workspace_bytes, pbn_stream_t stream);
 
+/* The scene summary (csrc/summary.hip): what a caller still computes from the results of pbn_post_batch[_tta], in one pass over
+ * the FOLDED points of the merged forward, on the same stream and without a read-back.  `units` is the table of
+ * pbn_post_batch_tta (copies = 1: the plain merged forward); B = units.n_scenes, P = n_prop, n_j the folded points of scene j,
+ * N = point_start[B]; point_instance int32[N] and post_scalars (n_keep[B], ...) are that pass's outputs, n_keep[j] =
+ * post_scalars[j] stays on the device (clamped so that the scenes' counts sum to at most P).
+ *   sem_fold int32[N]        : sem_score is the forward's score table [n_points_merged, n_cls], row stride ld elements, element type
+ *                              score_dtype; the copies of point i of scene j are rows copies * point_start[j] + c * n_j + i.  Per
+ *                              class s = widen(copy 0), then s = s + widen(copy c) for c = 1 .. copies - 1, each ONE float32
+ *                              addition in that order; the label is the first maximum (`v > best`, as pbn_sem_argmax_table: a NaN
+ *                              never wins, an all-NaN row gives class 0).  copies = 1 equals pbn_sem_argmax_table's sem_pred.
+ *   class_vote int64[B, P],
+ *   class_points int32[B, P] : for the n_keep[j] kept instances of scene j (the rows of scores / semantic_id / npoints): the class
+ *                              with the most points among the instance's points, counted on sem_fold, ties to the lower class,
+ *                              through label_table (eval_map.py:142-155), and that count.  A class outside [0, n_labels) gives -1
+ *                              and ORs 2 into status[j].  Tails -1 / 0.
+ *   box f32[B, P, 6],
+ *   centroid f32[B, P, 3]    : min xyz then max xyz, and the mean, of the instance's points; xyz f32[N, 3] in the scene's own frame
+ *                              (NULL: both tables are left untouched).  Minima and maxima are reduced as order-preserving integer
+ *                              keys of the float32 bits; the centre is exact and independent of the order of summation: q =
+ *                              (int64) rint(x * 65536.0f) per coordinate (ties to even), summed with integer atomics, centroid =
+ *                              (float)((double) sum q / (double) count / 65536.0).  A point with a NaN coordinate or |x| >= 32768
+ *                              takes no part in box or centre (it still votes) and ORs 4 into status[j], whether or not it belongs
+ *                              to an instance; an instance without a
+ *                              valid point gets NaN.  Tails 0.
+ *   status int32[B]          : cleared by the first launch; bit 2 and bit 4 as above, bit 8: a point_instance value >= n_keep[j] or
+ *                              negative other than -100 (the point counts for no instance).
+ * Three launches (clear, fold + accumulate with one lane per folded point, finalise), integer atomics only, so two runs give the
+ * same bytes.  A workgroup keeps the accumulators of the scene of its first point in LDS when that scene has at most
+ * pbn_scene_summary_lds_instances(n_cls) kept instances (0 = no such path) and adds to the workspace directly otherwise.  The
+ * workspace holds one accumulator row per proposal (pbn_scene_summary_workspace_bytes; 0 for sizes outside the supported range),
+ * 8-byte aligned.  All before any launch: PBN_ERR_ARG for a table that is not as stated, n_cls outside [1, 32], ld < n_cls, an
+ * unknown dtype or a missing pointer; PBN_ERR_UNSUPPORTED above pbn_post_max_proposals(); PBN_ERR_WORKSPACE for a workspace that
+ * is too small.  n_prop = 0 is served: sem_fold and status are written, the tables are empty (point_instance, post_scalars,
+ * label_table, the tables and the workspace may then be NULL). */
+size_t pbn_scene_summary_workspace_bytes(int n_prop, int n_cls);
+int pbn_scene_summary_lds_instances(int n_cls);
+int pbn_scene_summary(const void* sem_score, int ld, int n_cls, int score_dtype, int n_points_merged, pbn_tta_table units,
+                      const int32_t* point_instance, const int32_t* post_scalars, int n_prop, const float* xyz,
+                      const int64_t* label_table, int n_labels, int32_t* sem_fold, int64_t* class_vote, int32_t* class_points,
+                      float* box, float* centroid, int32_t* status, void* workspace, size_t workspace_bytes, pbn_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * ScanNet AP evaluator, the association step of /root/reference/tools/eval.py:205-250
  * (`assign_instances_for_scan`).  The reference counts, for every (prediction, ground-truth instance) pair, the points

@@ -173,6 +173,10 @@ SIGNATURES = {
                                c_float, c_vp, c_int, c_i32p, c_f32p, c_vp, c_i32p, c_i32p, c_vp, c_size, c_vp]),
     "pbn_post_batch_tta": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_int, c_int, TtaTable, c_vp, c_float, c_int,
                                    c_float, c_vp, c_int, c_i32p, c_f32p, c_vp, c_i32p, c_i32p, c_vp, c_size, c_vp]),
+    "pbn_scene_summary_workspace_bytes": (c_size, [c_int, c_int]),
+    "pbn_scene_summary_lds_instances": (c_int, [c_int]),
+    "pbn_scene_summary": (c_int, [c_vp, c_int, c_int, c_int, c_int, TtaTable, c_i32p, c_i32p, c_int, c_f32p, c_vp, c_int, c_i32p,
+                                  c_vp, c_i32p, c_f32p, c_f32p, c_i32p, c_vp, c_size, c_vp]),
     "pbn_instance_overlap": (c_int, [c_i32p, c_int, c_int, c_i32p, c_int, c_i32p, c_vp]),
     "pbn_gt_encode_dev": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_i32p, c_int, c_i32p, c_int, c_i32p, c_i32p, c_vp]),
     "pbn_gt_index_dev": (c_int, [c_vp, c_int, c_int, c_i32p, c_int, c_i32p, c_i32p, c_int, c_i32p, c_i32p, c_i32p, c_vp]),

@@ -7,6 +7,9 @@
 namespace pbn {
 
 constexpr int WAVE = 64;
+// classes a semantic head may have: bounds the LDS tables of k_sem_argmax_table / k_select_points (stages.hip) and the score
+// registers of k_summary_points (summary.hip)
+constexpr int SEL_MAX_CLASSES = 32;
 
 extern thread_local int g_last_hip_error;
 

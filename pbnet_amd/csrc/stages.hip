@@ -280,8 +280,7 @@ __global__ __launch_bounds__(TPB) void k_mlp_rows_mfma(const T* __restrict__ in,
 // ---- semantic argmax + own-class softmax score + [class, batch] population table (PBNet.py:134,151-163) -------------
 // Block = SEL_BLOCK consecutive points.  Besides the global table it leaves the per-block class histogram that
 // k_select_points turns into stable output positions.
-constexpr int SEL_BLOCK = 1024;
-constexpr int SEL_MAX_CLASSES = 32;
+constexpr int SEL_BLOCK = 1024;                   // SEL_MAX_CLASSES: pbn_common.h
 
 template <typename T>
 __global__ __launch_bounds__(TPB) void k_sem_argmax_table(const T* __restrict__ score, int ld, int n_cls,

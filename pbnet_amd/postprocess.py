@@ -15,7 +15,10 @@ fold: one pass with a scene axis (csrc/post_batch.hip), the masks as one label p
 
 `refine_tta_merged_device` is that pass WITH the fold, for a merged forward that holds `copies` rotated copies of every scene (the
 reference's evaluation unit, eval_map.py:48-70): the proposals of all copies of a scene are refined together over the scene's own
-points (pbn_post_batch_tta).  Scene table, working tables and results are over folded points."""
+points (pbn_post_batch_tta).  Scene table, working tables and results are over folded points.
+
+`summarize_merged_device` runs behind either merged pass (csrc/summary.hip): the folded semantic label per point and, per kept
+instance, the class its points vote for (eval_map.py:142-155), its box and its centre -- three launches, no read-back."""
 import numpy as np
 import torch
 
@@ -481,3 +484,125 @@ def refine_batch_device(sem_pred_p, proposals, clt_scores, point_starts, superpo
                 raise ValueError("scene %d: superpoints must be %d int64 ids" % (j, point_starts[j + 1] - point_starts[j]))
             merged[point_starts[j]:point_starts[j + 1]].copy_(s.view(-1))
     return refine_merged_device(sem_pred_p, proposals, clt_scores, point_starts, sp_starts, merged, cfg, workspace=ws)
+
+
+# ---- the scene summary: folded semantics, class vote and boxes per kept instance (csrc/summary.hip) ---------------------------------
+STATUS_SUMMARY_CLASS, STATUS_SUMMARY_COORD, STATUS_SUMMARY_INSTANCE = 2, 4, 8       # bits of SceneSummary.status
+MAX_CLASSES = 32                                                                    # SEL_MAX_CLASSES (csrc/pbn_common.h)
+
+
+class SummaryWorkspace(object):
+    """Every buffer `summarize_merged_device` touches, outputs included, sized from capacities: proposals of the merged forward,
+    its FOLDED points, its scenes and the classes of the semantic head.  A call that fits allocates nothing; its results ALIAS
+    these buffers, so the next call on the same workspace overwrites them.  One workspace per stream."""
+
+    def __init__(self, n_prop, n_points_total, n_scenes, n_cls, device):
+        p, n, b, k = max(int(n_prop), 1), max(int(n_points_total), 1), int(n_scenes), int(n_cls)
+        lib = N.lib()
+        if p > lib.pbn_post_max_proposals():
+            raise ValueError("the device form takes at most %d proposals, got %d" % (lib.pbn_post_max_proposals(), p))
+        if not 1 <= b <= MAX_SCENES:
+            raise ValueError("a merged forward holds 1..%d scenes, got %d" % (MAX_SCENES, b))
+        if not 1 <= k <= MAX_CLASSES:
+            raise ValueError("the semantic head has 1..%d classes, got %d" % (MAX_CLASSES, k))
+        self.n_prop, self.n_points_total, self.n_scenes, self.n_cls = p, n, b, k
+        self.device = torch.device(device)
+        self.nbytes = int(lib.pbn_scene_summary_workspace_bytes(p, k))
+        mk = lambda m, dt: torch.zeros(m, dtype=dt, device=self.device)
+        self.buffer = mk(self.nbytes, torch.uint8)
+        self.sem_fold = mk(n, torch.int32)
+        self.class_vote, self.class_points = mk(b * p, torch.int64), mk(b * p, torch.int32)
+        self.box, self.centroid = mk(b * p * 6, torch.float32), mk(b * p * 3, torch.float32)
+        self.status = mk(MAX_SCENES, torch.int32)
+        self.label_table = torch.tensor(SEMANTIC_LABEL_IDX, dtype=torch.int64, device=self.device)
+
+    def fits(self, n_prop, n_points_total, n_scenes, n_cls):
+        return (n_prop <= self.n_prop and n_points_total <= self.n_points_total and n_scenes <= self.n_scenes
+                and n_cls <= self.n_cls)
+
+    def grown_for(self, n_prop, n_points_total, n_scenes, n_cls):
+        """A workspace that fits both this one's capacities and the given sizes (this one when it already does)."""
+        if self.fits(n_prop, n_points_total, n_scenes, n_cls):
+            return self
+        return SummaryWorkspace(max(n_prop, self.n_prop), max(n_points_total, self.n_points_total), max(n_scenes, self.n_scenes),
+                                max(n_cls, self.n_cls), self.device)
+
+
+class SceneSummary(object):
+    """What `summarize_merged_device` leaves on the device for the B scenes of a merged forward with P proposals: sem_fold
+    i32[N] over folded points, class_vote i64[B, P], class_points i32[B, P], box f32[B, P, 6] and centroid f32[B, P, 3] (None
+    without coordinates), status i32[B].  Nothing has been read back; `scene` synchronises only when the caller does not hand
+    the scalars in."""
+
+    def __init__(self, ws, refined, point_starts, with_xyz):
+        self.workspace, self.refined, self.point_starts = ws, refined, list(point_starts)
+        self.n_scenes = b = len(point_starts) - 1
+        self.n_prop = p = refined.n_prop
+        self.sem_fold = ws.sem_fold[:self.point_starts[-1]]
+        self.class_vote, self.class_points = ws.class_vote[:b * p].view(b, p), ws.class_points[:b * p].view(b, p)
+        self.box = ws.box[:b * p * 6].view(b, p, 6) if with_xyz else None
+        self.centroid = ws.centroid[:b * p * 3].view(b, p, 3) if with_xyz else None
+        self.status = ws.status[:b]
+
+    def readback(self):
+        """The 3 B integers `scene` reads: the post-processing's n_keep[B] and status[B], then the summary's status[B] -- one
+        read-back for both passes."""
+        return torch.cat([self.refined.scalars, self.status]).tolist()
+
+    def scene(self, j, scalars=None):
+        """Scene j's summary: dict(sem_fold i32[n_j], class_vote i64[k_j], class_points i32[k_j], box f32[k_j, 6] or None,
+        centroid f32[k_j, 3] or None).  ValueError when scene j's summary status is set (the post-processing's own status is
+        `RefinedBatch.scene`'s to report).  `scalars`: the 3 B integers of `readback()` if the caller has them already."""
+        sc = [int(v) for v in (self.readback() if scalars is None else scalars)]
+        b = self.n_scenes
+        k, status = max(0, min(sc[j], self.n_prop)), sc[2 * b + j]
+        if status & STATUS_SUMMARY_CLASS:
+            raise ValueError("scene %d: the class an instance's points vote for is outside the label table" % j)
+        if status & STATUS_SUMMARY_COORD:
+            raise ValueError("scene %d: a coordinate is NaN or not inside (-32768, 32768)" % j)
+        if status & STATUS_SUMMARY_INSTANCE:
+            raise ValueError("scene %d: a point_instance value is neither -100 nor a kept instance" % j)
+        return dict(sem_fold=self.sem_fold[self.point_starts[j]:self.point_starts[j + 1]], class_vote=self.class_vote[j, :k],
+                    class_points=self.class_points[j, :k], box=None if self.box is None else self.box[j, :k],
+                    centroid=None if self.centroid is None else self.centroid[j, :k])
+
+
+def summarize_merged_device(sem_score, refined_batch, point_starts, copies=1, xyz=None, cfg_labels=None, workspace=None):
+    """The scene summary behind `refine_merged_device` / `refine_tta_merged_device` (pbn_scene_summary): three launches on the
+    current stream, no read-back.  sem_score: the merged forward's `sem_pred_score_p` [copies * N, K] (float32 / bfloat16 /
+    float16, any row stride); refined_batch: the `RefinedBatch` of the same forward (its point_instance and n_keep are read on the
+    device); point_starts: its B + 1 starts over FOLDED points; xyz: float32 [N, 3] in the scenes' own frames, or None (no box, no
+    centre); cfg_labels: the label table as a list, default the one `refine_*_device` uses (the refined batch's own tensor).
+    Returns a `SceneSummary`."""
+    N.require_cuda(sem_score, refined_batch.point_instance, xyz)
+    if sem_score.dim() != 2 or sem_score.dtype not in N.DT or sem_score.stride(1) != 1:
+        raise TypeError("sem_score must be a [rows, classes] float32, bfloat16 or float16 tensor with unit column stride")
+    b, n_total, copies = len(point_starts) - 1, int(point_starts[-1]), int(copies)
+    table = tta_table(point_starts, [0] * (b + 1), copies)
+    n_merged, n_cls = copies * n_total, int(sem_score.shape[1])
+    if int(sem_score.shape[0]) != n_merged:
+        raise ValueError("sem_score holds %d rows, the table %d x %d" % (sem_score.shape[0], copies, n_total))
+    if list(refined_batch.point_starts) != [int(v) for v in point_starts]:
+        raise ValueError("the refined batch was made for another scene table")
+    if xyz is not None and (xyz.dtype != torch.float32 or tuple(xyz.shape) != (n_total, 3)):
+        raise ValueError("xyz must be float32 [%d, 3]" % n_total)
+    n_prop = refined_batch.n_prop
+    ws = workspace
+    if ws is None:
+        ws = SummaryWorkspace(n_prop, n_total, b, n_cls, sem_score.device)
+    elif not ws.fits(n_prop, n_total, b, n_cls):
+        raise ValueError("workspace (%d, %d, %d, %d) does not fit (%d, %d, %d, %d)" % (ws.n_prop, ws.n_points_total, ws.n_scenes,
+                                                                                      ws.n_cls, n_prop, n_total, b, n_cls))
+    if cfg_labels is None:
+        labels = refined_batch.workspace.label_table
+    else:
+        labels = torch.tensor([int(v) for v in cfg_labels], dtype=torch.int64, device=sem_score.device)
+    xyz_c = None if xyz is None else xyz.contiguous()
+    res = SceneSummary(ws, refined_batch, point_starts, xyz is not None)
+    rc = N.lib().pbn_scene_summary(N.c_vp(sem_score.data_ptr()), int(sem_score.stride(0)), n_cls, N.DT[sem_score.dtype], n_merged,
+                                   table, N.ptr(refined_batch.point_instance), N.ptr(refined_batch.scalars), n_prop, N.ptr(xyz_c),
+                                   N.ptr(labels), int(labels.numel()), N.ptr(ws.sem_fold), N.ptr(ws.class_vote),
+                                   N.ptr(ws.class_points), N.ptr(ws.box), N.ptr(ws.centroid), N.ptr(ws.status), N.ptr(ws.buffer),
+                                   ws.nbytes, N.current_stream())
+    N.check(rc, "pbn_scene_summary")
+    return res

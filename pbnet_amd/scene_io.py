@@ -87,3 +87,24 @@ def write_val_gt(npy_dir, gt_dir, scenes):
         sem = np.load(scene_path(npy_dir, scene, "sem_label"))
         ins = np.load(scene_path(npy_dir, scene, "ins_label"))
         save_gt_ids(os.path.join(gt_dir, scene + ".txt"), encode_gt_ids(sem, ins))
+
+
+def write_submission(result_dir, scene_name, point_instance, scores, label_ids):
+    """The benchmark submission files of one scene, as eval_map.py:142-155 writes them: `<result_dir>/<scene>.txt` with one line
+    `predicted_masks/<scene>_%03d.txt <label> %.4f` per instance (no newline after the last) and one 0/1 mask per instance in
+    `<result_dir>/predicted_masks/<scene>_%03d.txt`, a point per line.  point_instance [n]: the instance that owns each point or
+    -100 (the serving front's `instances["point_instance"]`); scores [K]; label_ids [K]: the benchmark label per instance --
+    the reference's writer votes over the instance's points, which is the serving front's `class_vote`.  Host code: tensors are
+    brought to the host here."""
+    to_np = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    point_instance, scores, label_ids = to_np(point_instance).reshape(-1), to_np(scores).reshape(-1), to_np(label_ids).reshape(-1)
+    if scores.shape[0] != label_ids.shape[0]:
+        raise ValueError("scene %s: %d scores, %d labels" % (scene_name, scores.shape[0], label_ids.shape[0]))
+    os.makedirs(os.path.join(result_dir, "predicted_masks"), exist_ok=True)
+    lines = []
+    for k in range(scores.shape[0]):
+        lines.append("predicted_masks/{}_{:03d}.txt {} {:.4f}".format(scene_name, k, int(label_ids[k]), float(scores[k])))
+        np.savetxt(os.path.join(result_dir, "predicted_masks", scene_name + "_%03d.txt" % k), (point_instance == k).astype(np.int32),
+                   fmt="%d")
+    with open(os.path.join(result_dir, scene_name + ".txt"), "w") as f:
+        f.write("\n".join(lines))

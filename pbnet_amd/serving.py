@@ -24,6 +24,13 @@ MAX_SCENES // 3 = 2 waiting units share one forward (6 batch elements), the post
 scene's own points (`postprocess.refine_tta_merged_device`), and `res["instances"]["point_instance"]` has one entry per point of
 the scene, `res["sem_pred_p"]` the unit's 3 n labels.
 
+With `SceneServer(..., refine=cfg, summary=True)` the scene summary (`postprocess.summarize_merged_device`, csrc/summary.hip)
+runs behind the post-processing, ahead of the same read-back: `res["sem_fold"]` holds one label per point of the scene (with tta
+the copies' scores summed in float32, copy after copy, then the first maximum), `res["instances"]` gains `class_vote` and
+`class_points` (the class the instance's points vote for -- what the reference's submission writer records, eval_map.py:142-155
+-- and its count), `box` [K, 6] and `centroid` [K, 3].  Coordinates are `xyz_original` without tta; with tta the unit's optional
+`xyz_scene` (float32 [n, 3], the unrotated scene), and `box` / `centroid` are None for a unit without it.
+
 `merge_scenes` / `split_results` are the two pure functions; `SceneServer` is the small scheduler around them: F worker threads,
 each with its own HIP stream (create the server FIRST in a process: the runtime maps a process's first streams to distinct
 hardware queues), each taking up to `max_batch` waiting scenes per forward -- it never waits for a batch to fill:
@@ -186,7 +193,7 @@ class SceneServer(object):
     """F forwards in flight x up to B scenes per forward.  `submit` returns a Future; `close` drains the queue."""
 
     def __init__(self, model, max_batch=None, forwards_in_flight=2, device=None, epoch=1, split=True, streams=None, refine=None,
-                 paused=False, tta=None):
+                 paused=False, tta=None, summary=False):
         """refine: an object with TEST_SCORE_THRESH, TEST_NPOINT_THRESH and TEST_NMS_THRESH -- every scene's result is then
         dict(sem_pred_p, instances) (module docstring); a scene whose superpoint ids or classes are out of range gets a ValueError
         on its own future, its batch-mates their results.  None (default): the raw forward results, as before.
@@ -196,7 +203,13 @@ class SceneServer(object):
         max_batch: scenes (with tta: units) per forward at most; default 4, with tta min(4, MAX_SCENES // tta).
         tta: copies per submitted unit (the reference evaluates with 3).  `submit` then takes a unit (`merge_tta_units`), a forward
         holds up to MAX_SCENES // tta units, and a unit's result is dict(sem_pred_p [tta * n], instances over the scene's n
-        points), the copies folded in the post-processing -- which is why tta needs refine.  None (default): as before."""
+        points), the copies folded in the post-processing -- which is why tta needs refine.  None (default): as before.
+        summary: every result also carries the scene summary (module docstring); it reads the post-processing's results on the
+        device, so it needs refine.  A scene whose summary status is set (a coordinate that is NaN or outside +-32768, a voted
+        class outside the label table) gets a ValueError on its own future.  False (default): the results are as before."""
+        if summary and refine is None:
+            raise ValueError("summary needs refine: it summarises the instances of the post-processing")
+        self.summary = bool(summary)
         if tta is not None:
             if refine is None:
                 raise ValueError("tta needs refine: the copies are folded in the post-processing")
@@ -265,10 +278,13 @@ class SceneServer(object):
             items.append(nxt)
         return items
 
-    def _refined(self, ret, starts, sup, ws):
+    def _refined(self, ret, starts, sup, ws, xyz=None, has_xyz=None):
         """Post-process the merged result for all its scenes; one read-back.  Returns (per-scene results or exceptions, workspace).
-        The outputs are copied out of the worker's workspace: the next forward of this worker overwrites it."""
+        The outputs are copied out of the worker's workspace: the next forward of this worker overwrites it.  With summary the
+        workspace is the pair (post-processing, summary); xyz: the merged scenes' own coordinates [N, 3] or None, has_xyz: which
+        scenes brought them."""
         n_prop = max(int(ret["proposals"][1].shape[0]) - 1, 0)
+        ws, sws = ws if isinstance(ws, tuple) else (ws, None)
         sizes = (n_prop, starts[-1], len(starts) - 1, sup[1][-1])
         ws = postprocess.PostBatchWorkspace(*sizes, device=self.device) if ws is None else ws.grown_for(*sizes)
         c = 1 if self.tta is None else self.tta     # with tta `starts` are over folded points and unit j holds c copies of them
@@ -280,14 +296,53 @@ class SceneServer(object):
                                                       self.refine, copies=c, workspace=ws)
         rb.point_instance, rb.scores, rb.semantic_id, rb.npoints = (t.clone() for t in (rb.point_instance, rb.scores,
                                                                                         rb.semantic_id, rb.npoints))
-        scalars = rb.scalars.tolist()                                   # the one read-back (it also waits for the forward)
+        if not self.summary:
+            scalars = rb.scalars.tolist()                               # the one read-back (it also waits for the forward)
+            res = []
+            for j in range(len(starts) - 1):
+                try:
+                    res.append(dict(sem_pred_p=ret["sem_pred_p"][c * starts[j]:c * starts[j + 1]], instances=rb.scene(j, scalars)))
+                except ValueError as e:
+                    res.append(e)
+            return res, ws
+        score = ret["sem_pred_score_p"]
+        sizes = (n_prop, starts[-1], len(starts) - 1, int(score.shape[1]))
+        sws = postprocess.SummaryWorkspace(*sizes, device=self.device) if sws is None else sws.grown_for(*sizes)
+        sm = postprocess.summarize_merged_device(score, rb, starts, copies=c, xyz=xyz, workspace=sws)
+        sm.sem_fold, sm.class_vote, sm.class_points = sm.sem_fold.clone(), sm.class_vote.clone(), sm.class_points.clone()
+        if xyz is not None:
+            sm.box, sm.centroid = sm.box.clone(), sm.centroid.clone()
+        scalars = sm.readback()                                         # the one read-back: both passes' scalars, concatenated
         res = []
         for j in range(len(starts) - 1):
             try:
-                res.append(dict(sem_pred_p=ret["sem_pred_p"][c * starts[j]:c * starts[j + 1]], instances=rb.scene(j, scalars)))
+                inst, extra = rb.scene(j, scalars[:2 * rb.n_scenes]), sm.scene(j, scalars)
+                if has_xyz is not None and not has_xyz[j]:
+                    extra["box"] = extra["centroid"] = None
+                inst.update(class_vote=extra["class_vote"], class_points=extra["class_points"], box=extra["box"],
+                            centroid=extra["centroid"])
+                res.append(dict(sem_pred_p=ret["sem_pred_p"][c * starts[j]:c * starts[j + 1]], sem_fold=extra["sem_fold"],
+                                instances=inst))
             except ValueError as e:
                 res.append(e)
-        return res, ws
+        return res, (ws, sws)
+
+    def _unit_coordinates(self, units, starts):
+        """The folded points' own coordinates for the summary of a tta forward: (float32 [N, 3] or None, which units brought
+        `xyz_scene`).  A unit without it gets zeros, and no box."""
+        has = [u.get("xyz_scene") is not None for u in units]
+        if not self.summary or not any(has):
+            return None, has
+        parts = []
+        for j, u in enumerate(units):
+            n = starts[j + 1] - starts[j]
+            if has[j]:
+                if u["xyz_scene"].dtype != torch.float32 or tuple(u["xyz_scene"].shape) != (n, 3):
+                    raise ValueError("unit %d: `xyz_scene` must be float32 [%d, 3]" % (j, n))
+                parts.append(u["xyz_scene"])
+            else:
+                parts.append(torch.zeros(n, 3, dtype=torch.float32, device=self.device))
+        return (parts[0] if len(parts) == 1 else torch.cat(parts)).contiguous(), has
 
     def _forward_tta(self, items, ws):
         """One merged forward of up to MAX_SCENES // tta units; returns (per-unit results or exceptions, workspace)."""
@@ -297,7 +352,8 @@ class SceneServer(object):
             ret = self.model(batch["feat_voxel"], batch["xyz_voxel"], batch["xyz_original"], batch["v2p_index"], None, self.epoch,
                              "test", teacher=batch["teacher"], n_batch=t * len(items))
         if "proposals" in ret:
-            return self._refined(ret, starts, sup, ws)
+            xyz, has = self._unit_coordinates([it[0] for it in items], starts)
+            return self._refined(ret, starts, sup, ws, xyz, has)
         return [dict(sem_pred_p=ret["sem_pred_p"][t * starts[j]:t * starts[j + 1]]) for j in range(len(items))], ws
 
     def _worker(self, stream):
@@ -322,7 +378,7 @@ class SceneServer(object):
                             ret = self.model(batch["feat_voxel"], batch["xyz_voxel"], batch["xyz_original"], batch["v2p_index"], None,
                                              self.epoch, "test", teacher=teacher, n_batch=len(items))
                         if self.refine is not None and "proposals" in ret:
-                            res, ws = self._refined(ret, starts, sup, ws)
+                            res, ws = self._refined(ret, starts, sup, ws, batch["xyz_original"] if self.summary else None)
                         elif self.split:
                             res = split_results(ret, starts)
                         else:
