@@ -710,6 +710,42 @@ int pbn_ap_record_append(int32_t* state, int32_t* log, int64_t log_words, int sc
                          const int32_t* uid, const int32_t* gt_vert, const int64_t* semantic_id, const float* conf,
                          const int32_t* inter, pbn_stream_t stream);
 
+/* The same association for ALL scenes of one merged forward (csrc/apassoc_batch.hip; AssociationLog.append_batch), on what
+ * pbn_post_batch[_tta] leaves: one label per folded point, no dense [P, n] table.  `units` is the table of that pass (copies = 1:
+ * the plain merged forward; B = units.n_scenes, everything here is over FOLDED points, scene j owns point_start[j] ..
+ * point_start[j + 1], N = point_start[B]); point_instance int32[N], post_scalars (n_keep[B], status[B]), scores f32[B, P] and
+ * semantic_id int64[B, P] are its outputs, left on the device (P = n_prop).  Ground truth over the same N points: `ids` (int32 or
+ * int64 per ids_i64), or ids = NULL and a (sem, ins) pair with label_table[n_labels], encoded per scene as pbn_gt_encode_dev does
+ * (the lowest point of an instance is the lowest within its scene).
+ * Per scene j, in the order 0 .. B - 1, the log receives exactly the record that pbn_gt_encode_dev (optional), pbn_gt_index_dev,
+ * pbn_instance_overlap_dev on the densified labels (row k = the points with point_instance == k) and pbn_ap_record_append write:
+ * same layout, header words, magic, n_pts = n_j, scene_tag = tags.tag[j], the same used | wanted | n_records | overflow | last
+ * offset state machine with the sticky overflow (wanted always advances, the records before the overflow are whole, none after it
+ * is written), status = post_scalars[B + j] ORed with this pass's bits 4 / 8 / 16 / 32 / 64.  n_keep[j] is clamped as
+ * pbn_scene_summary does (the scenes' counts sum to at most P); n_keep[j] == 0 gives the header alone.  A point counts for
+ * inter[k][g] only when its label k lies in [0, n_keep[j]) and its id has a slot g >= 0; -100 and every other label outside that
+ * range count for no prediction and are no error here.
+ * Six launches whatever B is (eight with the (sem, ins) form; four / six when n_prop == 0, which is served: B header-only
+ * records), no read-back, grids sized by capacity, integer atomics only (two runs give the same log bytes).  One direct table per
+ * scene (B x id_cap words, id_cap <= 2^20), walked in ascending id order by one workgroup per scene; uid, gt_vert and n_gt per
+ * scene in the workspace.  The overlap counters are the record's own inter words: a workgroup keeps the counters of the scene of
+ * its first point in LDS when n_keep * n_gt <= pbn_ap_assoc_batch_lds_counters() and adds to the record directly otherwise, as
+ * do its lanes beyond a scene boundary.  pbn_ap_assoc_batch_workspace_bytes(N, B, u_cap, id_cap, n_inst_cap): n_inst_cap = 0 sizes
+ * it for the `ids` form only; 0 for sizes outside the supported range.
+ * All before any launch: PBN_ERR_ARG for a table that is not as stated, B * copies > PBN_MAX_SCENES, a missing pointer, neither
+ * form of the ground truth, or a capacity below 1; PBN_ERR_UNSUPPORTED above pbn_post_max_proposals() proposals or with id_cap >
+ * 2^20; PBN_ERR_RANGE for log_words >= 2^31; PBN_ERR_WORKSPACE for a workspace that is too small. */
+typedef struct pbn_ap_scene_tags {
+    int32_t tag[PBN_MAX_SCENES];
+} pbn_ap_scene_tags;
+size_t pbn_ap_assoc_batch_workspace_bytes(int n_points_total, int n_scenes, int u_cap, int id_cap, int n_inst_cap);
+int pbn_ap_assoc_batch_lds_counters(void);
+int pbn_ap_assoc_batch(pbn_tta_table units, const int32_t* point_instance, const int32_t* post_scalars, const float* scores,
+                       const int64_t* semantic_id, int n_prop, const void* ids, int ids_i64, const void* sem, int sem_i64,
+                       const void* ins, int ins_i64, const int32_t* label_table, int n_labels, int u_cap, int id_cap,
+                       int n_inst_cap, pbn_ap_scene_tags tags, int32_t* state, int32_t* log, int64_t log_words, void* workspace,
+                       size_t workspace_bytes, pbn_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * One-call sub-pipelines (csrc/executor.hip): they only sequence the entry points above.
  *

@@ -103,6 +103,11 @@ class TtaTable(ctypes.Structure):
                 ("sp_start", c_i32 * (MAX_SCENES + 1))]
 
 
+class SceneTags(ctypes.Structure):
+    """pbn_ap_scene_tags (include/pbnet_hip.h)."""
+    _fields_ = [("tag", c_i32 * MAX_SCENES)]
+
+
 class PostBatchLayout(ctypes.Structure):
     """pbn_post_batch_layout (include/pbnet_hip.h)."""
     _fields_ = [(k, c_i64) for k in ("masks", "counts", "prop_scene", "score", "rows", "pick_rows", "n_rows", "n_pick", "iou",
@@ -183,6 +188,10 @@ SIGNATURES = {
     "pbn_instance_overlap_dev": (c_int, [c_i32p, c_i32p, c_int, c_int, c_i32p, c_i32p, c_int, c_i32p, c_vp]),
     "pbn_ap_record_append": (c_int, [c_i32p, c_i32p, c_i64, c_int, c_i32p, c_int, c_i32p, c_int, c_int, c_i32p, c_i32p, c_i32p,
                                      c_i32p, c_vp, c_f32p, c_i32p, c_vp]),
+    "pbn_ap_assoc_batch_workspace_bytes": (c_size, [c_int, c_int, c_int, c_int, c_int]),
+    "pbn_ap_assoc_batch_lds_counters": (c_int, []),
+    "pbn_ap_assoc_batch": (c_int, [TtaTable, c_i32p, c_i32p, c_f32p, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_i32p,
+                                   c_int, c_int, c_int, c_int, SceneTags, c_i32p, c_i32p, c_i64, c_vp, c_size, c_vp]),
     "pbn_rulebook_pair_blocks": (c_int, [c_int]),
     "pbn_bn_workspace_bytes": (c_size, [c_int]),
     "pbn_bn_train_forward": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_f32p, c_f32p, ctypes.c_float, ctypes.c_float, c_f32p,

@@ -197,13 +197,11 @@ AP_STATUS = ((1, "a superpoint id is >= n_superpoints"),
 AP_STATUS_ID_RANGE, AP_STATUS_ID_COUNT, AP_STATUS_LABEL_RANGE, AP_STATUS_INSTANCE_CAP, AP_STATUS_SEMANTIC_RANGE = 4, 8, 16, 32, 64
 
 
-def decode_association_log(words, names):
-    """Walk the records of an association log (int32 words as `AssociationLog` leaves them; `names[tag]` = scene name).
-    Returns ({scene: SceneMatches} in log order, [names of the scenes without a cluster]): a record with n_keep == 0 yields no
-    entry, as train.py:217-219 skips such a scene (tools/eval.py would count its ground-truth instances as misses: run
-    assign_instances_for_scan for those names where that is wanted).  ValueError with the scene's name and the reason for any status bit."""
+def _walk_association_log(words, names):
+    """Generator over the records of an association log in log order: (tag, scene name, reasons of its status bits, SceneMatches
+    or None for a header-only record).  ValueError for a log that is not a sequence of whole records."""
     words = np.ascontiguousarray(words, dtype=np.int32).reshape(-1)
-    matches, dropped, pos, end = {}, [], 0, int(words.shape[0])
+    pos, end = 0, int(words.shape[0])
     while pos < end:
         if end - pos < AP_RECORD_HEADER or int(words[pos]) != AP_RECORD_MAGIC:
             raise ValueError("the association log has no record header at word %d" % pos)
@@ -216,19 +214,45 @@ def decode_association_log(words, names):
         reasons = [text for bit, text in AP_STATUS if status & bit]
         if status & ~sum(bit for bit, _ in AP_STATUS):
             reasons.append("unknown status bits 0x%x" % status)
-        if reasons:
-            raise ValueError("%s: %s" % (scene, "; ".join(reasons)))
-        if n_keep == 0:
-            dropped.append(scene)
-        else:
+        rec = None
+        if n_keep and not reasons:
             body = words[pos + AP_RECORD_HEADER:pos + size]
             uid, vert = body[:n_gt].astype(np.int64), body[n_gt:2 * n_gt].astype(np.int64)
             label_id = body[2 * n_gt:2 * n_gt + n_keep].astype(np.int64)
             conf = body[2 * n_gt + n_keep:2 * n_gt + 2 * n_keep].copy().view(np.float32)
             inter_all = body[2 * n_gt + 2 * n_keep:].astype(np.int64).reshape(n_keep, n_gt)
-            matches[scene] = matches_from_table(scene, inter_all, uid, vert, label_id, conf)
+            rec = matches_from_table(scene, inter_all, uid, vert, label_id, conf)
+        yield tag, scene, reasons, rec
         pos += size
-    return matches, dropped
+
+
+def _sort_records(records, on_status):
+    """(matches, dropped[, failed]) from walked records, in the order given."""
+    if on_status not in ("raise", "skip"):
+        raise ValueError("on_status must be 'raise' or 'skip', got %r" % (on_status,))
+    matches, dropped, failed = {}, [], []
+    for _, scene, reasons, rec in records:
+        if reasons:
+            if on_status == "raise":
+                raise ValueError("%s: %s" % (scene, "; ".join(reasons)))
+            failed.append((scene, reasons))
+        elif rec is None:
+            dropped.append(scene)
+        else:
+            matches[scene] = rec
+    return (matches, dropped) if on_status == "raise" else (matches, dropped, failed)
+
+
+def decode_association_log(words, names, on_status="raise"):
+    """Walk the records of an association log (int32 words as `AssociationLog` leaves them; `names[tag]` = scene name).
+    Returns ({scene: SceneMatches} in log order, [names of the scenes without a cluster]): a record with n_keep == 0 yields no
+    entry, as train.py:217-219 skips such a scene (tools/eval.py would count its ground-truth instances as misses: run
+    assign_instances_for_scan for those names where that is wanted).  ValueError with the scene's name and the reason for any status bit.
+    on_status="skip": a scene with status bits is left out of the matches instead and returned in a third list of
+    (name, reasons), so one bad scene does not cost the epoch."""
+    if on_status not in ("raise", "skip"):
+        raise ValueError("on_status must be 'raise' or 'skip', got %r" % (on_status,))
+    return _sort_records(_walk_association_log(words, names), on_status)
 
 
 class AssociationLog(object):
@@ -258,6 +282,8 @@ class AssociationLog(object):
         self.p_cap = self.n_pts_cap = 0
         self.inter = self.gt_index = self.ids = None
         self._grow(p_cap, n_pts_cap)
+        self.batch_ws = self.batch_gt = None                          # append_batch's buffers, made by its first call
+        self.batch_n_cap = self.batch_ws_bytes = 0
         self.names = []
 
     def _grow(self, p_cap, n_pts_cap):
@@ -325,14 +351,103 @@ class AssociationLog(object):
         """`append` on what postprocess.refine_instances_device left: its capacity-sized views and device scalars."""
         self.append(name, refined.clusters, refined.scores, refined.semantic_id, refined.n_keep, refined.status, gt)
 
-    def collect(self):
-        """The single read-back of the epoch: the state block, then the used part of the log.  Returns what
-        `decode_association_log` returns; RuntimeError when a record did not fit, with the word count the epoch wanted."""
+    def _grow_batch(self, n_total):
+        """The buffers of `append_batch`: the workspace of pbn_ap_assoc_batch for MAX_SCENES scenes and two int64 rows for the
+        concatenated ground truth.  They grow only, when a call does not fit."""
+        if self.batch_ws is not None and n_total <= self.batch_n_cap:
+            return
+        n = max(int(n_total), self.batch_n_cap, 1)
+        nbytes = int(N.lib().pbn_ap_assoc_batch_workspace_bytes(n, N.MAX_SCENES, self.u_cap, self.id_cap, self.n_inst_cap))
+        if nbytes == 0:
+            raise ValueError("no workspace for %d points with u_cap %d, id_cap %d, n_inst_cap %d" % (n, self.u_cap, self.id_cap,
+                                                                                                    self.n_inst_cap))
+        self.batch_ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        self.batch_gt = torch.zeros(2, n, dtype=torch.int64, device=self.device)
+        self.batch_n_cap, self.batch_ws_bytes = n, nbytes
+
+    def append_batch(self, names, refined_batch, gts=None, copies=1, ids=None, sem=None, ins=None, tags=None):
+        """Enqueue ALL scenes of one merged forward from what the batched post-processing left on the device (a
+        `postprocess.RefinedBatch`: one label per folded point, no dense table): pbn_ap_assoc_batch, six launches whatever the
+        number of scenes (eight with (sem, ins) pairs), B records appended in scene order.  The records are the ones `append`
+        writes for `refined_batch.dense(j)`, byte for byte, so `collect` decodes them as before.
+
+        names: one per scene.  gts: per scene a device id vector [n_j] (int32 / int64) or a (sem, ins) pair of device label
+        vectors [n_j] -- the same form for every scene; they are concatenated into a buffer of this log (no allocation once it
+        fits).  Or gts=None and the merged tensors over all N folded points directly: `ids=`, or `sem=` and `ins=`.
+        copies: the copies of a scene in the merged forward (`refine_tta_merged_device`); the points here are the folded ones.
+        tags: the records' scene tags, default the names' positions in `self.names`, which is what `collect` decodes with.
+        Does not synchronise and reads nothing back."""
+        rb = refined_batch
+        b, starts, n_prop = rb.n_scenes, [int(v) for v in rb.point_starts], int(rb.n_prop)
+        n_total = starts[-1]
+        names = list(names)
+        if len(names) != b:
+            raise ValueError("%d names for %d scenes" % (len(names), b))
+        tags = [len(self.names) + j for j in range(b)] if tags is None else [int(t) for t in tags]
+        if len(tags) != b:
+            raise ValueError("%d tags for %d scenes" % (len(tags), b))
+        N.require_cuda(rb.point_instance, rb.scalars, rb.scores, rb.semantic_id)
+        if (rb.point_instance.dtype != torch.int32 or rb.scores.dtype != torch.float32 or rb.semantic_id.dtype != torch.int64
+                or rb.scalars.dtype != torch.int32 or int(rb.scalars.numel()) < 2 * b):
+            raise TypeError("refined_batch must hold int32 point_instance and scalars, float32 scores and int64 semantic_id")
+        if int(rb.point_instance.numel()) != n_total or int(rb.scores.numel()) != b * n_prop or int(rb.semantic_id.numel()) != b * n_prop:
+            raise ValueError("refined_batch does not have the shapes of its scene table")
+        self._grow_batch(n_total)
+        if gts is not None:
+            if ids is not None or sem is not None or ins is not None or len(gts) != b:
+                raise ValueError("gts holds one entry per scene (%d) and excludes ids= / sem= / ins=" % b)
+            pairs = [isinstance(g, (tuple, list)) for g in gts]
+            if any(pairs) != all(pairs):
+                raise ValueError("every scene of a call brings the same form of ground truth: ids or a (sem, ins) pair")
+            rows = []
+            for r in range(2 if pairs[0] else 1):
+                parts = [self._labels(g[r] if pairs[0] else g, ("sem", "ins")[r] if pairs[0] else "gt", starts[j + 1] - starts[j])
+                         for j, g in enumerate(gts)]
+                if b == 1:
+                    rows.append(parts[0])
+                    continue
+                for j, t in enumerate(parts):
+                    self.batch_gt[r, starts[j]:starts[j + 1]].copy_(t)
+                rows.append(self.batch_gt[r, :n_total])
+            ids, sem, ins = (None, rows[0], rows[1]) if pairs[0] else (rows[0], None, None)
+        elif ids is not None:
+            if sem is not None or ins is not None:
+                raise ValueError("ids= excludes sem= / ins=")
+            ids = self._labels(ids, "ids", n_total)
+        elif sem is not None and ins is not None:
+            sem, ins = self._labels(sem, "sem", n_total), self._labels(ins, "ins", n_total)
+        else:
+            raise ValueError("append_batch needs ground truth: gts, ids= or sem= and ins=")
+        table = N.TtaTable()
+        table.n_scenes, table.copies = b, int(copies)
+        for j in range(b + 1):
+            table.point_start[j], table.sp_start[j] = starts[j], 0
+        st = N.SceneTags()
+        for j in range(b):
+            st.tag[j] = tags[j]
+        pi, sc = rb.point_instance.contiguous(), rb.scalars.contiguous()
+        scores, sid = rb.scores.contiguous(), rb.semantic_id.contiguous()
+        i64 = lambda t: int(t is not None and t.dtype == torch.int64)                                  # noqa: E731
+        N.check(N.lib().pbn_ap_assoc_batch(table, N.ptr(pi), N.ptr(sc), N.ptr(scores), N.ptr(sid), n_prop, N.ptr(ids), i64(ids),
+                                           N.ptr(sem), i64(sem), N.ptr(ins), i64(ins), N.ptr(self.label_table),
+                                           int(self.label_table.numel()), self.u_cap, self.id_cap, self.n_inst_cap, st,
+                                           N.ptr(self.state), N.ptr(self.log), self.log_words, N.ptr(self.batch_ws),
+                                           self.batch_ws_bytes, N.current_stream()), "pbn_ap_assoc_batch")
+        self.names.extend(names)
+
+    def read_log(self):
+        """The read-back behind `collect`: the used words of the log as a host array; RuntimeError when a record did not fit,
+        with the word count the epoch wanted."""
         used, wanted, n_records, overflow = self.state[:4].tolist()
         if overflow:
             raise RuntimeError("the association log overflowed: %d of %d scenes fit in log_words = %d, the epoch wanted %d words"
                                % (n_records, len(self.names), self.log_words, wanted))
-        return decode_association_log(self.log[:used].cpu().numpy(), self.names)
+        return self.log[:used].cpu().numpy()
+
+    def collect(self, on_status="raise"):
+        """The single read-back of the epoch: the state block, then the used part of the log.  Returns what
+        `decode_association_log` returns; RuntimeError when a record did not fit, with the word count the epoch wanted."""
+        return decode_association_log(self.read_log(), self.names, on_status)
 
 
 def _word_ptr(t, i):
@@ -442,6 +557,36 @@ def compute_averages(aps):
         avg["classes"][name] = {"ap": np.average(aps[0, li, rest]), "ap50%": np.average(aps[0, li, o50]),
                                 "ap25%": np.average(aps[0, li, o25])}
     return avg
+
+
+def evaluate_served(server_or_model, units, cfg, logger=None, tta=3):
+    """eval_map.py:40-158 on the serving front: every unit is submitted with its ground truth, the front post-processes and
+    associates on the device (`SceneServer(..., refine=cfg, association=True)`), and the epoch ends in `evaluate_matches`,
+    `compute_averages` and `print_results`.  `units`: (name, unit, gt) triples -- `unit` what `SceneServer.submit` takes (with tta
+    the reference's evaluation unit of `tta` rotated copies), `gt` a device id vector over the scene's own points or a (sem, ins)
+    pair.  `server_or_model`: a paused or running `SceneServer` built with association=True (it is closed here), or a model, for
+    which one is made with refine=cfg and `tta` copies per unit (None: plain scenes).  Scenes without a kept instance are
+    reported and left out (eval_map.py:102-104), as are scenes whose result or record reports an error.  Returns the averages."""
+    from .serving import SceneServer
+    say = print if logger is None else logger.info
+    server = server_or_model
+    if not isinstance(server, SceneServer):
+        server = SceneServer(server_or_model, refine=cfg, tta=tta, association=True)
+    if not getattr(server, "association_on", False):
+        raise ValueError("evaluate_served needs a SceneServer built with association=True")
+    futs = [(name, server.submit(unit, gt=gt, name=name)) for name, unit, gt in units]
+    server.close()
+    for name, f in futs:
+        if f.exception() is not None:
+            say("%s: not served: %s" % (name, f.exception()))
+    matches, dropped, failed = server.association()
+    for name in dropped:
+        say("%s: no instance kept, left out" % (name,))
+    for name, reasons in failed:
+        say("%s: left out: %s" % (name, "; ".join(reasons)))
+    avgs = compute_averages(evaluate_matches(matches))
+    print_results(avgs, logger)
+    return avgs
 
 
 def format_results(avgs):

@@ -31,6 +31,13 @@ the copies' scores summed in float32, copy after copy, then the first maximum), 
 -- and its count), `box` [K, 6] and `centroid` [K, 3].  Coordinates are `xyz_original` without tta; with tta the unit's optional
 `xyz_scene` (float32 [n, 3], the unrotated scene), and `box` / `centroid` are None for a unit without it.
 
+With `SceneServer(..., refine=cfg, association=True)` the front scores its own output: every submission brings its ground truth
+(`submit(scene, gt=ids)` or `gt=(sem, ins)`, device vectors over the scene's own points), and behind the post-processing of a
+merged forward the AP association of all its scenes is enqueued on the worker's stream (`evaluate.AssociationLog.append_batch`,
+csrc/apassoc_batch.hip: six launches per forward, nothing read back).  Results are unchanged; after `close()`,
+`server.association()` reads every worker's log once and returns `(matches, dropped, failed)` in submission order, ready for
+`evaluate.evaluate_matches` -- `evaluate.evaluate_served` is the whole of eval_map.py:40-158 on this front.
+
 `merge_scenes` / `split_results` are the two pure functions; `SceneServer` is the small scheduler around them: F worker threads,
 each with its own HIP stream (create the server FIRST in a process: the runtime maps a process's first streams to distinct
 hardware queues), each taking up to `max_batch` waiting scenes per forward -- it never waits for a batch to fill:
@@ -42,7 +49,7 @@ from concurrent.futures import Future
 
 import torch
 
-from . import postprocess
+from . import evaluate, postprocess
 from ._native import MAX_SCENES
 
 
@@ -193,7 +200,7 @@ class SceneServer(object):
     """F forwards in flight x up to B scenes per forward.  `submit` returns a Future; `close` drains the queue."""
 
     def __init__(self, model, max_batch=None, forwards_in_flight=2, device=None, epoch=1, split=True, streams=None, refine=None,
-                 paused=False, tta=None, summary=False):
+                 paused=False, tta=None, summary=False, association=False):
         """refine: an object with TEST_SCORE_THRESH, TEST_NPOINT_THRESH and TEST_NMS_THRESH -- every scene's result is then
         dict(sem_pred_p, instances) (module docstring); a scene whose superpoint ids or classes are out of range gets a ValueError
         on its own future, its batch-mates their results.  None (default): the raw forward results, as before.
@@ -206,7 +213,16 @@ class SceneServer(object):
         points), the copies folded in the post-processing -- which is why tta needs refine.  None (default): as before.
         summary: every result also carries the scene summary (module docstring); it reads the post-processing's results on the
         device, so it needs refine.  A scene whose summary status is set (a coordinate that is NaN or outside +-32768, a voted
-        class outside the label table) gets a ValueError on its own future.  False (default): the results are as before."""
+        class outside the label table) gets a ValueError on its own future.  False (default): the results are as before.
+        association: True, or a dict of `evaluate.AssociationLog` capacities (u_cap, id_cap, n_inst_cap, log_words): every
+        submission brings `gt`, every worker appends the records of its forwards to a log of its own (one log per stream) with
+        the GLOBAL submission number as the tag, and `association()` merges them after `close()`.  It reads the
+        post-processing's results on the device, so it needs refine; it adds no read-back.  False (default): as before."""
+        if association and refine is None:
+            raise ValueError("association needs refine: it scores the instances of the post-processing")
+        self.association_on = bool(association)
+        self._assoc_kw = dict(association) if isinstance(association, dict) else {}
+        self._logs, self._names, self._unserved, self._gt_pairs = [], [], [], None
         if summary and refine is None:
             raise ValueError("summary needs refine: it summarises the instances of the post-processing")
         self.summary = bool(summary)
@@ -244,14 +260,60 @@ class SceneServer(object):
         for t in self._threads:
             t.start()
 
-    def submit(self, scene, teacher=None):
+    def _gt_problem(self, scene, gt):
+        """Why `gt` cannot be the ground truth of `scene` (None when it can): host checks only."""
+        n = int(scene["xyz_original"].shape[0]) // (1 if self.tta is None else self.tta)
+        parts = list(gt) if isinstance(gt, (tuple, list)) else [gt]
+        if gt is None or len(parts) not in (1, 2) or (len(parts) == 1 and isinstance(gt, (tuple, list))):
+            return "association needs `gt`: a device id vector or a (sem, ins) pair over the scene's %d points" % n
+        for t in parts:
+            if (not torch.is_tensor(t) or not t.is_cuda or t.dtype not in (torch.int32, torch.int64) or t.dim() != 1
+                    or int(t.shape[0]) != n):
+                return "`gt` must hold int32 or int64 device vectors of the scene's %d points" % n
+        with self._lock:                        # a merged forward takes one form of ground truth: the first submission sets it
+            if self._gt_pairs is None:
+                self._gt_pairs = len(parts) == 2
+        if self._gt_pairs != (len(parts) == 2):
+            return "every submission of a server brings the same form of `gt`: id vectors or (sem, ins) pairs"
+        return None
+
+    def submit(self, scene, teacher=None, gt=None, name=None):
+        """Queue one scene (with tta: one unit); returns its Future.  gt / name: with association, the scene's ground truth and
+        the name of its record (default: the submission number); a submission whose `gt` is missing or not over the scene's own
+        points gets a ValueError on its future and is not served."""
         if self._closed:
             raise RuntimeError("SceneServer is closed")
         f = Future()
+        number = None
+        if self.association_on:
+            with self._lock:
+                number = len(self._names)
+                self._names.append(number if name is None else name)
+            problem = self._gt_problem(scene, gt)
+            if problem is not None:
+                with self._lock:
+                    self._unserved.append((number, problem))
+                f.set_exception(ValueError("submission %r: %s" % (self._names[number], problem)))
+                return f
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))        # the scene's tensors are ready when the submitting stream gets here
-        self._q.put((scene, teacher, f, ev))
+        self._q.put((scene, teacher, f, ev, gt, number))
         return f
+
+    def association(self):
+        """After `close()`: (matches, dropped, failed) of everything served with association=True -- what
+        `evaluate.decode_association_log(..., on_status="skip")` returns, over the records of ALL workers merged in submission
+        order, so the AP does not depend on how scenes were batched or which worker took them.  `failed` also lists the
+        submissions that were refused for their `gt`.  Reads each worker's log once; RuntimeError when a log overflowed."""
+        if not self.association_on:
+            raise ValueError("this server was built without association=True")
+        if not self._closed or any(t.is_alive() for t in self._threads):
+            raise RuntimeError("association() reads the logs after close()")
+        records = [(number, self._names[number], [problem], None) for number, problem in self._unserved]
+        for log in self._logs:
+            records += list(evaluate._walk_association_log(log.read_log(), self._names))
+        records.sort(key=lambda r: r[0])
+        return evaluate._sort_records(records, "skip")
 
     def close(self):
         self._closed = True
@@ -278,7 +340,13 @@ class SceneServer(object):
             items.append(nxt)
         return items
 
-    def _refined(self, ret, starts, sup, ws, xyz=None, has_xyz=None):
+    def _associate(self, rb, copies, assoc):
+        """Enqueue the association of a merged forward's scenes behind its post-processing: no read-back."""
+        if assoc is not None:
+            log, names, gts, numbers = assoc
+            log.append_batch(names, rb, gts, copies=copies, tags=numbers)
+
+    def _refined(self, ret, starts, sup, ws, xyz=None, has_xyz=None, assoc=None):
         """Post-process the merged result for all its scenes; one read-back.  Returns (per-scene results or exceptions, workspace).
         The outputs are copied out of the worker's workspace: the next forward of this worker overwrites it.  With summary the
         workspace is the pair (post-processing, summary); xyz: the merged scenes' own coordinates [N, 3] or None, has_xyz: which
@@ -294,6 +362,7 @@ class SceneServer(object):
         else:
             rb = postprocess.refine_tta_merged_device(ret["sem_pred_p"], ret["proposals"], ret["clt_scores"], starts, sup[1], sup[0],
                                                       self.refine, copies=c, workspace=ws)
+        self._associate(rb, c, assoc)
         rb.point_instance, rb.scores, rb.semantic_id, rb.npoints = (t.clone() for t in (rb.point_instance, rb.scores,
                                                                                         rb.semantic_id, rb.npoints))
         if not self.summary:
@@ -344,7 +413,7 @@ class SceneServer(object):
                 parts.append(torch.zeros(n, 3, dtype=torch.float32, device=self.device))
         return (parts[0] if len(parts) == 1 else torch.cat(parts)).contiguous(), has
 
-    def _forward_tta(self, items, ws):
+    def _forward_tta(self, items, ws, assoc=None):
         """One merged forward of up to MAX_SCENES // tta units; returns (per-unit results or exceptions, workspace)."""
         t = self.tta
         batch, starts, sup = merge_tta_units([it[0] for it in items], t, [it[1] for it in items])
@@ -353,12 +422,13 @@ class SceneServer(object):
                              "test", teacher=batch["teacher"], n_batch=t * len(items))
         if "proposals" in ret:
             xyz, has = self._unit_coordinates([it[0] for it in items], starts)
-            return self._refined(ret, starts, sup, ws, xyz, has)
+            return self._refined(ret, starts, sup, ws, xyz, has, assoc)
         return [dict(sem_pred_p=ret["sem_pred_p"][t * starts[j]:t * starts[j + 1]]) for j in range(len(items))], ws
 
     def _worker(self, stream):
         torch.cuda.set_device(self.device)
         ws = None                               # this worker's post-processing workspace (refine), grown when a batch does not fit
+        alog = None                             # this worker's association log (association), made with its first forward
         with torch.cuda.stream(stream):
             while True:
                 items = self._take()
@@ -366,10 +436,17 @@ class SceneServer(object):
                     return
                 futs = [it[2] for it in items]
                 try:
+                    assoc = None
+                    if self.association_on:
+                        if alog is None:                # this worker's log: one log per stream
+                            alog = evaluate.AssociationLog(1, 1, device=self.device, **self._assoc_kw)
+                            with self._lock:
+                                self._logs.append(alog)
+                        assoc = (alog, [self._names[it[5]] for it in items], [it[4] for it in items], [it[5] for it in items])
                     for it in items:
                         stream.wait_event(it[3])
                     if self.tta is not None:
-                        res, ws = self._forward_tta(items, ws)
+                        res, ws = self._forward_tta(items, ws, assoc)
                     else:
                         merged = merge_scenes([it[0] for it in items], [it[1] for it in items],
                                               with_superpoints=self.refine is not None)
@@ -378,7 +455,8 @@ class SceneServer(object):
                             ret = self.model(batch["feat_voxel"], batch["xyz_voxel"], batch["xyz_original"], batch["v2p_index"], None,
                                              self.epoch, "test", teacher=teacher, n_batch=len(items))
                         if self.refine is not None and "proposals" in ret:
-                            res, ws = self._refined(ret, starts, sup, ws, batch["xyz_original"] if self.summary else None)
+                            res, ws = self._refined(ret, starts, sup, ws, batch["xyz_original"] if self.summary else None,
+                                                    assoc=assoc)
                         elif self.split:
                             res = split_results(ret, starts)
                         else:
