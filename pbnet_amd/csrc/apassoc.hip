@@ -5,40 +5,18 @@
 // sized by capacity or fixed and striding, and work past the live count leaves.  Integer atomics only: every result is
 // bit-identical from run to run.
 #include "pbn_common.h"
+#include "assoc_dev.h"
 
 namespace pbn {
 namespace {
 
-constexpr int TPB = 256;
-constexpr int STRIDE_BLOCKS = 2048;                 // cap of every striding grid
-constexpr int GT_ID_CAP_MAX = 1 << 20;              // direct table of pbn_gt_index_dev
-constexpr int SCAN_IDS = 4;                         // ids per thread and trip of k_gt_scan
-constexpr int OVERLAP_CHUNK = 4096;                 // as k_instance_overlap (post.hip)
+constexpr int TPB = POST_TPB;
+constexpr int OVERLAP_CHUNK = 4096;                 // points per workgroup of k_instance_overlap_dev
 constexpr int OVERLAP_LDS_BINS = 8192;
-constexpr int HDR = PBN_AP_RECORD_HEADER;
-// state block of the log: used | wanted | n_records | overflow | offset of the record being written (-1 = none) | 3 spare
-constexpr int ST_USED = 0, ST_WANTED = 1, ST_RECORDS = 2, ST_OVERFLOW = 3, ST_OFFSET = 4;
-
-__device__ __forceinline__ long long load_label(const void* p, int i64, long long i) {
-    return i64 ? ((const long long*)p)[i] : (long long)((const int*)p)[i];
-}
 
 __device__ __forceinline__ int live_count(const int* dev, int cap) {
     const int n = dev ? *dev : cap;
     return n < 0 ? 0 : (n > cap ? cap : n);
-}
-
-// one add per distinct bin of a wave: lanes that hit the same bin are merged first (the leader adds the lane count), as in
-// k_instance_overlap.  Every lane of the wave must call this; bin < 0 takes no part.
-__device__ __forceinline__ void wave_merged_add(int* bins, int bin) {
-    unsigned long long todo = __ballot(bin >= 0);
-    while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const int lb = __shfl(bin, leader);
-        const unsigned long long same = __ballot(bin == lb) & todo;
-        if (lane_id() == leader) atomicAdd(&bins[lb], __popcll(same));
-        todo &= ~same;
-    }
 }
 
 __global__ __launch_bounds__(TPB) void k_fill_i32(int* __restrict__ p, int n, int value) {
@@ -50,27 +28,26 @@ __global__ __launch_bounds__(TPB) void k_fill_i32(int* __restrict__ p, int n, in
 __global__ __launch_bounds__(TPB) void k_gt_first(const void* __restrict__ ins, int ins_i64, int n_pts, int n_inst_cap,
                                                  int* __restrict__ first, int* __restrict__ status) {
     for (int i = blockIdx.x * TPB + threadIdx.x; i < n_pts; i += gridDim.x * TPB) {
-        const long long inst = load_label(ins, ins_i64, i);
+        const long long inst = load_index(ins, ins_i64, i);
         if (inst < 0) continue;
         if (inst >= n_inst_cap) { atomicOr(status, PBN_AP_STATUS_INSTANCE_CAP); continue; }
         atomicMin(&first[inst], i);
     }
 }
 
-// ids[i] = table[sem[first[inst]]] * 1000 + inst + 1 (semantic -100 = class 0), 0 without an instance
+// ids[i] = gt_code of (sem[first[inst]], inst), 0 without an instance
 __global__ __launch_bounds__(TPB) void k_gt_code(const void* __restrict__ sem, int sem_i64, const void* __restrict__ ins,
                                                 int ins_i64, int n_pts, const int* __restrict__ label_table, int n_labels,
                                                 const int* __restrict__ first, int n_inst_cap, int* __restrict__ ids,
                                                 int* __restrict__ status) {
     for (int i = blockIdx.x * TPB + threadIdx.x; i < n_pts; i += gridDim.x * TPB) {
-        const long long inst = load_label(ins, ins_i64, i);
+        const long long inst = load_index(ins, ins_i64, i);
         int code = 0;
         if (inst >= 0 && inst < n_inst_cap) {
             const int f = first[inst];                     // <= i: this very point took part in the minimum
-            long long s = (f >= 0 && f < n_pts) ? load_label(sem, sem_i64, f) : 0;
-            if (s == -100) s = 0;
-            if (s < 0 || s >= n_labels) atomicOr(status, PBN_AP_STATUS_SEMANTIC_RANGE);
-            else code = label_table[s] * 1000 + (int)inst + 1;
+            const GtCode g = gt_code((f >= 0 && f < n_pts) ? load_index(sem, sem_i64, f) : 0, inst, label_table, n_labels);
+            if (g.status) atomicOr(status, g.status);
+            code = g.code;
         }
         ids[i] = code;
     }
@@ -84,7 +61,7 @@ __global__ __launch_bounds__(TPB) void k_gt_hist(const void* __restrict__ ids, i
         const int i = base + threadIdx.x;
         int bin = -1;
         if (i < n_pts) {
-            const long long id = load_label(ids, ids_i64, i);
+            const long long id = load_index(ids, ids_i64, i);
             if (id < 0 || id >= id_cap) atomicOr(status, PBN_AP_STATUS_ID_RANGE);
             else bin = (int)id;
         }
@@ -92,62 +69,21 @@ __global__ __launch_bounds__(TPB) void k_gt_hist(const void* __restrict__ ids, i
     }
 }
 
-// One workgroup walks the table in ascending id order: the ids with a count get consecutive slots (uid, gt_vert) and
-// table[id] becomes the id's slot.  An id past u_cap slots gets -1 (its points take no part) and reports ID_COUNT.
+// gt_number_scan (assoc_dev.h) by one workgroup; an id past u_cap slots reports ID_COUNT
 __global__ __launch_bounds__(TPB) void k_gt_scan(int* __restrict__ table, int id_cap, int* __restrict__ uid,
                                                 int* __restrict__ gt_vert, int u_cap, int* __restrict__ n_gt,
                                                 int* __restrict__ status) {
     __shared__ int s_wave[TPB / 64];
-    const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
-    int base = 0;
     bool over = false;
-    for (int t0 = 0; t0 < id_cap; t0 += TPB * SCAN_IDS) {                          // uniform trip count
-        const int id0 = t0 + (int)threadIdx.x * SCAN_IDS;
-        int c[SCAN_IDS], mine = 0;
-#pragma unroll
-        for (int k = 0; k < SCAN_IDS; ++k) {
-            c[k] = id0 + k < id_cap ? table[id0 + k] : 0;
-            mine += c[k] > 0 ? 1 : 0;
-        }
-        int incl = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += v;
-        }
-        __syncthreads();                                   // the previous trip's readers are done with s_wave
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < TPB / 64; ++w) {
-            before += w < wave ? s_wave[w] : 0;
-            all += s_wave[w];
-        }
-        int pos = base + before + incl - mine;
-#pragma unroll
-        for (int k = 0; k < SCAN_IDS; ++k) {
-            if (c[k] <= 0) continue;
-            if (pos < u_cap) {
-                uid[pos] = id0 + k;
-                gt_vert[pos] = c[k];
-                table[id0 + k] = pos;
-            } else {
-                table[id0 + k] = -1;
-                over = true;
-            }
-            ++pos;
-        }
-        base += all;
-    }
+    const int live = gt_number_scan(table, id_cap, uid, gt_vert, u_cap, s_wave, &over);
     if (over) atomicOr(status, PBN_AP_STATUS_ID_COUNT);
-    if (threadIdx.x == 0) *n_gt = base < u_cap ? base : u_cap;
+    if (threadIdx.x == 0) *n_gt = live;
 }
 
 __global__ __launch_bounds__(TPB) void k_gt_lookup(const void* __restrict__ ids, int ids_i64, int n_pts, int id_cap,
                                                   const int* __restrict__ table, int* __restrict__ gt_index) {
     for (int i = blockIdx.x * TPB + threadIdx.x; i < n_pts; i += gridDim.x * TPB) {
-        const long long id = load_label(ids, ids_i64, i);
+        const long long id = load_index(ids, ids_i64, i);
         gt_index[i] = (id >= 0 && id < id_cap) ? table[id] : -1;
     }
 }
@@ -164,7 +100,12 @@ __global__ __launch_bounds__(TPB) void k_overlap_clear(const int* __restrict__ n
     }
 }
 
-// k_instance_overlap (post.hip) with the row gate p < n_keep, the live bin count on the device and output row stride u_cap
+// inter[p][gt_index[i]] += 1 for every point i inside prediction p (mask value != 0): the association counts of
+// tools/eval.py:230-245 (`count_nonzero(logical_and(gt_ids == id, pred_mask))` per (prediction, instance) pair, one pass
+// over the scene per pair in the reference) as ONE pass per prediction.  A block owns OVERLAP_CHUNK consecutive points of
+// one prediction; instances are runs of neighbouring vertices, so a wave first merges lanes that hit the same bin.
+// Row gate p < n_keep and live bin count n_gt on the device (a null pointer: the capacity itself, the host-count form
+// pbn_instance_overlap); output row stride u_cap.
 // USE_LDS: a block's bins in LDS first (u_cap <= OVERLAP_LDS_BINS); without it straight to global atomics, and no LDS is held
 template <bool USE_LDS>
 __global__ __launch_bounds__(TPB) void k_instance_overlap_dev(const int* __restrict__ clusters, const int* __restrict__ n_keep_dev,
@@ -203,36 +144,15 @@ __global__ __launch_bounds__(TPB) void k_instance_overlap_dev(const int* __restr
 }
 
 // ---- pbn_ap_record_append ----------------------------------------------------------------------------------------------
-// One thread: size of the record, the log's bookkeeping and the header.  Consumes (reads and clears) the association status.
+// One thread: ap_record_reserve (assoc_dev.h) for this scene.  Consumes (reads and clears) the association status.
 __global__ __launch_bounds__(64) void k_ap_record_reserve(int* __restrict__ state, int* __restrict__ log, int log_words,
                                                          int scene_tag, const int* __restrict__ n_keep_dev, int p_cap,
                                                          const int* __restrict__ n_gt_dev, int u_cap, int n_pts,
                                                          const int* __restrict__ post_status, int* __restrict__ assoc_status) {
     if (threadIdx.x != 0) return;
-    const int nk = live_count(n_keep_dev, p_cap), ng = live_count(n_gt_dev, u_cap);
-    const long long words = nk == 0 ? HDR : (long long)HDR + 2LL * ng + 2LL * nk + (long long)nk * ng;
     const int status = (post_status ? *post_status : 0) | *assoc_status;
     *assoc_status = 0;
-    const long long wanted = (long long)state[ST_WANTED] + words;
-    state[ST_WANTED] = wanted > 0x7fffffffLL ? 0x7fffffff : (int)wanted;
-    const int used = state[ST_USED];
-    if (state[ST_OVERFLOW] || used < 0 || (long long)used + words > (long long)log_words) {
-        state[ST_OVERFLOW] = 1;                             // sticky: nothing is written after the first record that did not fit
-        state[ST_OFFSET] = -1;
-        return;
-    }
-    int* rec = log + used;
-    rec[0] = PBN_AP_RECORD_MAGIC;
-    rec[1] = scene_tag;
-    rec[2] = nk;
-    rec[3] = ng;
-    rec[4] = n_pts;
-    rec[5] = status;
-    rec[6] = (int)words;
-    rec[7] = 0;
-    state[ST_USED] = used + (int)words;
-    state[ST_RECORDS] += 1;
-    state[ST_OFFSET] = used;
+    ap_record_reserve(state, log, log_words, scene_tag, live_count(n_keep_dev, p_cap), live_count(n_gt_dev, u_cap), n_pts, status);
 }
 
 // body of the record at the published offset: uid | gt_vert | label_id | conf bits | inter rows compacted from stride u_cap
@@ -246,28 +166,17 @@ __global__ __launch_bounds__(TPB) void k_ap_record_write(const int* __restrict__
     int* rec = log + off;
     const int nk = rec[2], ng = rec[3];
     if (nk == 0) return;
-    const long long a = ng, b = 2LL * ng, c = b + nk, d = c + nk, total = d + (long long)nk * ng;
+    const long long head = 2LL * ng + 2LL * nk, total = head + (long long)nk * ng;
     const long long step = (long long)gridDim.x * TPB;
     for (long long e = (long long)blockIdx.x * TPB + threadIdx.x; e < total; e += step) {
         int v;
-        if (e < a) v = uid[e];
-        else if (e < b) v = gt_vert[e - a];
-        else if (e < c) {
-            const long long s = semantic_id[e - b];
-            v = (int)s;
-            if (s != (long long)v) atomicOr(&rec[5], PBN_AP_STATUS_LABEL_RANGE);
-        } else if (e < d) v = __float_as_int(conf[e - c]);
+        if (e < head) v = ap_record_head_word(e, nk, ng, rec, uid, gt_vert, semantic_id, conf);
         else {
-            const long long r = e - d, q = r / ng;
+            const long long r = e - head, q = r / ng;
             v = inter[q * u_cap + (r - q * ng)];
         }
-        rec[HDR + e] = v;
+        rec[AP_HDR + e] = v;
     }
-}
-
-inline int stride_blocks(long long n) {
-    const long long b = (n + TPB - 1) / TPB;
-    return (int)(b < 1 ? 1 : (b > STRIDE_BLOCKS ? STRIDE_BLOCKS : b));
 }
 
 }  // namespace
@@ -330,6 +239,27 @@ extern "C" int pbn_instance_overlap_dev(const int32_t* clusters, const int32_t* 
             hipLaunchKernelGGL(k_instance_overlap_dev<false>, grid, dim3(TPB), 0, stream, clusters, n_keep, p_cap, n_pts, gt_index,
                                n_gt, u_cap, inter);
     }
+    PBN_LAUNCH_CHECK();
+    return PBN_OK;
+}
+
+// the host-count form (the evaluator's table, tools/eval.py:230-245): every row and every bin live, inter[n_pred, n_gt] cleared whole
+extern "C" int pbn_instance_overlap(const int32_t* masks, int n_pred, int n_pts, const int32_t* gt_index, int n_gt,
+                                    int32_t* inter, pbn_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_pred < 0 || n_pts < 0 || n_gt < 1) return PBN_ERR_ARG;
+    if (n_pred == 0) return PBN_OK;
+    if (!inter) return PBN_ERR_ARG;
+    { const int frc_ = fill_bytes(inter, 0, sizeof(int32_t) * (size_t)n_pred * n_gt, stream); if (frc_ != PBN_OK) return frc_; }
+    if (n_pts == 0) return PBN_OK;
+    if (!masks || !gt_index) return PBN_ERR_ARG;
+    const dim3 grid(cdiv(n_pts, OVERLAP_CHUNK), n_pred);
+    if (n_gt <= OVERLAP_LDS_BINS)
+        hipLaunchKernelGGL(k_instance_overlap_dev<true>, grid, dim3(TPB), 0, stream, masks, (const int*)nullptr, n_pred, n_pts, gt_index,
+                           (const int*)nullptr, n_gt, inter);
+    else
+        hipLaunchKernelGGL(k_instance_overlap_dev<false>, grid, dim3(TPB), 0, stream, masks, (const int*)nullptr, n_pred, n_pts, gt_index,
+                           (const int*)nullptr, n_gt, inter);
     PBN_LAUNCH_CHECK();
     return PBN_OK;
 }

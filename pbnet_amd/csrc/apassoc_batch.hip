@@ -17,54 +17,17 @@
 //     counter of a wave;
 //   * integer atomics only, so two runs give the same log bytes; nothing waits for the host, grids are sized by capacity.
 #include "pbn_common.h"
-#include "post_dev.h"
+#include "assoc_dev.h"
 
 namespace pbn {
 namespace {
 
-constexpr int TPB = 256;
-constexpr int STRIDE_BLOCKS = 2048;                 // cap of every striding grid
-constexpr int GT_ID_CAP_MAX = 1 << 20;              // direct table per scene, as pbn_gt_index_dev
-constexpr int SCAN_IDS = 4;                         // ids per thread and trip of k_batch_scan
+constexpr int TPB = POST_TPB;
 constexpr int OVERLAP_CHUNK = 2048;                 // folded points per workgroup of k_batch_overlap
 constexpr int OVERLAP_LDS_COUNTERS = 8192;          // 32 KiB of counters per workgroup
 constexpr int BODY_BLOCKS = 64;                     // blocks per scene of k_batch_body
-constexpr int HDR = PBN_AP_RECORD_HEADER;
-constexpr int ST_USED = 0, ST_WANTED = 1, ST_RECORDS = 2, ST_OVERFLOW = 3, ST_OFFSET = 4;
 // per-scene words of the workspace's small block: n_gt | association status | n_keep (clamped) | offset of the record (-1 = not written)
 constexpr int SC_NGT = 0, SC_STATUS = 1, SC_NKEEP = 2, SC_OFFSET = 3, SC_WORDS = 4;
-
-__device__ __forceinline__ long long load_label(const void* p, int i64, long long i) {
-    return i64 ? ((const long long*)p)[i] : (long long)((const int*)p)[i];
-}
-
-// the scene that owns folded point `pt` (0 <= pt < point_start[B]): the last j with point_start[j] <= pt, so an empty scene is
-// stepped over (summary.hip)
-__device__ __forceinline__ int scene_of_folded(const pbn_tta_table& U, int pt) {
-    int s = 0;
-#pragma unroll
-    for (int j = 1; j < PBN_MAX_SCENES; ++j) s = (j < U.n_scenes && pt >= U.point_start[j]) ? j : s;
-    return s;
-}
-
-__device__ __forceinline__ int start_of(const pbn_tta_table& U, int j) {
-    int v = U.point_start[0];
-#pragma unroll
-    for (int k = 1; k <= PBN_MAX_SCENES; ++k) v = k == j ? U.point_start[k] : v;
-    return v;
-}
-
-// one add per distinct bin of a wave (apassoc.hip): every lane of the wave must call this; bin < 0 takes no part
-__device__ __forceinline__ void wave_merged_add(int* bins, int bin) {
-    unsigned long long todo = __ballot(bin >= 0);
-    while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const int lb = __shfl(bin, leader);
-        const unsigned long long same = __ballot(bin == lb) & todo;
-        if (lane_id() == leader) atomicAdd(&bins[lb], __popcll(same));
-        todo &= ~same;
-    }
-}
 
 // tables cleared, `first` to "no point yet", the per-scene scalars to 0 / -1
 __global__ __launch_bounds__(TPB) void k_batch_clear(int* __restrict__ table, long long n_table, int* __restrict__ first,
@@ -78,13 +41,13 @@ __global__ __launch_bounds__(TPB) void k_batch_clear(int* __restrict__ table, lo
 // ---- ground-truth encoding per scene (get_val_gt.py:26-37, k_gt_first / k_gt_code of apassoc.hip with a scene axis) ----------
 __global__ __launch_bounds__(TPB) void k_batch_gt_first(const void* __restrict__ ins, int ins_i64, pbn_tta_table U, int n_inst_cap,
                                                        int* __restrict__ first, int* __restrict__ scene_words) {
-    const int n_total = start_of(U, U.n_scenes);
+    const int n_total = start_of(U.point_start, U.n_scenes);
     for (int i = blockIdx.x * TPB + threadIdx.x; i < n_total; i += gridDim.x * TPB) {
-        const long long inst = load_label(ins, ins_i64, i);
+        const long long inst = load_index(ins, ins_i64, i);
         if (inst < 0) continue;
-        const int scene = scene_of_folded(U, i);
+        const int scene = scene_of_folded(U.point_start, U.n_scenes, i);
         if (inst >= n_inst_cap) { atomicOr(&scene_words[scene * SC_WORDS + SC_STATUS], PBN_AP_STATUS_INSTANCE_CAP); continue; }
-        atomicMin(&first[(size_t)scene * n_inst_cap + inst], i - start_of(U, scene));
+        atomicMin(&first[(size_t)scene * n_inst_cap + inst], i - start_of(U.point_start, scene));
     }
 }
 
@@ -92,18 +55,18 @@ __global__ __launch_bounds__(TPB) void k_batch_gt_code(const void* __restrict__ 
                                                       int ins_i64, pbn_tta_table U, const int* __restrict__ label_table,
                                                       int n_labels, const int* __restrict__ first, int n_inst_cap,
                                                       int* __restrict__ ids, int* __restrict__ scene_words) {
-    const int n_total = start_of(U, U.n_scenes);
+    const int n_total = start_of(U.point_start, U.n_scenes);
     for (int i = blockIdx.x * TPB + threadIdx.x; i < n_total; i += gridDim.x * TPB) {
-        const long long inst = load_label(ins, ins_i64, i);
+        const long long inst = load_index(ins, ins_i64, i);
         int code = 0;
         if (inst >= 0 && inst < n_inst_cap) {
-            const int scene = scene_of_folded(U, i);
-            const int p0 = start_of(U, scene), n_j = start_of(U, scene + 1) - p0;
+            const int scene = scene_of_folded(U.point_start, U.n_scenes, i);
+            const int p0 = start_of(U.point_start, scene), n_j = start_of(U.point_start, scene + 1) - p0;
             const int f = first[(size_t)scene * n_inst_cap + inst];          // <= i - p0: this very point took part in the minimum
-            long long s = (f >= 0 && f < n_j) ? load_label(sem, sem_i64, (long long)p0 + f) : 0;
-            if (s == -100) s = 0;
-            if (s < 0 || s >= n_labels) atomicOr(&scene_words[scene * SC_WORDS + SC_STATUS], PBN_AP_STATUS_SEMANTIC_RANGE);
-            else code = label_table[s] * 1000 + (int)inst + 1;
+            const GtCode g = gt_code((f >= 0 && f < n_j) ? load_index(sem, sem_i64, (long long)p0 + f) : 0, inst, label_table,
+                                     n_labels);
+            if (g.status) atomicOr(&scene_words[scene * SC_WORDS + SC_STATUS], g.status);
+            code = g.code;
         }
         ids[i] = code;
     }
@@ -113,13 +76,13 @@ __global__ __launch_bounds__(TPB) void k_batch_gt_code(const void* __restrict__ 
 // table[scene][id] += 1 per point (the id's vertex count); B * id_cap <= 2^23, so the flat bin fits an int
 __global__ __launch_bounds__(TPB) void k_batch_hist(const void* __restrict__ ids, int ids_i64, pbn_tta_table U, int id_cap,
                                                    int* __restrict__ table, int* __restrict__ scene_words) {
-    const int n_total = start_of(U, U.n_scenes);
+    const int n_total = start_of(U.point_start, U.n_scenes);
     for (int base = blockIdx.x * TPB; base < n_total; base += gridDim.x * TPB) {      // uniform per block: whole waves ballot
         const int i = base + threadIdx.x;
         int bin = -1;
         if (i < n_total) {
-            const int scene = scene_of_folded(U, i);
-            const long long id = load_label(ids, ids_i64, i);
+            const int scene = scene_of_folded(U.point_start, U.n_scenes, i);
+            const long long id = load_index(ids, ids_i64, i);
             if (id < 0 || id >= id_cap) atomicOr(&scene_words[scene * SC_WORDS + SC_STATUS], PBN_AP_STATUS_ID_RANGE);
             else bin = scene * id_cap + (int)id;
         }
@@ -127,59 +90,16 @@ __global__ __launch_bounds__(TPB) void k_batch_hist(const void* __restrict__ ids
     }
 }
 
-// k_gt_scan (apassoc.hip), one workgroup per scene: the scene's table walked in ascending id order, the ids with a count get
-// consecutive slots (uid, gt_vert) and table[id] becomes the slot; an id past u_cap slots gets -1 and reports ID_COUNT
+// k_gt_scan (apassoc.hip), one workgroup per scene: gt_number_scan over the scene's table; an id past u_cap slots reports ID_COUNT
 __global__ __launch_bounds__(TPB) void k_batch_scan(int* __restrict__ table_all, int id_cap, int* __restrict__ uid_all,
                                                    int* __restrict__ gt_vert_all, int u_cap, int* __restrict__ scene_words) {
     __shared__ int s_wave[TPB / 64];
     const int scene = blockIdx.x;
-    int* table = table_all + (size_t)scene * id_cap;
-    int* uid = uid_all + (size_t)scene * u_cap;
-    int* gt_vert = gt_vert_all + (size_t)scene * u_cap;
-    const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
-    int base = 0;
     bool over = false;
-    for (int t0 = 0; t0 < id_cap; t0 += TPB * SCAN_IDS) {                          // uniform trip count
-        const int id0 = t0 + (int)threadIdx.x * SCAN_IDS;
-        int c[SCAN_IDS], mine = 0;
-#pragma unroll
-        for (int k = 0; k < SCAN_IDS; ++k) {
-            c[k] = id0 + k < id_cap ? table[id0 + k] : 0;
-            mine += c[k] > 0 ? 1 : 0;
-        }
-        int incl = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += v;
-        }
-        __syncthreads();                                   // the previous trip's readers are done with s_wave
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < TPB / 64; ++w) {
-            before += w < wave ? s_wave[w] : 0;
-            all += s_wave[w];
-        }
-        int pos = base + before + incl - mine;
-#pragma unroll
-        for (int k = 0; k < SCAN_IDS; ++k) {
-            if (c[k] <= 0) continue;
-            if (pos < u_cap) {
-                uid[pos] = id0 + k;
-                gt_vert[pos] = c[k];
-                table[id0 + k] = pos;
-            } else {
-                table[id0 + k] = -1;
-                over = true;
-            }
-            ++pos;
-        }
-        base += all;
-    }
+    const int live = gt_number_scan(table_all + (size_t)scene * id_cap, id_cap, uid_all + (size_t)scene * u_cap,
+                                    gt_vert_all + (size_t)scene * u_cap, u_cap, s_wave, &over);
     if (over) atomicOr(&scene_words[scene * SC_WORDS + SC_STATUS], PBN_AP_STATUS_ID_COUNT);
-    if (threadIdx.x == 0) scene_words[scene * SC_WORDS + SC_NGT] = base < u_cap ? base : u_cap;
+    if (threadIdx.x == 0) scene_words[scene * SC_WORDS + SC_NGT] = live;
 }
 
 // ---- the B records: k_ap_record_reserve (apassoc.hip) for scene 0 .. B - 1 in order, by one thread ------------------------
@@ -196,31 +116,10 @@ __global__ __launch_bounds__(64) void k_batch_reserve(int* __restrict__ state, i
         const int nk = post_scalars && n_prop > 0 ? max(0, min(post_scalars[j], n_prop - kept_sum)) : 0;
         kept_sum += nk;
         const int ng = sw[SC_NGT];
-        const long long words = nk == 0 ? HDR : (long long)HDR + 2LL * ng + 2LL * nk + (long long)nk * ng;
         const int status = (post_scalars ? post_scalars[U.n_scenes + j] : 0) | sw[SC_STATUS];
         sw[SC_NKEEP] = nk;
-        const long long wanted = (long long)state[ST_WANTED] + words;
-        state[ST_WANTED] = wanted > 0x7fffffffLL ? 0x7fffffff : (int)wanted;
-        const int used = state[ST_USED];
-        if (state[ST_OVERFLOW] || used < 0 || (long long)used + words > (long long)log_words) {
-            state[ST_OVERFLOW] = 1;                         // sticky: nothing is written after the first record that did not fit
-            state[ST_OFFSET] = -1;
-            sw[SC_OFFSET] = -1;
-            continue;
-        }
-        int* rec = log + used;
-        rec[0] = PBN_AP_RECORD_MAGIC;
-        rec[1] = tags.tag[j];
-        rec[2] = nk;
-        rec[3] = ng;
-        rec[4] = start_of(U, j + 1) - start_of(U, j);
-        rec[5] = status;
-        rec[6] = (int)words;
-        rec[7] = 0;
-        state[ST_USED] = used + (int)words;
-        state[ST_RECORDS] += 1;
-        state[ST_OFFSET] = used;
-        sw[SC_OFFSET] = used;
+        sw[SC_OFFSET] = ap_record_reserve(state, log, log_words, tags.tag[j], nk, ng,
+                                          start_of(U.point_start, j + 1) - start_of(U.point_start, j), status);
     }
 }
 
@@ -238,19 +137,10 @@ __global__ __launch_bounds__(TPB) void k_batch_body(int* __restrict__ log, const
     const int* gt_vert = gt_vert_all + (size_t)scene * u_cap;
     const long long* sid = semantic_id + (size_t)scene * n_prop;
     const float* cf = conf + (size_t)scene * n_prop;
-    const long long a = ng, b = 2LL * ng, c = b + nk, d = c + nk, total = d + (long long)nk * ng;
+    const long long head = 2LL * ng + 2LL * nk, total = head + (long long)nk * ng;
     const long long step = (long long)gridDim.x * TPB;
-    for (long long e = (long long)blockIdx.x * TPB + threadIdx.x; e < total; e += step) {
-        int v = 0;
-        if (e < a) v = uid[e];
-        else if (e < b) v = gt_vert[e - a];
-        else if (e < c) {
-            const long long s = sid[e - b];
-            v = (int)s;
-            if (s != (long long)v) atomicOr(&rec[5], PBN_AP_STATUS_LABEL_RANGE);
-        } else if (e < d) v = __float_as_int(cf[e - c]);
-        rec[HDR + e] = v;
-    }
+    for (long long e = (long long)blockIdx.x * TPB + threadIdx.x; e < total; e += step)
+        rec[AP_HDR + e] = e < head ? ap_record_head_word(e, nk, ng, rec, uid, gt_vert, sid, cf) : 0;
 }
 
 // inter[label][slot of the point's id] += 1 straight into the records
@@ -258,11 +148,11 @@ __global__ __launch_bounds__(TPB) void k_batch_overlap(const int* __restrict__ p
                                                       int ids_i64, pbn_tta_table U, int id_cap, const int* __restrict__ table,
                                                       const int* __restrict__ scene_words, int* __restrict__ log) {
     __shared__ int s_cnt[OVERLAP_LDS_COUNTERS];
-    const int n_total = start_of(U, U.n_scenes);
+    const int n_total = start_of(U.point_start, U.n_scenes);
     const int lo = blockIdx.x * OVERLAP_CHUNK;
     const int hi = min(n_total, lo + OVERLAP_CHUNK);
     // the workgroup's own scene: that of its first point (uniform)
-    const int scene0 = scene_of_folded(U, lo);
+    const int scene0 = scene_of_folded(U.point_start, U.n_scenes, lo);
     const int off0 = scene_words[scene0 * SC_WORDS + SC_OFFSET];
     const int nk0 = scene_words[scene0 * SC_WORDS + SC_NKEEP], ng0 = scene_words[scene0 * SC_WORDS + SC_NGT];
     const long long cnt0 = off0 >= 0 ? (long long)nk0 * ng0 : 0;
@@ -275,18 +165,18 @@ __global__ __launch_bounds__(TPB) void k_batch_overlap(const int* __restrict__ p
         int direct = -1;                                       // word of the log this lane adds to directly
         if (i < hi) {
             const int label = point_instance[i];
-            const int scene = scene_of_folded(U, i);
+            const int scene = scene_of_folded(U.point_start, U.n_scenes, i);
             const int* sw = scene_words + scene * SC_WORDS;
             const int off = scene == scene0 ? off0 : sw[SC_OFFSET];
             const int nk = scene == scene0 ? nk0 : sw[SC_NKEEP];
             if (off >= 0 && label >= 0 && label < nk) {        // -100 and every other label outside [0, n_keep) count for nothing
-                const long long id = load_label(ids, ids_i64, i);
+                const long long id = load_index(ids, ids_i64, i);
                 const int g = (id >= 0 && id < id_cap) ? table[(size_t)scene * id_cap + id] : -1;
                 if (g >= 0) {
                     const int ng = scene == scene0 ? ng0 : sw[SC_NGT];
                     const int bin = label * ng + g;
                     if (lds && scene == scene0) atomicAdd(&s_cnt[bin], 1);
-                    else direct = off + HDR + 2 * ng + 2 * nk + bin;
+                    else direct = off + AP_HDR + 2 * ng + 2 * nk + bin;
                 }
             }
         }
@@ -294,16 +184,11 @@ __global__ __launch_bounds__(TPB) void k_batch_overlap(const int* __restrict__ p
     }
     __syncthreads();
     if (!lds) return;                                          // uniform
-    int* out = log + off0 + HDR + 2 * ng0 + 2 * nk0;
+    int* out = log + off0 + AP_HDR + 2 * ng0 + 2 * nk0;
     for (int e = threadIdx.x; e < lds_words; e += TPB) {
         const int c = s_cnt[e];
         if (c) atomicAdd(&out[e], c);
     }
-}
-
-inline int stride_blocks(long long n) {
-    const long long b = (n + TPB - 1) / TPB;
-    return (int)(b < 1 ? 1 : (b > STRIDE_BLOCKS ? STRIDE_BLOCKS : b));
 }
 
 struct BatchCarve {

@@ -39,15 +39,8 @@ __global__ __launch_bounds__(64) void k_mask_iou(const unsigned* __restrict__ ma
                                                 int words, const int* __restrict__ counts, float* __restrict__ iou) {
     const int i = blockIdx.x, j = blockIdx.y;
     const int ri = rows ? rows[i] : i, rj = rows ? rows[j] : j;
-    const unsigned* a = masks + (size_t)ri * words;
-    const unsigned* b = masks + (size_t)rj * words;
-    int c = 0;
-    for (int w = threadIdx.x; w < words; w += 64) c += __popc(a[w] & b[w]);
-    c = wave_reduce_add(c);
-    if (threadIdx.x == 0) {
-        const float inter = (float)c;
-        iou[(size_t)i * n_rows + j] = inter / (((float)counts[ri] + (float)counts[rj]) - inter);
-    }
+    const int c = mask_pair_intersection(masks + (size_t)ri * words, masks + (size_t)rj * words, words);
+    if (threadIdx.x == 0) iou[(size_t)i * n_rows + j] = mask_pair_iou(c, counts[ri], counts[rj]);
 }
 
 // seg[pt] = the LAST picked cluster that contains the point (eval_map.py:104-107 overwrites in order), else -100
@@ -142,23 +135,13 @@ __global__ __launch_bounds__(64) void k_mask_iou_dev(const unsigned* __restrict_
         const int i = e / n_rows, j = e - i * n_rows;
         const int ri = rows[i], rj = rows[j];
         if (ri < 0 || ri >= cap || rj < 0 || rj >= cap) continue;
-        const unsigned* a = masks + (size_t)ri * words;
-        const unsigned* b = masks + (size_t)rj * words;
-        int c = 0;
-        for (int w = threadIdx.x; w < words; w += 64) c += __popc(a[w] & b[w]);
-        c = wave_reduce_add(c);
-        if (threadIdx.x == 0) {
-            const float inter = (float)c;
-            iou[(size_t)i * cap + j] = inter / (((float)counts[ri] + (float)counts[rj]) - inter);
-        }
+        const int c = mask_pair_intersection(masks + (size_t)ri * words, masks + (size_t)rj * words, words);
+        if (threadIdx.x == 0) iou[(size_t)i * cap + j] = mask_pair_iou(c, counts[ri], counts[rj]);
     }
 }
 
-// The greedy NMS of tools/mIOU.py:77-87 in one workgroup.  Order: score descending, among equal scores the LOWER survivor
-// index first; rank[i] = #{j : s[j] > s[i] or (s[j] == s[i] and j < i)} is a permutation (scores that passed `> score_t`
-// are not NaN), exact and stable, so the walk is the same on every run.  A survivor is picked when no earlier pick has
-// iou[pick][it] > nms_t (fp32 `>`: an IoU equal to the threshold does not suppress); after a pick every lane marks what that
-// pick suppresses.  pick = survivor positions in pick order, pick_rows = their proposal indices, tails -1.
+// nms_walk (post_dev.h) in one workgroup over the survivors of k_post_select: pick = survivor positions in pick order,
+// pick_rows = their proposal indices, tails -1
 __global__ __launch_bounds__(TPB) void k_post_nms(const float* __restrict__ score, const int* __restrict__ rows,
                                                  const int* __restrict__ n_rows_dev, int cap, const float* __restrict__ iou,
                                                  float nms_t, int* __restrict__ pick, int* __restrict__ pick_rows,
@@ -166,43 +149,7 @@ __global__ __launch_bounds__(TPB) void k_post_nms(const float* __restrict__ scor
     __shared__ float s_score[POST_MAX_PROPOSALS];
     __shared__ unsigned short s_order[POST_MAX_PROPOSALS];
     __shared__ unsigned char s_supp[POST_MAX_PROPOSALS];
-    const int n = min(*n_rows_dev, cap);
-    for (int i = threadIdx.x; i < n; i += TPB) {
-        const int r = rows[i];
-        s_score[i] = (r >= 0 && r < cap) ? score[r] : -INFINITY;
-        s_order[i] = (unsigned short)i;            // every slot names a survivor even if the ranks were no permutation (NaN)
-        s_supp[i] = 0;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < n; i += TPB) {
-        const float si = s_score[i];
-        int rank = 0;
-        for (int j = 0; j < n; ++j) {              // every lane reads the same word: an LDS broadcast
-            const float sj = s_score[j];
-            rank += (sj > si || (sj == si && j < i)) ? 1 : 0;
-        }
-        s_order[rank] = (unsigned short)i;
-    }
-    __syncthreads();
-    int n_pick = 0;
-    for (int k = 0; k < n; ++k) {
-        const int it = s_order[k];
-        if (s_supp[it]) continue;                  // uniform: every thread reads the same flag
-        if (threadIdx.x == 0) {
-            pick[n_pick] = it;
-            pick_rows[n_pick] = rows[it];
-        }
-        ++n_pick;
-        // `it` itself is left alone: a thread that has not read its flag yet must still see it clear
-        const float* row = iou + (size_t)it * cap;
-        for (int j = threadIdx.x; j < n; j += TPB)
-            if (j != it && row[j] > nms_t) s_supp[j] = 1;
-        __syncthreads();
-    }
-    for (int k = n_pick + threadIdx.x; k < cap; k += TPB) {
-        pick[k] = -1;
-        pick_rows[k] = -1;
-    }
+    const int n_pick = nms_walk(s_score, s_order, s_supp, score, rows, min(*n_rows_dev, cap), cap, iou, nms_t, pick, pick_rows);
     if (threadIdx.x == 0) *n_pick_dev = n_pick;
 }
 
@@ -304,15 +251,8 @@ __global__ __launch_bounds__(TPB) void k_post_compact(const int* __restrict__ co
         const int pos = block_flag_scan(flag, s_wave, &total);
         if (flag) {
             const int p = pick_rows[c];
-            const long long e = offsets_i64 ? ((const long long*)offsets)[p] : (long long)((const int*)offsets)[p];
-            long long cls = -1;
-            if (e >= 0 && e < n_entries) {
-                const long long pt = proposals_idx[2 * e + 1];
-                if (pt >= 0 && pt < n_sem) {
-                    const long long s = sem_i64 ? ((const long long*)pred_sem)[pt] : (long long)((const int*)pred_sem)[pt];
-                    if (s >= 0 && s < n_labels) cls = label_table[s];
-                }
-            }
+            const long long cls = first_member_class(proposals_idx, n_entries, offsets, offsets_i64, p, pred_sem, sem_i64, n_sem,
+                                                     label_table, n_labels);
             if (cls < 0) atomicOr(status, POST_STATUS_CLASS);
             keep[base + pos] = c;
             scores_out[base + pos] = score[p];
@@ -338,56 +278,6 @@ __global__ __launch_bounds__(TPB) void k_bits_to_dense_dev(const unsigned* __res
     int v = 0;
     if (r < min(*n_keep_dev, cap)) v = (masks[(size_t)keep[r] * words + (pt >> 5)] >> (pt & 31)) & 1u;
     dense[e] = v;
-}
-
-// inter[p][gt_index[i]] += 1 for every point i inside prediction p (mask value != 0): the association counts of
-// tools/eval.py:230-245 (`count_nonzero(logical_and(gt_ids == id, pred_mask))` per (prediction, instance) pair, one pass
-// over the scene per pair in the reference) as ONE pass per prediction.  A block owns OVERLAP_CHUNK consecutive points of
-// one prediction; instances are runs of neighbouring vertices, so a wave first merges lanes that hit the same bin
-// (leader adds the lane count) before touching the LDS histogram.
-constexpr int OVERLAP_CHUNK = 4096;
-constexpr int OVERLAP_LDS_BINS = 8192;
-
-__global__ __launch_bounds__(TPB) void k_instance_overlap(const int* __restrict__ masks, int n_pts,
-                                                         const int* __restrict__ gt_index, int n_gt, int use_lds,
-                                                         int* __restrict__ inter) {
-    __shared__ int s_hist[OVERLAP_LDS_BINS];
-    const int p = blockIdx.y;
-    const int lo = blockIdx.x * OVERLAP_CHUNK;
-    const int hi = min(n_pts, lo + OVERLAP_CHUNK);
-    int* out = inter + (size_t)p * n_gt;
-    if (use_lds) {
-        for (int b = threadIdx.x; b < n_gt; b += TPB) s_hist[b] = 0;
-        __syncthreads();
-    }
-    const int* row = masks + (size_t)p * n_pts;
-    for (int base = lo; base < hi; base += TPB) {         // uniform trip count: the ballots below need whole waves
-        const int i = base + threadIdx.x;
-        int bin = -1;
-        if (i < hi && row[i] != 0) {
-            const int g = gt_index[i];
-            if (g >= 0 && g < n_gt) bin = g;
-        }
-        unsigned long long todo = __ballot(bin >= 0);
-        while (todo) {
-            const int leader = __ffsll((long long)todo) - 1;
-            const int lb = __shfl(bin, leader);
-            const unsigned long long same = __ballot(bin == lb) & todo;
-            if ((int)(threadIdx.x & 63) == leader) {
-                const int c = __popcll(same);
-                if (use_lds) atomicAdd(&s_hist[lb], c);
-                else atomicAdd(&out[lb], c);
-            }
-            todo &= ~same;
-        }
-    }
-    if (use_lds) {
-        __syncthreads();
-        for (int b = threadIdx.x; b < n_gt; b += TPB) {
-            const int c = s_hist[b];
-            if (c) atomicAdd(&out[b], c);
-        }
-    }
 }
 
 }  // namespace
@@ -509,8 +399,9 @@ extern "C" int pbn_superpoint_refine_dev(const uint32_t* masks, const int32_t* p
     const int nb = cdiv(n_fold, TPB);
     const long long clear_max = (long long)n_sp_cap * (n_prop + 1) > (long long)n_prop * words ? (long long)n_sp_cap * (n_prop + 1)
                                                                                                 : (long long)n_prop * words;
-    const int clear_blocks = (int)(clear_max / TPB + 1 < 2048 ? clear_max / TPB + 1 : 2048);
-    hipLaunchKernelGGL(k_refine_clear, dim3(clear_blocks), dim3(TPB), 0, stream, n_pick, n_prop, n_sp_cap, words, hist, masks_out);
+    // + 1: clear_max / TPB + 1 blocks, one also for an empty table
+    hipLaunchKernelGGL(k_refine_clear, dim3(stride_blocks(clear_max + 1)), dim3(TPB), 0, stream, n_pick, n_prop, n_sp_cap, words,
+                       hist, masks_out);
     hipLaunchKernelGGL(k_point_labels_dev, dim3(nb), dim3(TPB), 0, stream, masks, pick_rows, n_pick, n_prop, words, n_fold,
                        (long long*)seg);
     hipLaunchKernelGGL(k_sp_hist_dev, dim3(nb), dim3(TPB), 0, stream, (const long long*)seg, (const long long*)superpoint, n_fold,
@@ -542,21 +433,6 @@ extern "C" int pbn_post_compact(const int32_t* counts2, const int32_t* pick_rows
                        n_keep, status);
     hipLaunchKernelGGL(k_bits_to_dense_dev, dim3(cdiv((long long)n_prop * n_fold, TPB)), dim3(TPB), 0, stream, masks2, keep, n_keep,
                        n_prop, pbn_post_words(n_fold), n_fold, clusters);
-    PBN_LAUNCH_CHECK();
-    return PBN_OK;
-}
-
-extern "C" int pbn_instance_overlap(const int32_t* masks, int n_pred, int n_pts, const int32_t* gt_index, int n_gt,
-                                    int32_t* inter, pbn_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (n_pred < 0 || n_pts < 0 || n_gt < 1) return PBN_ERR_ARG;
-    if (n_pred == 0) return PBN_OK;
-    if (!inter) return PBN_ERR_ARG;
-    { const int frc_ = fill_bytes(inter, 0, sizeof(int32_t) * (size_t)n_pred * n_gt, stream); if (frc_ != PBN_OK) return frc_; }
-    if (n_pts == 0) return PBN_OK;
-    if (!masks || !gt_index) return PBN_ERR_ARG;
-    hipLaunchKernelGGL(k_instance_overlap, dim3(cdiv(n_pts, OVERLAP_CHUNK), n_pred), dim3(TPB), 0, stream, masks, n_pts,
-                       gt_index, n_gt, n_gt <= OVERLAP_LDS_BINS ? 1 : 0, inter);
     PBN_LAUNCH_CHECK();
     return PBN_OK;
 }

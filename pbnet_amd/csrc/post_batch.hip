@@ -22,14 +22,6 @@ namespace {
 constexpr int TPB = POST_TPB;
 constexpr int NO_LABEL = -100;
 
-// entry j of a scene-table column, j uniform: selects over constant indices, so the by-value table stays in scalar registers
-__device__ __forceinline__ int table_at(const int32_t (&a)[PBN_MAX_SCENES + 1], int j) {
-    int v = a[0];
-#pragma unroll
-    for (int k = 1; k <= PBN_MAX_SCENES; ++k) v = k == j ? a[k] : v;
-    return v;
-}
-
 struct SceneRef { int scene, point_base, sp_base, sp_cap; };
 
 // the scene that owns merged point `pt` (-1: none): the last j with point_start[j] <= pt -- B + 1 comparisons
@@ -38,7 +30,7 @@ __device__ __forceinline__ SceneRef scene_of_point(const pbn_scene_table& T, lon
 #pragma unroll
     for (int j = 1; j < PBN_MAX_SCENES; ++j)
         if (j < T.n_scenes && pt >= T.point_start[j]) r = SceneRef{j, T.point_start[j], T.sp_start[j], T.sp_start[j + 1] - T.sp_start[j]};
-    if (pt < T.point_start[0] || pt >= table_at(T.point_start, T.n_scenes)) r.scene = -1;
+    if (pt < T.point_start[0] || pt >= start_of(T.point_start, T.n_scenes)) r.scene = -1;
     return r;
 }
 
@@ -56,7 +48,7 @@ __device__ __forceinline__ FoldRef fold_of_point(const pbn_scene_table& T, int c
             base = T.point_start[j];
             n = T.point_start[j + 1] - T.point_start[j];
         }
-    if (pt < (long long)copies * T.point_start[0] || pt >= (long long)copies * table_at(T.point_start, T.n_scenes))
+    if (pt < (long long)copies * T.point_start[0] || pt >= (long long)copies * start_of(T.point_start, T.n_scenes))
         return FoldRef{-1, 0};
     int local = (int)(pt - (long long)copies * base);              // < copies * n_j <= the merged point count: an int
     for (int c = 1; c < copies; ++c) local -= local >= n ? n : 0;
@@ -65,14 +57,7 @@ __device__ __forceinline__ FoldRef fold_of_point(const pbn_scene_table& T, int c
 
 // the scene whose vote slice holds table row `row` (0 <= row < sp_start[B]); slices of capacity 0 are stepped over
 __device__ __forceinline__ int scene_of_vote_row(const pbn_scene_table& T, int row) {
-    int s = 0;
-#pragma unroll
-    for (int j = 1; j < PBN_MAX_SCENES; ++j) s = (j < T.n_scenes && row >= T.sp_start[j]) ? j : s;
-    return s;
-}
-
-__device__ __forceinline__ long long load_index(const void* p, int is_i64, long long i) {
-    return is_i64 ? ((const long long*)p)[i] : (long long)((const int*)p)[i];
+    return scene_of_folded(T.sp_start, T.n_scenes, row);
 }
 
 // prop_scene[p] = scene of the first member, in unfolded numbering (-1: no first member, or it lies in no scene); score[p] = clt_score[p] as fp32
@@ -161,21 +146,13 @@ __global__ __launch_bounds__(64) void k_pb_iou(const unsigned* __restrict__ mask
         const int i = local / n, k = local - i * n;
         const int ri = rows[(size_t)scene * cap + i], rk = rows[(size_t)scene * cap + k];
         if (ri < 0 || ri >= cap || rk < 0 || rk >= cap) continue;
-        const unsigned* a = masks + (size_t)ri * pitch;
-        const unsigned* b = masks + (size_t)rk * pitch;
-        int c = 0;
-        for (int w = threadIdx.x; w < pitch; w += 64) c += __popc(a[w] & b[w]);
-        c = wave_reduce_add(c);
-        if (threadIdx.x == 0) {
-            const float inter = (float)c;
-            iou[(size_t)(row_base + i) * cap + k] = inter / (((float)counts[ri] + (float)counts[rk]) - inter);
-        }
+        const int c = mask_pair_intersection(masks + (size_t)ri * pitch, masks + (size_t)rk * pitch, pitch);
+        if (threadIdx.x == 0) iou[(size_t)(row_base + i) * cap + k] = mask_pair_iou(c, counts[ri], counts[rk]);
     }
 }
 
-// k_post_nms per scene (workgroup = scene): the same walk -- score descending, among equal scores the lower position in the
-// scene's own survivor list first; a survivor is picked when no earlier pick has iou > nms_t (fp32 `>`).
-// pick_rows[scene, :] = the picked proposals in pick order, tail -1; n_pick[scene]
+// k_post_nms per scene (workgroup = scene): nms_walk (post_dev.h) over the scene's own survivor list and its block of the IoU
+// table.  pick_rows[scene, :] = the picked proposals in pick order, tail -1; n_pick[scene]
 __global__ __launch_bounds__(TPB) void k_pb_nms(const float* __restrict__ score, const int* __restrict__ rows,
                                                const int* __restrict__ n_rows_dev, int cap, const float* __restrict__ iou,
                                                float nms_t, int* __restrict__ pick_rows, int* __restrict__ n_pick_dev) {
@@ -186,38 +163,8 @@ __global__ __launch_bounds__(TPB) void k_pb_nms(const float* __restrict__ score,
     int row_base = 0;
     for (int j = 0; j < scene; ++j) row_base += max(0, min(n_rows_dev[j], cap - row_base));
     const int n = max(0, min(n_rows_dev[scene], cap - row_base));
-    const int* my_rows = rows + (size_t)scene * cap;
-    int* my_pick = pick_rows + (size_t)scene * cap;
-    for (int i = threadIdx.x; i < n; i += TPB) {
-        const int r = my_rows[i];
-        s_score[i] = (r >= 0 && r < cap) ? score[r] : -INFINITY;
-        s_order[i] = (unsigned short)i;            // every slot names a survivor even if the ranks were no permutation (NaN)
-        s_supp[i] = 0;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < n; i += TPB) {
-        const float si = s_score[i];
-        int rank = 0;
-        for (int j = 0; j < n; ++j) {              // every lane reads the same word: an LDS broadcast
-            const float sj = s_score[j];
-            rank += (sj > si || (sj == si && j < i)) ? 1 : 0;
-        }
-        s_order[rank] = (unsigned short)i;
-    }
-    __syncthreads();
-    int n_pick = 0;
-    for (int k = 0; k < n; ++k) {
-        const int it = s_order[k];
-        if (s_supp[it]) continue;                  // uniform: every thread reads the same flag
-        if (threadIdx.x == 0) my_pick[n_pick] = my_rows[it];
-        ++n_pick;
-        // `it` itself is left alone: a thread that has not read its flag yet must still see it clear
-        const float* row = iou + (size_t)(row_base + it) * cap;
-        for (int j = threadIdx.x; j < n; j += TPB)
-            if (j != it && row[j] > nms_t) s_supp[j] = 1;
-        __syncthreads();
-    }
-    for (int k = n_pick + threadIdx.x; k < cap; k += TPB) my_pick[k] = -1;
+    const int n_pick = nms_walk(s_score, s_order, s_supp, score, rows + (size_t)scene * cap, n, cap, iou + (size_t)row_base * cap,
+                                nms_t, nullptr, pick_rows + (size_t)scene * cap);
     if (threadIdx.x == 0) n_pick_dev[scene] = n_pick;
 }
 
@@ -302,14 +249,7 @@ __global__ __launch_bounds__(TPB) void k_pb_relabel(const int* __restrict__ sp_l
         }
         seg_refined[pt] = l;
     }
-    unsigned long long todo = __ballot(bin >= 0);
-    while (todo) {                                 // uniform: every lane of the wave is here
-        const int leader = __ffsll((long long)todo) - 1;
-        const int lb = __shfl(bin, leader);
-        const unsigned long long same = __ballot(bin == lb) & todo;
-        if (lane_id() == leader) atomicAdd(&counts2[lb], __popcll(same));
-        todo &= ~same;
-    }
+    wave_merged_add(counts2, bin);                 // uniform: every lane of the wave is here
 }
 
 // k_post_compact per scene (workgroup = scene): the picks that still own a point, in pick order, renumbered from 0
@@ -342,14 +282,8 @@ __global__ __launch_bounds__(TPB) void k_pb_compact(const int* __restrict__ coun
             float sc = 0.f;
             if (p >= 0 && p < cap) {
                 sc = score[p];
-                const long long e = load_index(offsets, offsets_i64, p);
-                if (e >= 0 && e < n_entries) {
-                    const long long pt = proposals_idx[2 * e + 1];
-                    if (pt >= 0 && pt < n_points) {
-                        const long long s = load_index(pred_sem, sem_i64, pt);
-                        if (s >= 0 && s < n_labels) cls = label_table[s];
-                    }
-                }
+                cls = first_member_class(proposals_idx, n_entries, offsets, offsets_i64, p, pred_sem, sem_i64, n_points, label_table,
+                                         n_labels);
             }
             if (cls < 0) atomicOr(&status[scene], POST_STATUS_CLASS);
             scores_out[at + base + pos] = sc;
@@ -459,7 +393,7 @@ int post_batch_run(const int64_t* proposals_idx, int n_entries, const void* prop
     if (!point_instance || !scalars || (n_sp_total > 0 && !superpoint)) return PBN_ERR_ARG;
     const int nb_points = cdiv(n_points_total, TPB);
     if (n_prop == 0) {
-        hipLaunchKernelGGL(k_pb_empty, dim3(nb_points < 2048 ? nb_points : 2048), dim3(TPB), 0, stream, n_points_total, 2 * B,
+        hipLaunchKernelGGL(k_pb_empty, dim3(stride_blocks(n_points_total)), dim3(TPB), 0, stream, n_points_total, 2 * B,
                            point_instance, scalars);
         PBN_LAUNCH_CHECK();
         return PBN_OK;
@@ -506,8 +440,8 @@ int post_batch_run(const int64_t* proposals_idx, int n_entries, const void* prop
     hipLaunchKernelGGL(k_pb_nms, dim3(B), dim3(TPB), 0, stream, score, rows, n_rows, n_prop, iou, nms_t, pick_rows, n_pick);
     const long long clear_max = (long long)n_sp_total * (n_prop + 1) > (long long)B * n_prop ? (long long)n_sp_total * (n_prop + 1)
                                                                                               : (long long)B * n_prop;
-    hipLaunchKernelGGL(k_pb_clear, dim3((unsigned)(clear_max / TPB + 1 < 2048 ? clear_max / TPB + 1 : 2048)), dim3(TPB), 0, stream,
-                       n_pick, n_prop, scenes, votes, counts2);
+    // + 1: clear_max / TPB + 1 blocks, as pbn_superpoint_refine_dev sizes its clear
+    hipLaunchKernelGGL(k_pb_clear, dim3(stride_blocks(clear_max + 1)), dim3(TPB), 0, stream, n_pick, n_prop, scenes, votes, counts2);
     hipLaunchKernelGGL(k_pb_paint_vote, dim3(nb_points), dim3(TPB), 0, stream, masks, pick_rows, n_pick, n_prop, pitch,
                        n_points_total, scenes, (const long long*)superpoint, seg, votes, status);
     if (n_sp_total > 0)

@@ -63,22 +63,6 @@ __device__ __forceinline__ Kept kept_of_scene(const int* __restrict__ post_scala
     return r;
 }
 
-// the scene that owns folded point `pt` (0 <= pt < point_start[B]): the last j with point_start[j] <= pt, so an empty scene is
-// stepped over
-__device__ __forceinline__ int scene_of_folded(const pbn_tta_table& U, int pt) {
-    int s = 0;
-#pragma unroll
-    for (int j = 1; j < PBN_MAX_SCENES; ++j) s = (j < U.n_scenes && pt >= U.point_start[j]) ? j : s;
-    return s;
-}
-
-__device__ __forceinline__ int start_of(const pbn_tta_table& U, int j) {
-    int v = U.point_start[0];
-#pragma unroll
-    for (int k = 1; k <= PBN_MAX_SCENES; ++k) v = k == j ? U.point_start[k] : v;
-    return v;
-}
-
 __global__ __launch_bounds__(TPB) void k_summary_clear(unsigned* __restrict__ acc, long long n_words, int stride,
                                                       int* __restrict__ status, int n_scenes) {
     const long long first = (long long)blockIdx.x * TPB + threadIdx.x, step = (long long)gridDim.x * TPB;
@@ -110,10 +94,10 @@ __global__ __launch_bounds__(TPB) void k_summary_points(const T* __restrict__ sc
                                                        int* __restrict__ sem_fold, unsigned* __restrict__ acc,
                                                        int* __restrict__ status) {
     __shared__ __attribute__((aligned(8))) unsigned s_acc[ACC_LDS_WORDS];
-    const int n_total = start_of(U, U.n_scenes);
+    const int n_total = start_of(U.point_start, U.n_scenes);
     const int stride = acc_stride(n_cls);
     // the workgroup's own scene: that of its first point (uniform)
-    const int scene0 = scene_of_folded(U, blockIdx.x * TPB);
+    const int scene0 = scene_of_folded(U.point_start, U.n_scenes, blockIdx.x * TPB);
     Kept kept0{0, 0};
     if (n_prop > 0) kept0 = kept_of_scene(post_scalars, U.n_scenes, n_prop, scene0);
     const bool lds = kept0.n > 0 && kept0.n <= lds_instances;
@@ -123,8 +107,8 @@ __global__ __launch_bounds__(TPB) void k_summary_points(const T* __restrict__ sc
 
     const int pt = blockIdx.x * TPB + threadIdx.x;
     if (pt < n_total) {
-        const int scene = scene_of_folded(U, pt);
-        const int p0 = start_of(U, scene), n_j = start_of(U, scene + 1) - p0;
+        const int scene = scene_of_folded(U.point_start, U.n_scenes, pt);
+        const int p0 = start_of(U.point_start, scene), n_j = start_of(U.point_start, scene + 1) - p0;
         const T* row = score + ((size_t)U.copies * p0 + (size_t)(pt - p0)) * ld;
         const size_t copy_step = (size_t)n_j * ld;
         float best = -__builtin_inff();

@@ -6,7 +6,7 @@ What changes against the reference is the data model, not the numbers:
 
 * association: the reference walks the scene once per (prediction, ground-truth instance) pair.  Here the scene's ids are
   turned into indices into their sorted unique list once, and ONE device pass per prediction fills a row of the
-  [predictions, unique ids] overlap table (`pbn_instance_overlap`, csrc/post.hip).  Vertex counts, void overlap and every
+  [predictions, unique ids] overlap table (`pbn_instance_overlap`, csrc/apassoc.hip).  Vertex counts, void overlap and every
   `intersection` field are sums / entries of that integer table.
 * a scene's matches are a `SceneMatches` record of flat arrays instead of dicts of dicts of copies;
   `to_reference()` / `from_reference()` convert to and from the reference's layout so either evaluator accepts either.

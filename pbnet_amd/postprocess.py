@@ -337,41 +337,6 @@ class RefinedBatch(object):
         return (pi[None, :] == torch.arange(k, dtype=torch.int32, device=pi.device)[:, None]).to(torch.int32)
 
 
-def refine_merged_device(sem_pred_p, proposals, clt_scores, point_starts, sp_starts, superpoint, cfg, workspace=None):
-    """`refine_batch_device` on ids that are already merged: `superpoint` int64[N_total] (scene-local ids; rows of scenes with
-    sp_starts[j + 1] == sp_starts[j] are never read; None when no scene has superpoints)."""
-    proposals_idx, proposals_offset = proposals[0], proposals[1]
-    N.require_cuda(proposals_idx, proposals_offset, sem_pred_p, clt_scores, superpoint)
-    _check_merged_inputs(proposals_idx, proposals_offset, sem_pred_p, clt_scores)
-    table = scene_table(point_starts, sp_starts)
-    b, n_total, n_sp_total = table.n_scenes, int(point_starts[-1]), int(sp_starts[-1])
-    if int(sem_pred_p.numel()) != n_total:
-        raise ValueError("sem_pred_p holds %d points, the scene table %d" % (sem_pred_p.numel(), n_total))
-    if n_sp_total > 0:
-        if superpoint is None or superpoint.dtype != torch.int64 or int(superpoint.numel()) < n_total:
-            raise ValueError("superpoint must be an int64 device tensor of %d ids" % n_total)
-    n_prop = max(int(proposals_offset.shape[0]) - 1, 0)
-    lib = N.lib()
-    if n_prop > lib.pbn_post_max_proposals():
-        raise ValueError("the device form takes at most %d proposals, got %d" % (lib.pbn_post_max_proposals(), n_prop))
-    ws = workspace
-    if ws is None:
-        ws = PostBatchWorkspace(n_prop, n_total, b, n_sp_total, proposals_idx.device)
-    elif not ws.fits(n_prop, n_total, b, n_sp_total):
-        raise ValueError("workspace (%d, %d, %d, %d) does not fit (%d, %d, %d, %d)" % (
-            ws.n_prop, ws.n_points_total, ws.n_scenes, ws.n_superpoints_total, n_prop, n_total, b, n_sp_total))
-    res = RefinedBatch(ws, n_prop, point_starts, sp_starts)
-    pidx, off, sem, clt = proposals_idx.contiguous(), proposals_offset.contiguous(), sem_pred_p.contiguous(), clt_scores.contiguous()
-    sp = None if n_sp_total == 0 else superpoint.contiguous()
-    N.check(lib.pbn_post_batch(N.ptr(pidx), int(pidx.shape[0]), N.ptr(off), int(off.dtype == torch.int64), n_prop, N.ptr(clt),
-                               N.DT[clt.dtype], N.ptr(sem), int(sem.dtype == torch.int64), n_total, table, N.ptr(sp),
-                               float(cfg.TEST_SCORE_THRESH), int(cfg.TEST_NPOINT_THRESH), float(cfg.TEST_NMS_THRESH),
-                               N.ptr(ws.label_table), int(ws.label_table.numel()), N.ptr(ws.point_instance), N.ptr(ws.scores),
-                               N.ptr(ws.semantic_id), N.ptr(ws.npoints), N.ptr(ws.scalars), N.ptr(ws.buffer), ws.nbytes,
-                               N.current_stream()), "pbn_post_batch")
-    return res
-
-
 def tta_table(point_starts, sp_starts, copies):
     """The by-value launch argument of pbn_post_batch_tta from two host lists of B + 1 ascending starts over FOLDED points and the
     number of copies of every scene in the merged forward (B * copies batch elements, at most MAX_SCENES)."""
@@ -400,21 +365,22 @@ def _check_merged_inputs(proposals_idx, proposals_offset, sem_pred_p, clt_scores
         raise TypeError("clt_scores must be float32, bfloat16 or float16, got %s" % clt_scores.dtype)
 
 
-def refine_tta_merged_device(sem_pred_p, proposals, clt_scores, point_starts, sp_starts, superpoint, cfg, copies=3, workspace=None):
-    """`refine_merged_device` with the TTA fold (pbn_post_batch_tta): the merged forward holds `copies` copies of each of its B
-    scenes (B * copies <= MAX_SCENES batch elements, scene j's copies one after the other).  `point_starts` / `sp_starts`: B + 1
-    host integers over FOLDED points; sem_pred_p holds copies * point_starts[-1] labels (the class of an instance is read at its
-    unfolded first member, eval_map.py:64); `superpoint` int64[point_starts[-1]], one scene-local id per folded point (None when no
-    scene has any).  Returns a `RefinedBatch` over folded points: scene j's point_instance has n_j entries.  Thirteen launches for
-    all scenes, no host stop; `workspace`: a `PostBatchWorkspace` sized by folded points."""
+def _refine_merged(sem_pred_p, proposals, clt_scores, point_starts, sp_starts, superpoint, cfg, copies, workspace):
+    """Both merged entries: the checks, the workspace fit, the `RefinedBatch` and the call.  copies None: pbn_post_batch on a scene
+    table; an integer: pbn_post_batch_tta on a TTA table over folded points."""
     proposals_idx, proposals_offset = proposals[0], proposals[1]
     N.require_cuda(proposals_idx, proposals_offset, sem_pred_p, clt_scores, superpoint)
     _check_merged_inputs(proposals_idx, proposals_offset, sem_pred_p, clt_scores)
-    table = tta_table(point_starts, sp_starts, copies)
+    if copies is None:
+        entry, table, n_copies = "pbn_post_batch", scene_table(point_starts, sp_starts), 1
+    else:
+        entry, table = "pbn_post_batch_tta", tta_table(point_starts, sp_starts, copies)
+        n_copies = table.copies
     b, n_total, n_sp_total = table.n_scenes, int(point_starts[-1]), int(sp_starts[-1])
-    n_merged = table.copies * n_total
+    n_merged = n_copies * n_total
     if int(sem_pred_p.numel()) != n_merged:
-        raise ValueError("sem_pred_p holds %d points, the table %d x %d" % (sem_pred_p.numel(), table.copies, n_total))
+        raise ValueError("sem_pred_p holds %d points, the scene table %d" % (sem_pred_p.numel(), n_total) if copies is None else
+                         "sem_pred_p holds %d points, the table %d x %d" % (sem_pred_p.numel(), n_copies, n_total))
     if n_sp_total > 0:
         if superpoint is None or superpoint.dtype != torch.int64 or int(superpoint.numel()) < n_total:
             raise ValueError("superpoint must be an int64 device tensor of %d ids" % n_total)
@@ -431,13 +397,29 @@ def refine_tta_merged_device(sem_pred_p, proposals, clt_scores, point_starts, sp
     res = RefinedBatch(ws, n_prop, point_starts, sp_starts)
     pidx, off, sem, clt = proposals_idx.contiguous(), proposals_offset.contiguous(), sem_pred_p.contiguous(), clt_scores.contiguous()
     sp = None if n_sp_total == 0 else superpoint.contiguous()
-    N.check(lib.pbn_post_batch_tta(N.ptr(pidx), int(pidx.shape[0]), N.ptr(off), int(off.dtype == torch.int64), n_prop, N.ptr(clt),
-                                   N.DT[clt.dtype], N.ptr(sem), int(sem.dtype == torch.int64), n_merged, table, N.ptr(sp),
-                                   float(cfg.TEST_SCORE_THRESH), int(cfg.TEST_NPOINT_THRESH), float(cfg.TEST_NMS_THRESH),
-                                   N.ptr(ws.label_table), int(ws.label_table.numel()), N.ptr(ws.point_instance), N.ptr(ws.scores),
-                                   N.ptr(ws.semantic_id), N.ptr(ws.npoints), N.ptr(ws.scalars), N.ptr(ws.buffer), ws.nbytes,
-                                   N.current_stream()), "pbn_post_batch_tta")
+    N.check(getattr(lib, entry)(N.ptr(pidx), int(pidx.shape[0]), N.ptr(off), int(off.dtype == torch.int64), n_prop, N.ptr(clt),
+                                N.DT[clt.dtype], N.ptr(sem), int(sem.dtype == torch.int64), n_merged, table, N.ptr(sp),
+                                float(cfg.TEST_SCORE_THRESH), int(cfg.TEST_NPOINT_THRESH), float(cfg.TEST_NMS_THRESH),
+                                N.ptr(ws.label_table), int(ws.label_table.numel()), N.ptr(ws.point_instance), N.ptr(ws.scores),
+                                N.ptr(ws.semantic_id), N.ptr(ws.npoints), N.ptr(ws.scalars), N.ptr(ws.buffer), ws.nbytes,
+                                N.current_stream()), entry)
     return res
+
+
+def refine_merged_device(sem_pred_p, proposals, clt_scores, point_starts, sp_starts, superpoint, cfg, workspace=None):
+    """`refine_batch_device` on ids that are already merged: `superpoint` int64[N_total] (scene-local ids; rows of scenes with
+    sp_starts[j + 1] == sp_starts[j] are never read; None when no scene has superpoints)."""
+    return _refine_merged(sem_pred_p, proposals, clt_scores, point_starts, sp_starts, superpoint, cfg, None, workspace)
+
+
+def refine_tta_merged_device(sem_pred_p, proposals, clt_scores, point_starts, sp_starts, superpoint, cfg, copies=3, workspace=None):
+    """`refine_merged_device` with the TTA fold (pbn_post_batch_tta): the merged forward holds `copies` copies of each of its B
+    scenes (B * copies <= MAX_SCENES batch elements, scene j's copies one after the other).  `point_starts` / `sp_starts`: B + 1
+    host integers over FOLDED points; sem_pred_p holds copies * point_starts[-1] labels (the class of an instance is read at its
+    unfolded first member, eval_map.py:64); `superpoint` int64[point_starts[-1]], one scene-local id per folded point (None when no
+    scene has any).  Returns a `RefinedBatch` over folded points: scene j's point_instance has n_j entries.  Thirteen launches for
+    all scenes, no host stop; `workspace`: a `PostBatchWorkspace` sized by folded points."""
+    return _refine_merged(sem_pred_p, proposals, clt_scores, point_starts, sp_starts, superpoint, cfg, copies, workspace)
 
 
 def superpoint_starts(point_starts, has_superpoints, n_superpoints=None):

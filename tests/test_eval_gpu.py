@@ -177,3 +177,33 @@ def test_ground_truth_as_prediction_scores_one():
     kept = [li for li in present if any((gt == i).sum() // 2 >= E.MIN_REGION_SIZE for i in big if E._CLASS_OF_ID[i // 1000] == li)]
     for li in kept:
         assert ap2[0, li, 0] == 0.0 and ap2[0, li, o25] > 0.0, li
+
+
+@pytest.mark.parametrize("n_gt", [5, 8193], ids=["lds_bins", "global_bins"])
+def test_overlap_entry_against_numpy(n_gt):
+    """pbn_instance_overlap itself on both of its paths (bins in LDS up to 8192 instances, global atomics above): a point
+    count that is no multiple of the block or the chunk, index entries outside [0, n_gt) that must count for nothing, an
+    empty prediction; and the same bytes on a second call into a table that is not zero."""
+    from pbnet_amd import _native as N
+    rng = np.random.default_rng(n_gt)
+    n_pred, n_pts = 3, 4096 + 257
+    gt_index = rng.integers(0, n_gt, n_pts).astype(np.int32)
+    gt_index[rng.random(n_pts) < 0.1] = -1
+    gt_index[rng.random(n_pts) < 0.1] = n_gt + rng.integers(0, 3)
+    gt_index[[0, n_pts - 1]] = [n_gt - 1, 0]
+    masks = (rng.random((n_pred, n_pts)) < 0.5).astype(np.int32) * rng.integers(1, 4, (n_pred, n_pts)).astype(np.int32)
+    masks[1] = 0
+    want = np.zeros((n_pred, n_gt), np.int32)
+    p, i = np.nonzero(masks)
+    ok = (gt_index[i] >= 0) & (gt_index[i] < n_gt)
+    np.add.at(want, (p[ok], gt_index[i[ok]]), 1)
+    assert want[0].sum() > 0 and want[1].sum() == 0
+    m, idx = torch.from_numpy(masks).to(DEV), torch.from_numpy(gt_index).to(DEV)
+    inter = torch.full((n_pred, n_gt), 7, dtype=torch.int32, device=DEV)
+    got = []
+    for _ in range(2):
+        N.check(N.lib().pbn_instance_overlap(N.ptr(m), n_pred, n_pts, N.ptr(idx), n_gt, N.ptr(inter), N.current_stream()),
+                "pbn_instance_overlap")
+        got.append(inter.cpu().numpy())
+    assert np.array_equal(got[0], want)
+    assert got[0].tobytes() == got[1].tobytes()
