@@ -657,8 +657,8 @@ int pbn_scene_summary(const void* sem_score, int ld, int n_cls, int score_dtype,
  *              datasets/scannetv2/get_val_gt.py:26-39 -- stay on the host)
  *   inter    : int32[n_pred, n_gt] out (zeroed here).  Row sums are the predictions' vertex counts (:227), columns of
  *              non-benchmark ids sum to the void intersection (:235), the rest are the `intersection` fields (:239).
- * Matching and the precision/recall integration (eval.py:27-190) are scalar bookkeeping on these counts and run on
- * the host (pbnet_amd/evaluate.py). */
+ * Matching and the precision/recall integration (eval.py:27-190) are integer bookkeeping on these counts: on the host in
+ * pbnet_amd/evaluate.py (evaluate_matches, the default), or on the device from the epoch log (pbn_ap_table_*, below). */
 int pbn_instance_overlap(const int32_t* masks, int n_pred, int n_pts, const int32_t* gt_index, int n_gt, int32_t* inter,
                          pbn_stream_t stream);
 
@@ -745,6 +745,75 @@ int pbn_ap_assoc_batch(pbn_tta_table units, const int32_t* point_instance, const
                        const void* ins, int ins_i64, const int32_t* label_table, int n_labels, int u_cap, int id_cap,
                        int n_inst_cap, pbn_ap_scene_tags tags, int32_t* state, int32_t* log, int64_t log_words, void* workspace,
                        size_t workspace_bytes, pbn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * The AP table on the device (csrc/apeval.hip; pbnet_amd/evaluate.py APTable): the reference's tools/eval.py:27-190
+ * (`evaluate_matches`) on association logs where they lie -- what comes back is ap[n_classes, n_overlaps] instead of the logs.
+ * The table accumulates in a caller-owned workspace (pbn_ap_table_workspace_bytes(rec_cap, entry_cap), host-only, 0 for
+ * capacities outside the supported range): rec_cap records over all logs of the epoch, entry_cap (score, true) entries over all
+ * cells; the predictions of ONE log's usable records need a row each in the same capacity.  A prediction emits at most one
+ * entry per overlap >= 0.5 and at most three at 0.25 (instances are disjoint and IoU > th forces inter > th * vertices), so
+ * 12 * (sum of n_keep) entries are always enough.  Either overflow is sticky, reported in the scalar block with the wanted count
+ * and never a write out of bounds; the results are then not valid.
+ *   pbn_ap_table_reset   : clears the accumulated state (one launch).
+ *   pbn_ap_table_add_log : one log (log_state = the int32[8] state block of pbn_ap_record_append, read on the device: the
+ *                          used words, and its overflow flag, with which the log is refused as AssociationLog.read_log refuses
+ *                          it).  Three launches: (a) ONE wave walks the record headers and appends offset | tag + tag_base |
+ *                          status | n_keep per record to the directory (offset = the record's word in the concatenation of the
+ *                          logs added so far); a record that is not whole stops the walk (scalar `malformed` = 1 and its word;
+ *                          2 = a record with more than 65535 predictions, which no writer here produces); records with status
+ *                          bits or n_keep == 0 are listed and take no part.  (b) per prediction of a usable record: its class
+ *                          (index of label_id in `classes`, -1 if absent), its vertex count (row sum over ALL n_gt columns; kept
+ *                          when the class is >= 0 and the count >= min_region), and void + too-small same-class overlap; per
+ *                          class has_pred (a kept prediction) and has_gt (an instance column -- uid != 0, class of uid / 1000 >=
+ *                          0 -- with uid >= 1000 and gt_vert >= min_region).  (c) one wave per (record, overlap): over[q, g] =
+ *                          inter > 0 and (double) inter / max(pred_vert + gt_vert - inter, 1) > th for same-class pairs, a
+ *                          plain IEEE division and a strict >; for every instance that counts, in column order, predictions in
+ *                          prediction order: the first unvisited one with `over` is marked visited and becomes `best`, every
+ *                          later hit emits (0, min(best, conf)), raises best and stays unvisited; then (1, best), or one
+ *                          hard_fn without a hit.  visited persists over the record's instances at that overlap.  A kept
+ *                          prediction without `over` against any same-class instance, small ones included, emits (0, conf)
+ *                          when (double)(void + too-small overlap) / vertices <= th.  Entries go to one table as (cell = class *
+ *                          n_overlaps + overlap, score bits, true).  A wave keeps visited and the class, instance and counts bits
+ *                          of the record's first 4096 columns in LDS; columns beyond are classified where they are met.
+ *   pbn_ap_table_finish  : four launches: segment starts, entries into their cells' segments, ONE workgroup per cell, the
+ *                          outputs.  A cell's entries are sorted by (score, true) -- in LDS up to pbn_ap_table_lds_entries()
+ *                          entries, in place in global memory above, the same network -- and integrated in float64 in ascending
+ *                          distinct-score order as eval.py:131-176 does: first position of every distinct score, true matches
+ *                          scored strictly lower, tp / fp / fn, precision with the artificial last point 1, recall with 0, the
+ *                          [-0.5, 0, 0.5] widths, the sum (each thread its strided terms, then a fixed tree).  ap float32
+ *                          [n_classes * n_overlaps]: NaN without has_gt, 0 with has_gt alone or without entries; cells int32
+ *                          [n_classes * n_overlaps][4] = entries | true entries | hard_fn | distinct scores; flags int32[2 *
+ *                          n_classes] = has_gt | has_pred; directory int32[rec_cap][4], zero past the records; scalars
+ *                          int32[PBN_AP_TABLE_SCALARS] = records | records wanted | entries wanted | prediction rows wanted (the
+ *                          largest log) | overflow bits (1 records, 2 entries, 4 prediction rows) | malformed | its word | a log
+ *                          had overflowed | the words that log wanted | words walked | first record of the last log | logs.
+ *                          The table stays as it was: more logs may follow, and a second call gives the same bytes.
+ * Integer atomics only; the order in which entries arrive depends on them, the outputs do not (the sort key is total and equal
+ * keys are equal entries): two runs give the same bytes.  Nothing waits for the host.  All before any launch: PBN_ERR_ARG for a
+ * missing pointer, a capacity below 1, counts outside [1, PBN_AP_MAX_CLASSES] / [1, PBN_AP_MAX_OVERLAPS], a class id below 1 (0 is
+ * the unannotated id), a negative tag_base or min_region, an overlap outside [0, 1]; PBN_ERR_RANGE for entry_cap >= 2^30, rec_cap >= 2^29 or log_words >= 2^31;
+ * PBN_ERR_WORKSPACE for a workspace that is too small. */
+#define PBN_AP_MAX_CLASSES 32
+#define PBN_AP_MAX_OVERLAPS 16
+#define PBN_AP_TABLE_SCALARS 16
+typedef struct pbn_ap_class_ids {
+    int32_t n;
+    int32_t id[PBN_AP_MAX_CLASSES];
+} pbn_ap_class_ids;
+typedef struct pbn_ap_overlaps {
+    int32_t n;
+    int32_t _pad;
+    double th[PBN_AP_MAX_OVERLAPS];
+} pbn_ap_overlaps;
+size_t pbn_ap_table_workspace_bytes(int rec_cap, int64_t entry_cap);
+int pbn_ap_table_lds_entries(void);
+int pbn_ap_table_reset(void* workspace, size_t workspace_bytes, int rec_cap, int64_t entry_cap, pbn_stream_t stream);
+int pbn_ap_table_add_log(void* workspace, size_t workspace_bytes, int rec_cap, int64_t entry_cap, const int32_t* log_state,
+                         const int32_t* log, int64_t log_words, int tag_base, pbn_ap_class_ids classes, pbn_ap_overlaps overlaps,
+                         int min_region, pbn_stream_t stream);
+int pbn_ap_table_finish(void* workspace, size_t workspace_bytes, int rec_cap, int64_t entry_cap, int n_classes, int n_overlaps,
+                        float* ap, int32_t* cells, int32_t* flags, int32_t* directory, int32_t* scalars, pbn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * One-call sub-pipelines (csrc/executor.hip): they only sequence the entry points above.

@@ -108,6 +108,19 @@ class SceneTags(ctypes.Structure):
     _fields_ = [("tag", c_i32 * MAX_SCENES)]
 
 
+AP_MAX_CLASSES, AP_MAX_OVERLAPS, AP_TABLE_SCALARS = 32, 16, 16      # PBN_AP_MAX_CLASSES / _OVERLAPS, PBN_AP_TABLE_SCALARS
+
+
+class ApClassIds(ctypes.Structure):
+    """pbn_ap_class_ids (include/pbnet_hip.h)."""
+    _fields_ = [("n", c_i32), ("id", c_i32 * AP_MAX_CLASSES)]
+
+
+class ApOverlaps(ctypes.Structure):
+    """pbn_ap_overlaps (include/pbnet_hip.h)."""
+    _fields_ = [("n", c_i32), ("_pad", c_i32), ("th", ctypes.c_double * AP_MAX_OVERLAPS)]
+
+
 class PostBatchLayout(ctypes.Structure):
     """pbn_post_batch_layout (include/pbnet_hip.h)."""
     _fields_ = [(k, c_i64) for k in ("masks", "counts", "prop_scene", "score", "rows", "pick_rows", "n_rows", "n_pick", "iou",
@@ -192,6 +205,12 @@ SIGNATURES = {
     "pbn_ap_assoc_batch_lds_counters": (c_int, []),
     "pbn_ap_assoc_batch": (c_int, [TtaTable, c_i32p, c_i32p, c_f32p, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_i32p,
                                    c_int, c_int, c_int, c_int, SceneTags, c_i32p, c_i32p, c_i64, c_vp, c_size, c_vp]),
+    "pbn_ap_table_workspace_bytes": (c_size, [c_int, c_i64]),
+    "pbn_ap_table_lds_entries": (c_int, []),
+    "pbn_ap_table_reset": (c_int, [c_vp, c_size, c_int, c_i64, c_vp]),
+    "pbn_ap_table_add_log": (c_int, [c_vp, c_size, c_int, c_i64, c_i32p, c_i32p, c_i64, c_int, ApClassIds, ApOverlaps, c_int,
+                                     c_vp]),
+    "pbn_ap_table_finish": (c_int, [c_vp, c_size, c_int, c_i64, c_int, c_int, c_f32p, c_i32p, c_i32p, c_i32p, c_i32p, c_vp]),
     "pbn_rulebook_pair_blocks": (c_int, [c_int]),
     "pbn_bn_workspace_bytes": (c_size, [c_int]),
     "pbn_bn_train_forward": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_f32p, c_f32p, ctypes.c_float, ctypes.c_float, c_f32p,

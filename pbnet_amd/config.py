@@ -13,8 +13,10 @@ TRAIN_DEFAULTS = dict(task="train", manual_seed=22, voxel_size=0.02, scale_size=
                       device_meters=False,      # not the reference's: model_fn leaves the logged terms on the device
                       native_optimizer=False,   # not the reference's: optim.build_optimizer builds pbnet_amd.optim's classes
                       device_post=False,        # not the reference's: ValidationEpoch refines through refine_instances_device
-                      device_ap=False)          # not the reference's: ValidationEpoch associates on the device as well (needs
+                      device_ap=False,          # not the reference's: ValidationEpoch associates on the device as well (needs
                                                 # device_post): evaluate.AssociationLog, read back once by finish()
+                      device_ap_table=False)    # not the reference's: finish() matches and integrates on the device too (needs
+                                                # device_ap): evaluate.APTable reads the log where it lies
 TEST_OVERRIDES = dict(task="test", batch_size=1, cluster_epoch=-1)
 
 

@@ -14,8 +14,10 @@ What changes against the reference is the data model, not the numbers:
 * `AssociationLog` is the association without a host stop (csrc/apassoc.hip): ids numbered and tables filled on the device, one
   compact record per scene in an epoch log that `collect()` reads back once and `decode_association_log` turns into the same
   `SceneMatches`.
+* `APTable` is `evaluate_matches` without reading the log back (csrc/apeval.hip): the records are matched and the curves
+  integrated on the device, and what comes back is the AP table.  Off unless asked for; the host functions are the default.
 
-Everything here except the overlap table is host bookkeeping on a few hundred integers, as in the reference."""
+Everything else here except the overlap table is host bookkeeping on a few hundred integers, as in the reference."""
 import numpy as np
 import torch
 
@@ -197,6 +199,14 @@ AP_STATUS = ((1, "a superpoint id is >= n_superpoints"),
 AP_STATUS_ID_RANGE, AP_STATUS_ID_COUNT, AP_STATUS_LABEL_RANGE, AP_STATUS_INSTANCE_CAP, AP_STATUS_SEMANTIC_RANGE = 4, 8, 16, 32, 64
 
 
+def _status_reasons(status):
+    """The texts of a record's status bits, empty for a clean record."""
+    reasons = [text for bit, text in AP_STATUS if status & bit]
+    if status & ~sum(bit for bit, _ in AP_STATUS):
+        reasons.append("unknown status bits 0x%x" % status)
+    return reasons
+
+
 def _walk_association_log(words, names):
     """Generator over the records of an association log in log order: (tag, scene name, reasons of its status bits, SceneMatches
     or None for a header-only record).  ValueError for a log that is not a sequence of whole records."""
@@ -211,9 +221,7 @@ def _walk_association_log(words, names):
         if n_keep < 0 or n_gt < 0 or size != want or pos + size > end:
             raise ValueError("%s: the record at word %d is malformed (n_keep %d, n_gt %d, %d words, %d left)"
                              % (scene, pos, n_keep, n_gt, size, end - pos))
-        reasons = [text for bit, text in AP_STATUS if status & bit]
-        if status & ~sum(bit for bit, _ in AP_STATUS):
-            reasons.append("unknown status bits 0x%x" % status)
+        reasons = _status_reasons(status)
         rec = None
         if n_keep and not reasons:
             body = words[pos + AP_RECORD_HEADER:pos + size]
@@ -455,6 +463,140 @@ def _word_ptr(t, i):
     return N.c_vp(t.data_ptr() + i * t.element_size())
 
 
+class APTableOverflow(RuntimeError):
+    """A capacity of an `APTable` did not hold the epoch.  `rec_cap` / `entry_cap`: capacities that hold what this attempt could
+    count (records that did not fit were not matched, so their entries are not in the count yet)."""
+
+    def __init__(self, message, rec_cap, entry_cap):
+        RuntimeError.__init__(self, message)
+        self.rec_cap, self.entry_cap = int(rec_cap), int(entry_cap)
+
+
+class APTable(object):
+    """`evaluate_matches` on the device (csrc/apeval.hip, pbn_ap_table_*): association logs are read where they lie, matched
+    and integrated there, and `finish` reads back the table instead of the logs.  `add` does not synchronise and reads nothing
+    back; `finish` is the one read-back: the scalar block, the AP cells, the cell counts and four words per record.
+
+    Capacities: `rec_cap` records over all logs added, `entry_cap` (score, true) entries over all cells; the predictions of one
+    log need a row each in the same capacity.  12 * (sum of n_keep) entries are always enough (include/pbnet_hip.h); the default
+    allows 64 kept predictions per record on average.  Either overflow is reported by `finish` with the wanted capacity
+    (`APTableOverflow`; `ap_table_of_logs` answers it by matching the logs again with that capacity)."""
+
+    def __init__(self, rec_cap, entry_cap=None, device=None):
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.rec_cap = int(rec_cap)
+        self.entry_cap = 12 * 64 * self.rec_cap if entry_cap is None else int(entry_cap)
+        self.n_classes, self.n_overlaps = len(CLASS_LABELS), len(OVERLAPS)
+        self.ws_bytes = int(N.lib().pbn_ap_table_workspace_bytes(self.rec_cap, self.entry_cap))
+        if self.ws_bytes == 0:
+            raise ValueError("no AP table for rec_cap %d and entry_cap %d" % (self.rec_cap, self.entry_cap))
+        self.ws = torch.zeros(self.ws_bytes, dtype=torch.uint8, device=self.device)
+        self._classes, self._overlaps = N.ApClassIds(), N.ApOverlaps()
+        self._classes.n, self._overlaps.n = self.n_classes, self.n_overlaps
+        for i, c in enumerate(VALID_CLASS_IDS):
+            self._classes.id[i] = int(c)
+        for i, th in enumerate(OVERLAPS):
+            self._overlaps.th[i] = float(th)                # the np.arange doubles themselves, e.g. 0.6000000000000001
+        cells = self.n_classes * self.n_overlaps
+        # scalars | ap (float32 bits) | cells | flags | directory: one buffer, one read-back
+        self._parts = np.cumsum([0, N.AP_TABLE_SCALARS, cells, 4 * cells, 2 * self.n_classes, 4 * self.rec_cap])
+        self.out = torch.zeros(int(self._parts[-1]), dtype=torch.int32, device=self.device)
+        self.readback_bytes = 4 * int(self._parts[-1])
+        self.names, self.flags, self.scalars, self.directory = [], None, None, None
+        self.reset()
+
+    def reset(self):
+        """Forget the epoch: one launch, no synchronisation."""
+        N.check(N.lib().pbn_ap_table_reset(N.ptr(self.ws), self.ws_bytes, self.rec_cap, self.entry_cap, N.current_stream()),
+                "pbn_ap_table_reset")
+        self.names = []
+
+    def add(self, log):
+        """Match the records of an `AssociationLog` into the table.  Enqueued on the current stream, which must come after the
+        stream that wrote the log; the log is only read."""
+        self.add_words(log.log, log.state, log.log_words, log.names)
+
+    def add_words(self, words, state, log_words, names, tag_base=None):
+        """`add` on the parts of a log: `words` int32 [>= log_words] and `state` int32 [8] on the device (state[0] = the used
+        words, state[3] = the log's overflow flag, state[1] the words it wanted), `names[tag]` the scenes' names.  The records'
+        tags are shifted by `tag_base`, default the names held so far, so that they index `self.names`."""
+        N.require_cuda(words, state)
+        if words.dtype != torch.int32 or state.dtype != torch.int32 or int(state.numel()) < 4 or int(words.numel()) < log_words:
+            raise TypeError("a log is int32 words with an int32 state block of at least 4 words")
+        N.check(N.lib().pbn_ap_table_add_log(N.ptr(self.ws), self.ws_bytes, self.rec_cap, self.entry_cap, N.ptr(state),
+                                             N.ptr(words), int(log_words), len(self.names) if tag_base is None else int(tag_base),
+                                             self._classes, self._overlaps,
+                                             MIN_REGION_SIZE, N.current_stream()), "pbn_ap_table_add_log")
+        self.names.extend(names)
+
+    def finish(self):
+        """Integrate and read back.  Returns (ap float32 [1, classes, overlaps] as `evaluate_matches` gives it, names of the
+        scenes without a cluster, [(name, reasons)] of the scenes left out for their status bits, cells int32 [classes,
+        overlaps, 4] = entries | true entries | hard_fn | distinct scores).  RuntimeError when a log had overflowed or a capacity
+        of the table did, with the wanted capacity; ValueError for a log that is not a sequence of whole records."""
+        a = self._parts
+        part = lambda i: _word_ptr(self.out, int(a[i]))                                               # noqa: E731
+        N.check(N.lib().pbn_ap_table_finish(N.ptr(self.ws), self.ws_bytes, self.rec_cap, self.entry_cap, self.n_classes,
+                                            self.n_overlaps, part(1), part(2), part(3), part(4), part(0), N.current_stream()),
+                "pbn_ap_table_finish")
+        host = self.out.cpu().numpy()
+        sc = self.scalars = host[a[0]:a[1]].copy()
+        n_rec, rec_wanted, entries_wanted, preds_wanted, overflow, malformed, malformed_at, log_over, log_wanted = \
+            (int(v) for v in sc[:9])
+        if log_over:
+            raise RuntimeError("an association log overflowed: the epoch wanted %d words" % log_wanted)
+        if malformed == 2:
+            raise ValueError("the record at word %d of log %d has more than 65535 predictions" % (malformed_at, int(sc[11])))
+        if malformed:
+            raise ValueError("an association log is malformed: no whole record at word %d" % malformed_at)
+        # 12 entries per prediction are always enough; a log whose rows did not fit was not matched, so its entries are not counted
+        enough = 12 * preds_wanted * max(int(sc[11]), 1) if overflow & 4 else max(entries_wanted, preds_wanted, self.entry_cap)
+        if overflow & 1:
+            raise APTableOverflow("the AP table overflowed: rec_cap = %d, the epoch wanted %d records" % (self.rec_cap, rec_wanted),
+                                  rec_wanted, enough)
+        if overflow:
+            raise APTableOverflow("the AP table overflowed: entry_cap = %d, the epoch wanted %d entries and its largest log %d "
+                                  "prediction rows" % (self.entry_cap, entries_wanted, preds_wanted), self.rec_cap, enough)
+        ap = host[a[1]:a[2]].view(np.float32).reshape(1, self.n_classes, self.n_overlaps).copy()
+        cells = host[a[2]:a[3]].reshape(self.n_classes, self.n_overlaps, 4).copy()
+        self.flags = host[a[3]:a[4]].reshape(2, self.n_classes).copy()
+        self.directory = host[a[4]:a[5]].reshape(self.rec_cap, 4)[:n_rec].copy()
+        dropped, failed = [], []
+        for _, tag, status, n_keep in self.directory.tolist():
+            scene = self.names[tag] if 0 <= tag < len(self.names) else "<scene tag %d>" % tag
+            reasons = _status_reasons(status)
+            if reasons:
+                failed.append((scene, reasons))
+            elif n_keep == 0:
+                dropped.append(scene)
+        return ap, dropped, failed, cells
+
+
+def ap_table_of_logs(logs, names=None, rec_cap=None, entry_cap=None, device=None):
+    """The `APTable` of an epoch's `AssociationLog`s: (ap, dropped, failed, cells, table).  `names` None: every log's tags count
+    within its own names; else the tags of all logs index `names` (the serving front's global submission numbers).  The
+    capacities are a first guess (default: one record per name, `APTable`'s entries): when the table reports an overflow the
+    logs, which are only read, are matched again into a table of the capacities it asked for -- the records first, then the
+    prediction rows, then the entries -- so an epoch is not lost to a guess.  Each attempt is one read-back."""
+    logs = list(logs)
+    if rec_cap is None:
+        rec_cap = max(sum(len(log.names) for log in logs) if names is None else len(names), 1)
+    device = logs[0].device if device is None and logs else device
+    for attempt in range(4):
+        table = APTable(rec_cap, entry_cap, device=device)
+        if names is not None:
+            table.names = list(names)
+        for log in logs:
+            table.add_words(log.log, log.state, log.log_words, log.names if names is None else (),
+                            tag_base=None if names is None else 0)
+        try:
+            return table.finish() + (table,)
+        except APTableOverflow as e:
+            if attempt == 3:
+                raise
+            rec_cap, entry_cap = e.rec_cap, e.entry_cap
+
+
 # ----------------------------------------------------------------------------------------------------------- AP
 def _as_records(matches):
     out = []
@@ -559,14 +701,16 @@ def compute_averages(aps):
     return avg
 
 
-def evaluate_served(server_or_model, units, cfg, logger=None, tta=3):
+def evaluate_served(server_or_model, units, cfg, logger=None, tta=3, device_table=False):
     """eval_map.py:40-158 on the serving front: every unit is submitted with its ground truth, the front post-processes and
     associates on the device (`SceneServer(..., refine=cfg, association=True)`), and the epoch ends in `evaluate_matches`,
     `compute_averages` and `print_results`.  `units`: (name, unit, gt) triples -- `unit` what `SceneServer.submit` takes (with tta
     the reference's evaluation unit of `tta` rotated copies), `gt` a device id vector over the scene's own points or a (sem, ins)
     pair.  `server_or_model`: a paused or running `SceneServer` built with association=True (it is closed here), or a model, for
     which one is made with refine=cfg and `tta` copies per unit (None: plain scenes).  Scenes without a kept instance are
-    reported and left out (eval_map.py:102-104), as are scenes whose result or record reports an error.  Returns the averages."""
+    reported and left out (eval_map.py:102-104), as are scenes whose result or record reports an error.  Returns the averages.
+    device_table=True: matching and integration run on the device as well (`SceneServer.ap_table`, `APTable`): the logs are not
+    read back, the same lines are reported and the AP cells agree with the default form to one float32 ulp."""
     from .serving import SceneServer
     say = print if logger is None else logger.info
     server = server_or_model
@@ -579,12 +723,15 @@ def evaluate_served(server_or_model, units, cfg, logger=None, tta=3):
     for name, f in futs:
         if f.exception() is not None:
             say("%s: not served: %s" % (name, f.exception()))
-    matches, dropped, failed = server.association()
+    if device_table:
+        ap, dropped, failed, _ = server.ap_table()
+    else:
+        matches, dropped, failed = server.association()
     for name in dropped:
         say("%s: no instance kept, left out" % (name,))
     for name, reasons in failed:
         say("%s: left out: %s" % (name, "; ".join(reasons)))
-    avgs = compute_averages(evaluate_matches(matches))
+    avgs = compute_averages(ap if device_table else evaluate_matches(matches))
     print_results(avgs, logger)
     return avgs
 

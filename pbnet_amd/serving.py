@@ -315,6 +315,26 @@ class SceneServer(object):
         records.sort(key=lambda r: r[0])
         return evaluate._sort_records(records, "skip")
 
+    def ap_table(self, entry_cap=None):
+        """After `close()`: `association()` followed by `evaluate.evaluate_matches`, on the device -- every worker's log is
+        folded into one `evaluate.APTable` where it lies, and one read-back returns (ap float32 [1, classes, overlaps], dropped,
+        failed, cells), the lists in submission order as `association()` gives them.  `entry_cap`: the table's first entry capacity
+        (default: `APTable`'s; a table that overflows is built again with the capacity it asked for).  RuntimeError when a log
+        overflowed."""
+        if not self.association_on:
+            raise ValueError("this server was built without association=True")
+        if not self._closed or any(t.is_alive() for t in self._threads):
+            raise RuntimeError("ap_table() reads the logs after close()")
+        with torch.cuda.device(self.device):
+            torch.cuda.synchronize(self.device)         # the workers' streams wrote the logs; this thread's stream reads them
+            # the records carry the GLOBAL submission number, so every log's tags index self._names
+            ap, _, _, cells, table = evaluate.ap_table_of_logs(self._logs, self._names, entry_cap=entry_cap, device=self.device)
+        dropped = [(tag, self._names[tag]) for _, tag, status, n_keep in table.directory.tolist() if not status and not n_keep]
+        failed = [(number, (self._names[number], [problem])) for number, problem in self._unserved]
+        failed += [(tag, (self._names[tag], evaluate._status_reasons(status)))
+                   for _, tag, status, _ in table.directory.tolist() if status]
+        return ap, [name for _, name in sorted(dropped)], [f for _, f in sorted(failed, key=lambda t: t[0])], cells
+
     def close(self):
         self._closed = True
         self.start()                        # a paused server still serves what was queued

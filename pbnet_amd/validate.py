@@ -298,7 +298,11 @@ class ValidationEpoch(object):
     (`ap_log_words` int32 words) and the loss terms go to a `train_epoch.LossMeter`, both gated on the device by n_keep > 0;
     `finish()` reads the log and the meter once.  One visible difference: the `no cluster` lines (same text, same count) are
     printed by `finish()`, not by the step that met the scene.  `progress=True` still works but reads n_keep and the meters
-    back every step, which gives up the point of the mode."""
+    back every step, which gives up the point of the mode.
+
+    `cfg.device_ap_table` (needs `cfg.device_ap`): `finish()` does not read the log either -- an `evaluate.APTable` matches and
+    integrates on the device and the averages come from its table; `out["matches"]` is then None and `out["ap"]` holds the
+    cells.  Under a process group with more than one rank the epoch keeps the host path and says so in one line."""
 
     def __init__(self, model, cfg, epoch, model_fn=None, gt=None, logger=None, writer=None, reduce=True, device=None,
                  progress=False, ap_log_words=4 << 20):
@@ -310,6 +314,9 @@ class ValidationEpoch(object):
         self.device_ap = bool(getattr(cfg, "device_ap", False))         # absent = off: evaluate.assign_instances_for_scan
         if self.device_ap and not self.device_post:
             raise ValueError("cfg.device_ap needs cfg.device_post: the association reads what refine_instances_device leaves")
+        self.device_ap_table = bool(getattr(cfg, "device_ap_table", False))     # absent = off: evaluate.evaluate_matches
+        if self.device_ap_table and not self.device_ap:
+            raise ValueError("cfg.device_ap_table needs cfg.device_ap: the table reads the association log where it lies")
         self._post_ws, self._staging, self._empty_buf = None, {}, None
         self._ap_log, self._ap_log_words, self._loss_meter, self._meter_in = None, int(ap_log_words), None, None
         self.semantic = SemanticMeter(cfg.sem_num, -100, device=device)
@@ -518,9 +525,22 @@ class ValidationEpoch(object):
         from . import dist as pdist, evaluate
         world = tdist.get_world_size() if (tdist.is_available() and tdist.is_initialized()) else 1
         rank = tdist.get_rank() if world > 1 else 0
+        table_ap = None
         if self.device_ap:
             # the epoch's two read-backs: the association log (records in step order) and the loss meter
-            if self._ap_log is not None:
+            use_table = self.device_ap_table and self._ap_log is not None
+            if use_table and world > 1:
+                self._info("device_ap_table: %d ranks, matching and integration stay on the host" % world)
+                use_table = False
+            if use_table:
+                table_ap, dropped, failed, _, _ = evaluate.ap_table_of_logs([self._ap_log])
+                for scene, reasons in failed:             # as collect() raises for a record with status bits
+                    raise ValueError("%s: %s" % (scene, "; ".join(reasons)))
+                self.matches = None
+                self.no_cluster = len(dropped)
+                for _ in dropped:
+                    print("no cluster")
+            elif self._ap_log is not None:
                 self.matches, dropped = self._ap_log.collect()
                 self.no_cluster = len(dropped)
                 for _ in dropped:
@@ -558,8 +578,10 @@ class ValidationEpoch(object):
             mask = self.mask.result()
             out.update(mask=mask, All_mask_acc=mask["All_mask_acc"], Tp_acc=mask["Tp_acc"], Fp_acc=mask["Fp_acc"])
             scalars += [("val/All_mask_acc", mask["All_mask_acc"]), ("val/Tp_acc", mask["Tp_acc"]), ("val/Fp_acc", mask["Fp_acc"])]
-            if matches is not None:
-                avgs = evaluate.compute_averages(evaluate.evaluate_matches(matches))
+            if table_ap is not None:
+                out["ap"] = table_ap                      # matches stays None: the records never came to the host
+            if matches is not None or table_ap is not None:
+                avgs = evaluate.compute_averages(evaluate.evaluate_matches(matches) if table_ap is None else table_ap)
                 out.update(matches=matches, avgs=avgs, mAP=float(avgs["all_ap"]), AP_50=float(avgs["all_ap_50%"]),
                            AP_25=float(avgs["all_ap_25%"]))
                 scalars += [("val/mAP", avgs["all_ap"]), ("val/AP_50", avgs["all_ap_50%"]), ("val/AP_25", avgs["all_ap_25%"])]
