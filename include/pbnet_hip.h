@@ -967,7 +967,8 @@ int pbn_unet_train_backward(const pbn_train_op* ops, int n_ops, const pbn_unet_b
  * Batch construction (csrc/augment.hip): trainMerge / valMerge of datasets/scannetv2/dataset_preprocess.py:178-385.
  * Rows of a batch form one range; a unit (one dataAugment call) and a scene (primary + mix-up partner) are contiguous
  * row segments given by int32 offsets [n+1].  ext = double[n,6] (min xyz, max xyz).  workspace: pbn_aug_workspace_bytes
- * (n_units or n_scenes).  max_*_rows sizes the grid only.
+ * (n_units or n_scenes).  max_*_rows sizes the grid only.  The ext row of a segment without rows is unspecified.  Every
+ * entry refuses a count <= 0 of units or scenes and a null pointer with PBN_ERR_ARG before it writes anything.
  * ------------------------------------------------------------------------------------------------------------ */
 int pbn_aug_chunks(int n_rows);
 size_t pbn_aug_workspace_bytes(int n_segments);
@@ -977,7 +978,8 @@ int pbn_aug_affine(const float* xyz, const int32_t* unit_off, int n_units, int m
                    void* workspace, pbn_stream_t stream);
 /* One elastic pass (gran, mag) on the units of desc int32[n_el,5] = (unit, b0, b1, b2, first float of its 3 grids):
  * 6 box-blur passes of the float32 grids in noise (tmp: the same size; both are overwritten), then
- * x += RegularGridInterpolator(g)(x) * mag; ext = extent per unit after the pass. */
+ * x += RegularGridInterpolator(g)(x) * mag; ext = extent per unit after the pass.  Rows of units outside desc keep their
+ * bits; the ext rows of those units are overwritten with unspecified values (pass flags 0 for them to pbn_aug_sub_min). */
 int pbn_aug_elastic(double* xyz, const int32_t* unit_off, int n_units, int max_unit_rows, const int32_t* desc, int n_el,
                     int total_cells, float* noise, float* tmp, int gran, double mag, double* ext, void* workspace,
                     pbn_stream_t stream);
@@ -988,14 +990,22 @@ int pbn_aug_sub_min(double* xyz, const int32_t* unit_off, int n_units, int max_u
  * point).  triples double[n_scenes,85,3] consumed in order (n_triples valid per scene), levels double[17,3] the full_scale
  * of each shrink.  One launch pair per try; state int32[n_scenes,8] (done, next triple, triples used, last try's start,
  * its level, success, error, tries); counts int32[5,n_scenes,17].  ext_pre = extent before, ext_post = after the
- * offset, over all points. */
+ * offset, over all points (before the mask selects rows).  A point is kept when 0 <= x + o and x + o < level on every
+ * axis.  counts[t][s][k] is meaningful for the levels k that try t of scene s visits (up to and including the level it
+ * stops at); the other levels of a try that ran hold counts of candidates the loop never takes, tries that did not run
+ * and mode-1 scenes hold 0.  error 1: a try found no level with at most max_crop_p points (not reachable while
+ * levels[16][0] is 0 and max_crop_p >= 0); error 2: the try needed a triple at or beyond n_triples -- the words triples
+ * used, last try's start and its level are then unspecified, next triple and tries describe the tries that completed. */
 int pbn_aug_crop(const double* xyz, const int32_t* scene_off, int n_scenes, int max_scene_rows, const int32_t* mode,
                  const double* triples, const int32_t* n_triples, const double* levels, int max_crop_p, int min_crop_p,
                  int32_t* counts, int32_t* state, double* ext_pre, double* ext_post, void* workspace, pbn_stream_t stream);
 /* Mask + compaction in input order (xyz - ext_post min, f32(rgb + shift[unit]) | nl, sem) and the instance relabelling
  * loop; labels of unit u are shifted by ins_shift[u] (-100 stays).  label_map / present: int32[n_labels]
  * (label_off[n_scenes+1]), scene_i32: int32[2*n_scenes], scan: int32[pbn_aug_chunks(n_rows)+1].
- * scene_info int32[n_scenes,4] = (rows kept, instance_num, first output row, 0). */
+ * scene_info int32[n_scenes,4] = (rows kept, instance_num, first output row, 0); instance_num is the maximum kept label
+ * + 1 after relabelling (-99 when every kept label is -100) and 0 for a scene that keeps no row.  Output rows at and
+ * beyond the total kept count are not written; scan[0 .. chunks] is the exclusive scan of the kept rows per 2048-row
+ * chunk.  n_rows 0 is valid. */
 int pbn_aug_compact(const double* xyz, const float* rgb, const float* nl, const int64_t* sem, const int32_t* ins,
                     const double* shift, const int32_t* ins_shift, const int32_t* unit_off, int n_units,
                     const int32_t* scene_off, int n_scenes, const int32_t* mode, const double* triples, const double* levels,
@@ -1004,7 +1014,8 @@ int pbn_aug_compact(const double* xyz, const float* rgb, const float* nl, const 
                     float* feat_out, int64_t* sem_out, int32_t* label_out, int32_t* scene_info, int n_rows, int n_labels,
                     pbn_stream_t stream);
 /* getInstanceInfo: per instance mean / min / max (float64, fixed-order reduction) and point count; inst_info f32[n,9]
- * (-100 outside an instance), ins = label + inst_off[scene] (-100 stays).  out_start / inst_start: [n_scenes+1]. */
+ * (-100 outside an instance), ins = label + inst_off[scene] (-100 stays).  out_start / inst_start: [n_scenes+1].
+ * pointnum / stats f32[n_inst,9] (mean, min, max) are not written when n_inst is 0, nothing is when n_rows is 0 too. */
 int pbn_aug_instances(const double* xyz, const int32_t* label, const int32_t* out_start, int n_scenes,
                       const int32_t* inst_start, const int32_t* inst_off, int n_inst, int n_rows, int32_t* pointnum,
                       float* stats, float* inst_info, int64_t* ins, pbn_stream_t stream);

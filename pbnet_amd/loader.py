@@ -431,9 +431,17 @@ class DeviceMerge:
         self.readbacks += 1
         sinfo_h = host[:4 * B].reshape(B, 4)
         state_h = host[4 * B:].reshape(B, 8)
-        if (state_h[:, 6] != 0).any():
-            raise RuntimeError("crop: a try did not stop within %d shrink levels (scenes %s)"
-                               % (CROP_LEVELS, np.nonzero(state_h[:, 6])[0].tolist()))
+        if (state_h[:, 6] != 0).any():                  # state word 6: 1 = out of shrink levels, 2 = out of triples
+            why = []
+            if (state_h[:, 6] == 1).any():
+                why.append("a try did not stop within %d shrink levels (scenes %s)"
+                           % (CROP_LEVELS, np.nonzero(state_h[:, 6] == 1)[0].tolist()))
+            if (state_h[:, 6] == 2).any():
+                short = np.nonzero(state_h[:, 6] == 2)[0].tolist()
+                why.append("the crop triples ran out (scenes %s, %s drawn)" % (short, [int(n_trip[s]) for s in short]))
+            if not why:
+                why.append("unknown error state %s" % state_h[:, 6].tolist())
+            raise RuntimeError("crop: " + "; ".join(why))
         self.last_crop_used = state_h[:, 2].copy()
         n_out = int(sinfo_h[:, 0].sum())
         inst_num = sinfo_h[:, 1].astype(np.int64)
