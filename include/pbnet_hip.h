@@ -1048,6 +1048,33 @@ int pbn_mesh_segment_point(const float* xyz, const float* normals, int n_points,
                            pbn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Scans without a mesh (csrc/cloud.hip): the exact k nearest neighbours of every point over a uniform grid, and PCA normals
+ * over them -- the edges and normals pbn_mesh_segment_point takes.  xyz f32[n,3].  Argument checks run on the host before
+ * any launch; neither pbn_cloud_knn nor pbn_cloud_normals synchronises.
+ * ------------------------------------------------------------------------------------------------------------ */
+/* bytes of workspace for pbn_cloud_knn; 0 = sizes out of range (n_points < 0 or too large, k outside 1..pbn_cloud_max_k()) */
+size_t pbn_cloud_workspace_bytes(int n_points, int k);
+int pbn_cloud_max_k(void);                                      /* 32 */
+/* idx int32[n,k], d2 f32[n,k], in the caller's point order.  d2(i,j) = ((dx*dx + dy*dy) + dz*dz), dx = x[j] - x[i], each
+ * operation rounded to float32 (no FMA).  Row i holds the k points j != i with the smallest key (bits of d2 as u32, j) in
+ * ascending key order: coincident points are neighbours at distance 0, self is excluded by index.  When n - 1 < k a row
+ * ends in idx = -1, d2 = +inf.  cell > 0 is the grid's cell size, anything else lets the library pick it on the device; it
+ * is enlarged until an axis has at most 1024 cells and the grid fits the cell table, and the result never depends on it.
+ * status int32[1] (device): 0, or bit 1 when a coordinate is not finite and bit 8 when the sort gave up; no row is
+ * trusted (none is written) then. */
+int pbn_cloud_knn(const float* xyz, int n_points, int k, float cell, int32_t* idx, float* d2, int32_t* status,
+                  void* workspace, size_t workspace_bytes, pbn_stream_t stream);
+/* Measurement variant: HIP events around the stages, SYNCHRONISES; times_ms (host float[4]): box + grid, keys + sort,
+ * cell table, search. */
+int pbn_cloud_knn_timed(const float* xyz, int n_points, int k, float cell, int32_t* idx, float* d2, int32_t* status,
+                        void* workspace, size_t workspace_bytes, pbn_stream_t stream, float* times_ms);
+/* nl f32[n,3]: for point i, S = i followed by its valid neighbours (0 <= idx < n) in rank order; float64 mean, then the six
+ * float64 covariance sums; the unit eigenvector of the smallest eigenvalue (fixed-count cyclic Jacobi in float64), flipped
+ * when n . (viewpoint - p_i) < 0, rounded to float32.  |S| < 3 gives the zero vector.  viewpoint: device float[3]. */
+int pbn_cloud_normals(const float* xyz, int n_points, const int32_t* idx, int k, const float* viewpoint, float* nl,
+                      pbn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Validation meters (csrc/metrics.hip): the integer counts behind train.py:123-304 (eval_epoch).  No workspace, no
  * synchronisation, integer atomics only (identical counters run to run).  Neither entry writes its inputs.
  * ------------------------------------------------------------------------------------------------------------ */

@@ -291,7 +291,13 @@ SIGNATURES = {
     "pbn_mesh_segment": (c_int, [c_f32p, c_int, c_vp, c_int, c_int, c_float, c_int, c_vp, c_f32p, c_vp, c_size,
                                  ctypes.POINTER(ctypes.c_float), c_vp]),
     "pbn_mesh_segment_point": (c_int, [c_f32p, c_f32p, c_int, c_vp, c_int, c_int, c_float, c_int, c_vp, c_vp, c_size, c_vp]),
-    "pbn_sem_confusion": (c_int, [c_vp, c_int, c_vp, c_int, c_i64, c_int, c_int, c_vp, c_vp, c_vp]),
+    "pbn_cloud_workspace_bytes": (c_size, [c_int, c_int]),
+    "pbn_cloud_max_k": (c_int, []),
+    "pbn_cloud_knn": (c_int, [c_f32p, c_int, c_int, c_float, c_i32p, c_f32p, c_i32p, c_vp, c_size, c_vp]),
+    "pbn_cloud_knn_timed": (c_int, [c_f32p, c_int, c_int, c_float, c_i32p, c_f32p, c_i32p, c_vp, c_size, c_vp,
+                                    ctypes.POINTER(ctypes.c_float)]),
+    "pbn_cloud_normals": (c_int, [c_f32p, c_int, c_i32p, c_int, c_f32p, c_f32p, c_vp]),
+    "pbn_sem_confusion":(c_int, [c_vp, c_int, c_vp, c_int, c_i64, c_int, c_int, c_vp, c_vp, c_vp]),
     "pbn_mask_accuracy": (c_int, [c_vp, c_int, c_vp, c_int, c_i64, c_float, c_vp, c_vp]),
     "pbn_losses_workspace_bytes": (c_size, [c_i64, c_i64, c_i64]),
     "pbn_losses_forward": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_f32p, c_f32p, c_vp, c_i64, c_int, c_vp, c_int, c_vp,

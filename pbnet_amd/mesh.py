@@ -8,6 +8,13 @@ read_ply         a minimal reader of ScanNet's binary_little_endian meshes (plyf
 decode_mesh      f_test without the file writes: mean-centred xyz, rgb / 127.5 - 1, nl, face (int32), sup
 save_decoded     the reference's `<scene>_{xyz,rgb,nl,face,sup}.npy` (+ labels when given) through scene_io
 
+Scans without a mesh (csrc/cloud.hip): segment_point's normals and edges from the points alone.
+knn_graph        the exact k nearest neighbours over a uniform grid, bit for bit a float32 brute force
+point_normals    float64 PCA normals over each point and its neighbours, turned towards a viewpoint
+knn_edges        the graph as segment_point's E x 2 edges
+read_ply_points  the vertex-only counterpart of read_ply
+decode_points    decode_mesh without faces: xyz, rgb, nl, sup
+
 The normals, edge weights, sort and relabel run in csrc/mesh.hip; the Felzenszwalb sweep (segment_graph and the
 small-segment join) is sequential by definition and runs in the library's host C++ over one read-back.  There is no CPU
 path: a missing library or a CPU tensor raises.
@@ -114,6 +121,81 @@ def segment_point(vertices, normals, edges, kThresh=0.01, segMinVerts=20):
     return sup
 
 
+# ---------------------------------------------------------------------------------------------------- point clouds
+CLOUD_STAGES = ("box", "keys + sort", "cell table", "search")
+CLOUD_NONFINITE, CLOUD_SORT_SPIN = 1, 8          # status bits of pbn_cloud_knn
+
+
+def knn_graph(xyz, k=16, cell=None, times=None):
+    """The exact k nearest neighbours of every point (csrc/cloud.hip): idx int32 [N, k] and d2 float32 [N, k] on the
+    device, in the caller's point order.  d2 = ((dx*dx + dy*dy) + dz*dz) in float32; a row holds the k points j != i with
+    the smallest (bits of d2, j), ascending; when N - 1 < k it ends in idx = -1, d2 = +inf.  `cell` (the grid's cell size;
+    None lets the library choose) changes the speed, never the result.  A non-finite coordinate raises ValueError."""
+    xyz = _check_xyz("xyz", xyz)
+    n, k = int(xyz.shape[0]), int(k)
+    lib = N.lib()
+    if not 1 <= k <= lib.pbn_cloud_max_k():
+        raise ValueError("knn_graph: k must lie in 1..%d, got %d" % (lib.pbn_cloud_max_k(), k))
+    nbytes = lib.pbn_cloud_workspace_bytes(n, k)
+    if nbytes == 0:
+        raise ValueError("point cloud too large for the library: %d points" % n)
+    dev = xyz.device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    idx = torch.empty(n, k, dtype=torch.int32, device=dev)
+    d2 = torch.empty(n, k, dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    h = 0.0 if cell is None else float(cell)
+    if cell is not None and not h > 0.0:
+        raise ValueError("knn_graph: cell must be positive, got %r" % (cell,))
+    args = (N.ptr(xyz), n, k, h, N.ptr(idx), N.ptr(d2), N.ptr(status), N.ptr(ws), ws.numel(), N.current_stream())
+    if times is None:
+        N.check(lib.pbn_cloud_knn(*args), "pbn_cloud_knn")
+    else:
+        t = (ctypes.c_float * len(CLOUD_STAGES))()
+        N.check(lib.pbn_cloud_knn_timed(*args, t), "pbn_cloud_knn_timed")
+        times.update({name: float(t[i]) for i, name in enumerate(CLOUD_STAGES)})
+    st = int(status.item())
+    if st & CLOUD_NONFINITE:
+        raise ValueError("knn_graph: a coordinate is NaN or infinite")
+    if st:
+        raise RuntimeError("knn_graph: the device sort gave up (status %d)" % st)
+    return idx, d2
+
+
+def point_normals(xyz, idx, viewpoint=None):
+    """PCA normals over each point and its neighbours `idx` (int32 [N, k], -1 = none): float32 [N, 3] on the device, the
+    float64 eigenvector of the smallest covariance eigenvalue, turned towards `viewpoint` (three numbers or a tensor; None
+    = the float64 mean of xyz).  Fewer than three points in a neighbourhood give the zero vector."""
+    xyz = _check_xyz("xyz", xyz)
+    N.require_cuda(idx)
+    n = int(xyz.shape[0])
+    if idx.dtype != torch.int32 or idx.dim() != 2 or idx.shape[0] != n:
+        raise TypeError("idx must be an int32 [%d, k] tensor, got %s %s" % (n, idx.dtype, tuple(idx.shape)))
+    idx = idx.contiguous()
+    k = int(idx.shape[1])
+    if viewpoint is None:
+        vp = xyz.double().mean(0).float() if n else torch.zeros(3, dtype=torch.float32, device=xyz.device)
+    elif torch.is_tensor(viewpoint):
+        vp = viewpoint.to(device=xyz.device, dtype=torch.float32).reshape(3)
+    else:
+        vp = torch.tensor([float(v) for v in viewpoint], dtype=torch.float32).reshape(3).to(xyz.device)
+    vp = vp.contiguous()
+    nl = torch.empty(n, 3, dtype=torch.float32, device=xyz.device)
+    N.check(N.lib().pbn_cloud_normals(N.ptr(xyz), n, N.ptr(idx), k, N.ptr(vp), N.ptr(nl), N.current_stream()),
+            "pbn_cloud_normals")
+    return nl
+
+
+def knn_edges(idx):
+    """The kNN graph as segment_point's edges: int64 [E, 2] rows (i, idx[i, r]), i-major and rank-minor, -1 entries
+    dropped."""
+    n, k = int(idx.shape[0]), int(idx.shape[1])
+    src = torch.arange(n, dtype=torch.int64, device=idx.device).repeat_interleave(k)
+    dst = idx.reshape(-1).to(torch.int64)
+    keep = dst >= 0
+    return torch.stack([src[keep], dst[keep]], dim=1)
+
+
 # ------------------------------------------------------------------------------------------------------------ PLY
 _PLY_SCALARS = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
                 "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
@@ -177,6 +259,53 @@ def read_ply(path):
     return xyz, rgb, face["i"].astype(np.int64).reshape(-1, 3)
 
 
+def read_ply_points(path):
+    """A point cloud's PLY: returns (xyz float32 [V, 3], colours uint8 [V, 3]).
+
+    Accepted: format binary_little_endian 1.0 with the vertex element ONLY, under read_ply's property rules (`float x, y,
+    z`, `uchar red, green, blue`, an optional `uchar alpha`).  Anything else raises ValueError; a file with faces is a mesh
+    and belongs to read_ply."""
+    with open(path, "rb") as fh:
+        if fh.readline().strip() != b"ply":
+            raise ValueError("%s: not a PLY file" % path)
+        elements, fmt = [], None
+        while True:
+            line = fh.readline()
+            if not line:
+                raise ValueError("%s: no end_header" % path)
+            words = line.decode("ascii", "replace").split()
+            if not words or words[0] in ("comment", "obj_info"):
+                continue
+            if words[0] == "end_header":
+                break
+            if words[0] == "format":
+                fmt = words[1:]
+            elif words[0] == "element" and len(words) == 3:
+                elements.append((words[1], int(words[2]), []))
+            elif words[0] == "property" and elements:
+                elements[-1][2].append(tuple(words[1:]))
+            else:
+                raise ValueError("%s: unsupported header line %r" % (path, line))
+        body = fh.read()
+    if fmt != ["binary_little_endian", "1.0"]:
+        raise ValueError("%s: only binary_little_endian 1.0 is supported, got %s" % (path, fmt))
+    if [e[0] for e in elements] != ["vertex"]:
+        raise ValueError("%s: expected the vertex element only, got %s" % (path, [e[0] for e in elements]))
+    _, nv, vprops = elements[0]
+    names = [p[-1] for p in vprops]
+    types = [p[0] for p in vprops]
+    if names not in (["x", "y", "z", "red", "green", "blue"], ["x", "y", "z", "red", "green", "blue", "alpha"]) or \
+            any(_PLY_SCALARS.get(t) != "f4" for t in types[:3]) or any(_PLY_SCALARS.get(t) != "u1" for t in types[3:]):
+        raise ValueError("%s: vertex properties must be float x y z + uchar red green blue [alpha], got %s" % (path, vprops))
+    vdt = np.dtype([(n, "<f4" if i < 3 else "u1") for i, n in enumerate(names)])
+    if nv < 0 or len(body) < nv * vdt.itemsize:
+        raise ValueError("%s: truncated body (%d bytes, need %d)" % (path, len(body), nv * vdt.itemsize))
+    vert = np.frombuffer(body, vdt, nv, 0)
+    xyz = np.stack([vert["x"], vert["y"], vert["z"]], axis=1).astype(np.float32)
+    rgb = np.stack([vert["red"], vert["green"], vert["blue"]], axis=1).astype(np.uint8)
+    return xyz, rgb
+
+
 def write_ply(path, xyz, colours, faces, index_type="int", alpha=True):
     """The counterpart of read_ply (binary_little_endian, the layout ScanNet ships)."""
     xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
@@ -233,6 +362,27 @@ def decode_mesh(src, device="cuda", kThresh=0.01, segMinVerts=20):
     sup = _segment_mesh(xyz_d, face_d, kThresh, segMinVerts, nl=nl)
     return {"xyz": xyz_d, "rgb": torch.from_numpy(np.ascontiguousarray(rgb, np.float32)).to(dev), "nl": nl,
             "face": face_d, "sup": sup}
+
+
+def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpoint=None, return_graph=False):
+    """decode_mesh for a scan without faces: `src` is a vertex-only `.ply` path or (xyz [V,3], colours [V,3] 0..255).
+    centre_and_scale -> knn_graph -> point_normals -> knn_edges -> segment_point.  Returns xyz (mean-centred), rgb, nl and
+    sup on `device` -- what SceneCache and save_decoded take (no `face`) -- plus idx and d2 when return_graph is set.
+    `viewpoint` is given in the centred frame; None is the cloud's mean."""
+    if isinstance(src, (str, bytes)) or hasattr(src, "__fspath__"):
+        xyz, colours = read_ply_points(src)
+    else:
+        xyz, colours = (t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t) for t in src)
+    xyz_c, rgb = centre_and_scale(xyz, colours)
+    dev = torch.device(device)
+    xyz_d = torch.from_numpy(np.ascontiguousarray(xyz_c, np.float32)).to(dev)
+    idx, d2 = knn_graph(xyz_d, k=k)
+    nl = point_normals(xyz_d, idx, viewpoint)
+    sup = segment_point(xyz_d, nl, knn_edges(idx), kThresh, segMinVerts)
+    out = {"xyz": xyz_d, "rgb": torch.from_numpy(np.ascontiguousarray(rgb, np.float32)).to(dev), "nl": nl, "sup": sup}
+    if return_graph:
+        out.update(idx=idx, d2=d2)
+    return out
 
 
 def save_decoded(npy_dir, scene, decoded, sem_label=None, ins_label=None):
