@@ -1075,6 +1075,49 @@ int pbn_cloud_normals(const float* xyz, int n_points, const int32_t* idx, int k,
                       pbn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Raw sensor scans (csrc/thin.hip): grid thinning to the network's pitch, statistical outlier removal over the kNN graph's
+ * d2, and the way back from the kept points to the raw ones.  Argument checks run on the host before any launch; only the
+ * _timed entry synchronises.  Every output is a pure function of the input (no float atomics): two runs give the same
+ * bytes, and tests/thin_ref.py restates each in numpy.
+ * ------------------------------------------------------------------------------------------------------------ */
+/* bytes of workspace for pbn_thin_points; 0 = n_points out of range (< 0 or above 2^28) */
+size_t pbn_thin_workspace_bytes(int n_points);
+/* One output row per occupied cell of a grid of `pitch` (finite, > 0; else PBN_ERR_ARG).  xyz f32[n,3]; rgb f32[n,3] or
+ * NULL.  Origin o[a] = the float32 minimum of axis a; cell c[a] = floor((double(p[a]) - double(o[a])) / pitch) (correctly
+ * rounded float64 division); key = cz << 42 | cy << 21 | cx; rows in ascending key order.  Per row t: out_xyz / out_rgb
+ * f32[.,3] = float32(the float64 sum of the members' values, added from 0.0 in ascending point index, / double(count));
+ * count[t] = members; first[t] = the lowest member index; inverse int32[n]: the row of every input point.  The arrays
+ * out_xyz, out_rgb, count and first hold n rows, of which the first M are written.
+ * result int32[2] (device): [0] status -- 0, or bit 1 a coordinate is not finite, bit 2 an axis spans 2^21 cells or more,
+ * bit 8 a sort gave up; with a status no output is written -- and [1] M, the number of rows: one read-back gives both. */
+int pbn_thin_points(const float* xyz, const float* rgb, int n_points, double pitch, float* out_xyz, float* out_rgb,
+                    int32_t* count, int32_t* first, int32_t* inverse, int32_t* result, void* workspace, size_t workspace_bytes,
+                    pbn_stream_t stream);
+/* Measurement variant: HIP events around the stages, SYNCHRONISES; times_ms (host float[5]): box + keys, low-word sort,
+ * high-word keys + sort, run heads + scan, cells. */
+int pbn_thin_points_timed(const float* xyz, const float* rgb, int n_points, double pitch, float* out_xyz, float* out_rgb,
+                          int32_t* count, int32_t* first, int32_t* inverse, int32_t* result, void* workspace,
+                          size_t workspace_bytes, pbn_stream_t stream, float* times_ms);
+/* bytes of workspace for pbn_cloud_outlier_mask; 0 = n_points out of range */
+size_t pbn_cloud_outlier_workspace_bytes(int n_points);
+/* d2 f32[n,k] as pbn_cloud_knn writes it.  m_i = (float64 sum in rank order, from 0.0, of sqrt(double(d2[i,r])) over the
+ * finite entries) / their number; a row without a finite entry has no m_i, is not kept and counts nowhere.  Sums over
+ * points: blocks of 256 consecutive indices, inside a block the tree v[j] += v[j + s] for s = 128 .. 1 (absent entries
+ * 0.0), block partials added in block order.  mu = sum m_i / n_valid; sigma = sqrt(sum (m_i - mu)^2 / n_valid) (a second
+ * pass); keep[i] (uint8 0 / 1) = m_i <= mu + ratio * sigma in float64 (a product, then a sum).  stats double[3] (device):
+ * mu, sigma, n_valid; without a valid row mu and sigma are NaN; n_points == 0 writes zeros.  ratio finite and >= 0,
+ * k in 1..pbn_cloud_max_k(), else PBN_ERR_ARG. */
+int pbn_cloud_outlier_mask(const float* d2, int n_points, int k, double ratio, uint8_t* keep, double* stats, void* workspace,
+                           size_t workspace_bytes, pbn_stream_t stream);
+/* bytes of workspace for pbn_cloud_raw_index; 0 = n_points out of range */
+size_t pbn_cloud_raw_index_workspace_bytes(int n_points);
+/* raw_index int32[n_raw]: with t = inverse[i] (a row of the n_points points keep and idx speak of) and kept_row = the
+ * exclusive scan of keep: kept_row[t] when keep[t]; else kept_row[j] of the first j = idx[t, r] in rank order with keep[j];
+ * else -1 (also for t outside [0, n_points)).  idx int32[n_points,k], -1 = no neighbour. */
+int pbn_cloud_raw_index(const int32_t* inverse, int n_raw, const uint8_t* keep, const int32_t* idx, int n_points, int k,
+                        int32_t* raw_index, void* workspace, size_t workspace_bytes, pbn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Validation meters (csrc/metrics.hip): the integer counts behind train.py:123-304 (eval_epoch).  No workspace, no
  * synchronisation, integer atomics only (identical counters run to run).  Neither entry writes its inputs.
  * ------------------------------------------------------------------------------------------------------------ */

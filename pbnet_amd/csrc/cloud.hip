@@ -439,6 +439,13 @@ int knn_args(const float* xyz, int n, int k, const int32_t* idx, const float* d2
 }
 
 }  // namespace
+
+int cloud_box(const float* xyz, int n, unsigned* box, int32_t* status, hipStream_t st) {
+    hipLaunchKernelGGL(k_cloud_box, dim3(grid_for(n)), dim3(TPB), 0, st, xyz, n, box, status);
+    PBN_LAUNCH_CHECK();
+    return PBN_OK;
+}
+
 }  // namespace pbn
 
 using namespace pbn;

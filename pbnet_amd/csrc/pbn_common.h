@@ -124,6 +124,9 @@ constexpr int RADIX_U32_DIGIT_BITS = 11, RADIX_U32_PASSES = 3;
 size_t radix_sort_u32_scratch_bytes(int n);
 int radix_sort_u32(unsigned long long* keys_a, unsigned long long* keys_b, int32_t* vals_a, int32_t* vals_b, int n,
                    const unsigned* ghist, int32_t* status, void* scratch, size_t scratch_bytes, hipStream_t stream);
+// cloud.hip: k_cloud_box for thin.hip -- box[0..2] / box[3..5] = minimum / maximum per axis as order-preserving u32 keys
+// (the caller fills them with 0xff / 0 first), status |= 1 when a coordinate is NaN or infinite; n > 0
+int cloud_box(const float* xyz, int n, unsigned* box, int32_t* status, hipStream_t stream);
 // prepare.hip: device radix sort of (key, value) pairs; temp from sort_pairs_temp_bytes(n)
 size_t sort_pairs_temp_bytes(int n);
 int sort_pairs_u64_i32(const uint64_t* keys_in, uint64_t* keys_out, const int32_t* vals_in, int32_t* vals_out, int n,

@@ -15,6 +15,12 @@ knn_edges        the graph as segment_point's E x 2 edges
 read_ply_points  the vertex-only counterpart of read_ply
 decode_points    decode_mesh without faces: xyz, rgb, nl, sup
 
+Raw sensor scans (csrc/thin.hip): to the network's pitch and back.
+thin_points      one float64 centroid per occupied cell of a grid, bit for bit tests/thin_ref.py
+outlier_mask     statistical outlier removal over knn_graph's d2, sums of a fixed shape
+raw_index        for every raw point its row among the kept points (itself, or its first kept neighbour)
+carry_labels     per-point results of the kept points gathered back to the raw ones
+
 The normals, edge weights, sort and relabel run in csrc/mesh.hip; the Felzenszwalb sweep (segment_graph and the
 small-segment join) is sequential by definition and runs in the library's host C++ over one read-back.  There is no CPU
 path: a missing library or a CPU tensor raises.
@@ -196,6 +202,126 @@ def knn_edges(idx):
     return torch.stack([src[keep], dst[keep]], dim=1)
 
 
+# ------------------------------------------------------------------------------------------------------- raw scans
+THIN_STAGES = ("box + keys", "low-word sort", "high-word keys + sort", "run heads + scan", "cells")
+CLOUD_EXTENT = 2                                 # status bit of pbn_thin_points: an axis spans 2^21 cells or more
+
+
+def thin_points(xyz, colours=None, pitch=0.02, times=None):
+    """One point per occupied cell of a grid of `pitch` (csrc/thin.hip).  The grid starts at the per-axis float32 minimum;
+    cell = floor((double(p) - double(origin)) / pitch); rows come in ascending order of cz << 42 | cy << 21 | cx.  Returns a
+    dict on the device: xyz f32 [M, 3] (the float32 rounding of the float64 mean of a cell's members, summed in ascending
+    point index), rgb f32 [M, 3] likewise when `colours` (f32 [N, 3]) are given, count int32 [M] (members), first int32 [M]
+    (the lowest member index) and inverse int32 [N] (the row of every input point).  One read-back (status and M); a
+    non-finite coordinate or an extent of 2^21 cells or more on an axis raises ValueError."""
+    pitch = float(pitch)
+    if not (pitch > 0.0 and np.isfinite(pitch)):
+        raise ValueError("thin_points: pitch must be positive and finite, got %r" % (pitch,))
+    xyz = _check_xyz("xyz", xyz)
+    rgb = None if colours is None else _check_xyz("colours", colours)
+    n = int(xyz.shape[0])
+    if rgb is not None and rgb.shape[0] != n:
+        raise ValueError("thin_points: %d colours for %d points" % (rgb.shape[0], n))
+    lib = N.lib()
+    nbytes = lib.pbn_thin_workspace_bytes(n)
+    if nbytes == 0:
+        raise ValueError("point cloud too large for the library: %d points" % n)
+    dev = xyz.device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out_xyz = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    out_rgb = torch.empty(n, 3, dtype=torch.float32, device=dev) if rgb is not None else None
+    count, first, inverse = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+    result = torch.empty(2, dtype=torch.int32, device=dev)
+    args = (N.ptr(xyz), N.ptr(rgb), n, pitch, N.ptr(out_xyz), N.ptr(out_rgb), N.ptr(count), N.ptr(first), N.ptr(inverse),
+            N.ptr(result), N.ptr(ws), ws.numel(), N.current_stream())
+    if times is None:
+        N.check(lib.pbn_thin_points(*args), "pbn_thin_points")
+    else:
+        t = (ctypes.c_float * len(THIN_STAGES))()
+        N.check(lib.pbn_thin_points_timed(*args, t), "pbn_thin_points_timed")
+        times.update({name: float(t[i]) for i, name in enumerate(THIN_STAGES)})
+    st, m = (int(v) for v in result.tolist())                # the one read-back
+    if st & CLOUD_NONFINITE:
+        raise ValueError("thin_points: a coordinate is NaN or infinite")
+    if st & CLOUD_EXTENT:
+        raise ValueError("thin_points: the cloud spans 2^21 cells or more of pitch %r on an axis" % (pitch,))
+    if st:
+        raise RuntimeError("thin_points: the device sort gave up (status %d)" % st)
+    out = {"xyz": out_xyz[:m], "count": count[:m], "first": first[:m], "inverse": inverse}
+    if rgb is not None:
+        out["rgb"] = out_rgb[:m]
+    return out
+
+
+def outlier_mask(d2, ratio=2.0):
+    """Statistical outlier removal on knn_graph's d2 (f32 [N, k]): m_i = the float64 mean of sqrt(d2[i, r]) over the finite
+    entries, mu and sigma (population) over the rows that have one, keep_i = m_i <= mu + ratio * sigma.  Returns keep (bool
+    [N]) and stats (float64 [3]: mu, sigma, n_valid), both on the device; every sum has a fixed shape (csrc/thin.hip), so
+    two runs give the same bytes.  A row without a finite entry is not kept."""
+    ratio = float(ratio)
+    if not (ratio >= 0.0 and np.isfinite(ratio)):
+        raise ValueError("outlier_mask: ratio must be finite and >= 0, got %r" % (ratio,))
+    N.require_cuda(d2)
+    if d2.dtype != torch.float32 or d2.dim() != 2:
+        raise TypeError("d2 must be a float32 [n, k] tensor, got %s %s" % (d2.dtype, tuple(d2.shape)))
+    d2 = d2.contiguous()
+    n, k = int(d2.shape[0]), int(d2.shape[1])
+    lib = N.lib()
+    if not 1 <= k <= lib.pbn_cloud_max_k():
+        raise ValueError("outlier_mask: k must lie in 1..%d, got %d" % (lib.pbn_cloud_max_k(), k))
+    nbytes = lib.pbn_cloud_outlier_workspace_bytes(n)
+    if nbytes == 0:
+        raise ValueError("point cloud too large for the library: %d points" % n)
+    dev = d2.device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    keep = torch.empty(n, dtype=torch.bool, device=dev)
+    stats = torch.empty(3, dtype=torch.float64, device=dev)
+    N.check(lib.pbn_cloud_outlier_mask(N.ptr(d2), n, k, ratio, N.ptr(keep), N.ptr(stats), N.ptr(ws), ws.numel(),
+                                       N.current_stream()), "pbn_cloud_outlier_mask")
+    return keep, stats
+
+
+def raw_index(inverse, keep, idx):
+    """For every raw point the row, among the kept points, that speaks for it: int32 [N_raw] on the device.  With
+    t = inverse[i]: t's row among the kept points (the exclusive scan of keep) when keep[t]; else the row of the first kept
+    neighbour in rank order in idx[t, :]; else -1.  `inverse` int32 [N_raw] (thin_points), `keep` bool [M] (outlier_mask),
+    `idx` int32 [M, k] (knn_graph over the same M points)."""
+    N.require_cuda(inverse, keep, idx)
+    if inverse.dtype != torch.int32 or inverse.dim() != 1:
+        raise TypeError("inverse must be an int32 [n] tensor, got %s %s" % (inverse.dtype, tuple(inverse.shape)))
+    m = int(keep.shape[0])
+    if keep.dtype != torch.bool or keep.dim() != 1:
+        raise TypeError("keep must be a bool [m] tensor, got %s %s" % (keep.dtype, tuple(keep.shape)))
+    if idx.dtype != torch.int32 or idx.dim() != 2 or idx.shape[0] != m:
+        raise TypeError("idx must be an int32 [%d, k] tensor, got %s %s" % (m, idx.dtype, tuple(idx.shape)))
+    inverse, keep, idx = inverse.contiguous(), keep.contiguous(), idx.contiguous()
+    n_raw, k = int(inverse.shape[0]), int(idx.shape[1])
+    lib = N.lib()
+    if not 1 <= k <= lib.pbn_cloud_max_k():
+        raise ValueError("raw_index: k must lie in 1..%d, got %d" % (lib.pbn_cloud_max_k(), k))
+    nbytes = lib.pbn_cloud_raw_index_workspace_bytes(m)
+    if nbytes == 0:
+        raise ValueError("point cloud too large for the library: %d points" % m)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=inverse.device)
+    out = torch.empty(n_raw, dtype=torch.int32, device=inverse.device)
+    N.check(lib.pbn_cloud_raw_index(N.ptr(inverse), n_raw, N.ptr(keep), N.ptr(idx), m, k, N.ptr(out), N.ptr(ws), ws.numel(),
+                                    N.current_stream()), "pbn_cloud_raw_index")
+    return out
+
+
+def carry_labels(labels, raw_index, fill=-1):
+    """The gather that goes with raw_index: out[i] = labels[raw_index[i]], `fill` where raw_index[i] is -1.  `labels` is
+    any integer tensor whose first axis is the kept points; the result has raw_index's length on that axis."""
+    if labels.dtype.is_floating_point or labels.dtype == torch.bool:
+        raise TypeError("carry_labels: labels must be an integer tensor, got %s" % labels.dtype)
+    ri = raw_index.to(device=labels.device, dtype=torch.int64)
+    none = ri < 0
+    out = labels.index_select(0, ri.clamp(min=0)) if labels.shape[0] else \
+        labels.new_zeros((ri.shape[0],) + tuple(labels.shape[1:]))
+    out[none] = fill
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------ PLY
 _PLY_SCALARS = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
                 "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
@@ -364,17 +490,51 @@ def decode_mesh(src, device="cuda", kThresh=0.01, segMinVerts=20):
             "face": face_d, "sup": sup}
 
 
-def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpoint=None, return_graph=False):
+def _kept_points(xyz, colours, dev, k, pitch, outlier_ratio):
+    """decode_points' front for a raw scan: upload, thin_points (pitch), knn_graph -> outlier_mask -> compact
+    (outlier_ratio).  Returns the kept points' (xyz, colours) as host float32 arrays -- centre_and_scale is a host numpy
+    expression, so the kept M x 6 floats make one extra round trip -- and raw_index / count on the device."""
+    xyz_d = torch.from_numpy(np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)).to(dev)
+    col_d = torch.from_numpy(np.ascontiguousarray(colours, np.float32).reshape(-1, 3)).to(dev)
+    n_raw = int(xyz_d.shape[0])
+    if pitch is not None:
+        th = thin_points(xyz_d, col_d, pitch)
+        xyz_d, col_d, count, inverse = th["xyz"], th["rgb"], th["count"], th["inverse"]
+    else:
+        count = torch.ones(n_raw, dtype=torch.int32, device=dev)
+        inverse = torch.arange(n_raw, dtype=torch.int32, device=dev)
+    if outlier_ratio is not None:
+        idx, d2 = knn_graph(xyz_d, k=k)
+        keep, _ = outlier_mask(d2, outlier_ratio)
+        inverse = raw_index(inverse, keep, idx)
+        xyz_d, col_d, count = xyz_d[keep], col_d[keep], count[keep]
+    return xyz_d.cpu().numpy(), col_d.cpu().numpy(), inverse, count
+
+
+def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpoint=None, return_graph=False, pitch=None,
+                  outlier_ratio=None, return_kept=False):
     """decode_mesh for a scan without faces: `src` is a vertex-only `.ply` path or (xyz [V,3], colours [V,3] 0..255).
     centre_and_scale -> knn_graph -> point_normals -> knn_edges -> segment_point.  Returns xyz (mean-centred), rgb, nl and
     sup on `device` -- what SceneCache and save_decoded take (no `face`) -- plus idx and d2 when return_graph is set.
-    `viewpoint` is given in the centred frame; None is the cloud's mean."""
+    `viewpoint` is given in the centred frame; None is the cloud's mean.
+
+    A raw sensor scan (uneven density, flying pixels) is brought to the network's pitch first: with `pitch` the points are
+    thinned to one centroid per cell (thin_points), with `outlier_ratio` the points whose mean neighbour distance exceeds
+    mu + ratio * sigma are dropped (knn_graph over k neighbours, outlier_mask); the chain above then runs on the kept
+    points exactly as if they had been given as `src`.  The result gains raw_index (int32 [V]: for every raw point its row
+    among the kept points, -1 = none; see raw_index and carry_labels) and count (int32: raw points behind each kept one),
+    and with return_kept also kept_xyz / kept_rgb, the kept points before centring and scaling."""
     if isinstance(src, (str, bytes)) or hasattr(src, "__fspath__"):
         xyz, colours = read_ply_points(src)
     else:
         xyz, colours = (t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t) for t in src)
-    xyz_c, rgb = centre_and_scale(xyz, colours)
     dev = torch.device(device)
+    raw = None
+    if pitch is not None or outlier_ratio is not None:
+        xyz, colours, *raw = _kept_points(xyz, colours, dev, k, pitch, outlier_ratio)
+    elif return_kept:
+        raise ValueError("decode_points: return_kept needs pitch or outlier_ratio")
+    xyz_c, rgb = centre_and_scale(xyz, colours)
     xyz_d = torch.from_numpy(np.ascontiguousarray(xyz_c, np.float32)).to(dev)
     idx, d2 = knn_graph(xyz_d, k=k)
     nl = point_normals(xyz_d, idx, viewpoint)
@@ -382,6 +542,10 @@ def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpo
     out = {"xyz": xyz_d, "rgb": torch.from_numpy(np.ascontiguousarray(rgb, np.float32)).to(dev), "nl": nl, "sup": sup}
     if return_graph:
         out.update(idx=idx, d2=d2)
+    if raw is not None:
+        out.update(raw_index=raw[0], count=raw[1])
+        if return_kept:
+            out.update(kept_xyz=torch.from_numpy(xyz).to(dev), kept_rgb=torch.from_numpy(colours).to(dev))
     return out
 
 
