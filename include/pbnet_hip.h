@@ -1118,6 +1118,34 @@ int pbn_cloud_raw_index(const int32_t* inverse, int n_raw, const uint8_t* keep, 
                         int32_t* raw_index, void* workspace, size_t workspace_bytes, pbn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Annotated raw scans (csrc/vote.hip): the raw points' labels voted down to the kept points.  Integers only: two runs
+ * give the same bytes, and tests/vote_ref.py restates the contract in numpy.  Argument checks run on the host before any
+ * launch (n_classes in 1..1023, n_raw and m in 0..2^28, else PBN_ERR_ARG); nothing synchronises.
+ * ------------------------------------------------------------------------------------------------------------ */
+/* bytes of workspace for pbn_cloud_vote_labels; 0 = n_raw or m out of range */
+size_t pbn_cloud_vote_workspace_bytes(int n_raw, int m);
+/* rows int32[n_raw]: the kept row in [0, m) that speaks for raw point i, or -1 (pbn_cloud_raw_index, or pbn_thin_points'
+ * inverse); sem int32[n_raw]; ins int32[n_raw] or NULL.  Codes: s = sem < 0 ? n_classes : sem; q = ins < 0 ? 2^21 - 1 : ins
+ * (q = 0 for every point when ins is NULL): any negative label is "unannotated", a label like any other that orders
+ * LAST.  Vote key = s << 21 | q.  Per kept row t: members[t] = #{i: rows[i] == t}; the winner is the key with the largest
+ * count among them, ties to the LOWEST key; votes[t] = its count; out_sem[t] / out_ins[t] (int64) = its s / q, the two
+ * unannotated codes written as -100.  A row without members gets -100, -100, 0, 0; points with rows == -1 vote nowhere.
+ * old_id int64[min(m, 2^21)] or NULL.  Not NULL: the instance ids that won a row are renumbered 0 .. I'-1 in ascending
+ * old-id order in out_ins, old_id[new] = old for new < I'.  NULL: out_ins keeps the raw ids and I' is 0.
+ * result int32[2] (device): [0] status -- 0, or bit 1 a sem >= n_classes, bit 2 an ins >= 2^21 - 1, bit 4 a rows entry
+ * outside [-1, m), bit 8 a sort gave up; with a status the outputs are unspecified -- and [1] I': one read-back gives
+ * both.  n_raw == 0 fills the m rows and launches nothing else; m == 0 runs the range checks alone. */
+int pbn_cloud_vote_labels(const int32_t* rows, const int32_t* sem, const int32_t* ins, int n_raw, int m, int n_classes,
+                          int64_t* out_sem, int64_t* out_ins, int32_t* votes, int32_t* members, int32_t* result,
+                          int64_t* old_id, void* workspace, size_t workspace_bytes, pbn_stream_t stream);
+/* Measurement variant: HIP events around the stages, SYNCHRONISES; times_ms (host float[6]): fill + keys, key sort, row
+ * pairs + row sort, run heads + scan + starts, pick, compaction. */
+int pbn_cloud_vote_labels_timed(const int32_t* rows, const int32_t* sem, const int32_t* ins, int n_raw, int m, int n_classes,
+                                int64_t* out_sem, int64_t* out_ins, int32_t* votes, int32_t* members, int32_t* result,
+                                int64_t* old_id, void* workspace, size_t workspace_bytes, pbn_stream_t stream,
+                                float* times_ms);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Validation meters (csrc/metrics.hip): the integer counts behind train.py:123-304 (eval_epoch).  No workspace, no
  * synchronisation, integer atomics only (identical counters run to run).  Neither entry writes its inputs.
  * ------------------------------------------------------------------------------------------------------------ */

@@ -20,6 +20,8 @@ thin_points      one float64 centroid per occupied cell of a grid, bit for bit t
 outlier_mask     statistical outlier removal over knn_graph's d2, sums of a fixed shape
 raw_index        for every raw point its row among the kept points (itself, or its first kept neighbour)
 carry_labels     per-point results of the kept points gathered back to the raw ones
+vote_labels      the other direction (csrc/vote.hip): an annotated raw scan's (semantic, instance) pairs voted down to the
+                 kept points, surviving instance ids renumbered densely; bit for bit tests/vote_ref.py
 
 The normals, edge weights, sort and relabel run in csrc/mesh.hip; the Felzenszwalb sweep (segment_graph and the
 small-segment join) is sequential by definition and runs in the library's host C++ over one read-back.  There is no CPU
@@ -322,6 +324,83 @@ def carry_labels(labels, raw_index, fill=-1):
     return out
 
 
+# ------------------------------------------------------------------------------------------------- annotated scans
+VOTE_SEM_RANGE, VOTE_INS_RANGE, VOTE_ROW_RANGE = 1, 2, 4     # status bits of pbn_cloud_vote_labels (8: a sort gave up)
+VOTE_MAX_CLASSES, VOTE_MAX_INS = 1023, (1 << 21) - 1         # n_classes in 1..1023; instance ids in 0..2^21 - 2
+VOTE_STAGES = ("fill + keys", "key sort", "row pairs + row sort", "run heads + scan + starts", "pick", "compaction")
+
+
+def vote_labels(rows, sem, ins=None, m=None, n_classes=20, compact=True, times=None):
+    """An annotated raw scan's labels voted down to the kept points (csrc/vote.hip): per kept row the most frequent
+    (semantic, instance) pair among the raw points routed to it.  `rows` int32 [N_raw] (decode_points' raw_index or
+    thin_points' inverse: a row in [0, m) or -1 = votes nowhere), `sem` int32 [N_raw], `ins` int32 [N_raw] or None (every
+    point then carries instance 0).  Any negative label is "unannotated": a label like any other, ordered LAST (the
+    reference's align_superpoint_label); ties go to the lowest (sem, ins) pair.  Returns a dict on the device: sem_label
+    and ins_label int64 [m] (-100 = unannotated, or a row without members), votes int32 [m] (the winner's count), members
+    int32 [m] and old_id int64 [I'].  With `compact` the instance ids that won a row are renumbered 0..I'-1 in ascending
+    order and old_id[new] = old; without it ins_label keeps the raw ids and old_id is empty.  One read-back (status and
+    I'); `m` None takes rows.max() + 1, which costs a read-back of its own.  sem >= n_classes, ins >= 2^21 - 1 or a row
+    outside [-1, m) raises ValueError.  `times` (a dict) takes the stage times of the measurement entry, which synchronises."""
+    for name, t in (("rows", rows), ("sem", sem), ("ins", ins)):
+        if t is not None and (t.dtype != torch.int32 or t.dim() != 1):
+            raise TypeError("%s must be an int32 [n] tensor, got %s %s" % (name, t.dtype, tuple(t.shape)))
+    n_raw, n_classes = int(rows.shape[0]), int(n_classes)
+    if sem.shape[0] != n_raw or (ins is not None and ins.shape[0] != n_raw):
+        raise ValueError("vote_labels: %d rows, %d sem, %s ins" % (n_raw, sem.shape[0], None if ins is None else ins.shape[0]))
+    if not 1 <= n_classes <= VOTE_MAX_CLASSES:
+        raise ValueError("vote_labels: n_classes must lie in 1..%d, got %d" % (VOTE_MAX_CLASSES, n_classes))
+    if m is not None and int(m) < 0:
+        raise ValueError("vote_labels: m must not be negative, got %d" % m)
+    N.require_cuda(rows, sem, ins)
+    m = int(m) if m is not None else (int(rows.max().item()) + 1 if n_raw else 0)
+    rows, sem, ins = rows.contiguous(), sem.contiguous(), None if ins is None else ins.contiguous()
+    lib = N.lib()
+    nbytes = lib.pbn_cloud_vote_workspace_bytes(n_raw, m)
+    if nbytes == 0:
+        raise ValueError("point cloud too large for the library: %d raw points, %d rows" % (n_raw, m))
+    dev = rows.device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out_sem, out_ins = (torch.empty(m, dtype=torch.int64, device=dev) for _ in range(2))
+    votes, members = (torch.empty(m, dtype=torch.int32, device=dev) for _ in range(2))
+    old_id = torch.empty(max(1, min(m, VOTE_MAX_INS + 1)), dtype=torch.int64, device=dev) if compact else None
+    result = torch.empty(2, dtype=torch.int32, device=dev)
+    args = (N.ptr(rows), N.ptr(sem), N.ptr(ins), n_raw, m, n_classes, N.ptr(out_sem), N.ptr(out_ins), N.ptr(votes),
+            N.ptr(members), N.ptr(result), N.ptr(old_id), N.ptr(ws), ws.numel(), N.current_stream())
+    if times is None:
+        N.check(lib.pbn_cloud_vote_labels(*args), "pbn_cloud_vote_labels")
+    else:
+        t = (ctypes.c_float * len(VOTE_STAGES))()
+        N.check(lib.pbn_cloud_vote_labels_timed(*args, t), "pbn_cloud_vote_labels_timed")
+        times.update({name: float(t[i]) for i, name in enumerate(VOTE_STAGES)})
+    st, n_ins = (int(v) for v in result.tolist())            # the one read-back
+    if st & VOTE_SEM_RANGE:
+        raise ValueError("vote_labels: a semantic label is %d or more" % n_classes)
+    if st & VOTE_INS_RANGE:
+        raise ValueError("vote_labels: an instance label is %d or more" % VOTE_MAX_INS)
+    if st & VOTE_ROW_RANGE:
+        raise ValueError("vote_labels: a row lies outside [-1, %d)" % m)
+    if st:
+        raise RuntimeError("vote_labels: the device sort gave up (status %d)" % st)
+    return {"sem_label": out_sem, "ins_label": out_ins, "votes": votes, "members": members,
+            "old_id": old_id[:n_ins] if compact else torch.empty(0, dtype=torch.int64, device=dev)}
+
+
+def _raw_labels(name, labels, n):
+    """decode_points' label argument as a host int32 [n] array: integer arrays or tensors, or the float64 arrays the
+    reference's `.npy` files hold (integral values only)."""
+    a = labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+    if a.ndim != 1 or a.shape[0] != n:
+        raise ValueError("decode_points: %s must have shape [%d], got %s" % (name, n, tuple(a.shape)))
+    if a.dtype.kind == "f":
+        if not np.all(np.isfinite(a)) or not np.array_equal(a, np.rint(a)):
+            raise ValueError("decode_points: %s holds a value that is not an integer" % name)
+    elif a.dtype.kind not in "iu":
+        raise TypeError("decode_points: %s must be an integer or float array, got %s" % (name, a.dtype))
+    if a.size and (a.min() < -(2 ** 31) or a.max() > 2 ** 31 - 1):
+        raise ValueError("decode_points: %s holds a value outside int32" % name)
+    return np.ascontiguousarray(a.astype(np.int32))
+
+
 # ------------------------------------------------------------------------------------------------------------ PLY
 _PLY_SCALARS = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
                 "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
@@ -512,7 +591,7 @@ def _kept_points(xyz, colours, dev, k, pitch, outlier_ratio):
 
 
 def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpoint=None, return_graph=False, pitch=None,
-                  outlier_ratio=None, return_kept=False):
+                  outlier_ratio=None, return_kept=False, sem_label=None, ins_label=None, n_classes=20):
     """decode_mesh for a scan without faces: `src` is a vertex-only `.ply` path or (xyz [V,3], colours [V,3] 0..255).
     centre_and_scale -> knn_graph -> point_normals -> knn_edges -> segment_point.  Returns xyz (mean-centred), rgb, nl and
     sup on `device` -- what SceneCache and save_decoded take (no `face`) -- plus idx and d2 when return_graph is set.
@@ -523,12 +602,26 @@ def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpo
     mu + ratio * sigma are dropped (knn_graph over k neighbours, outlier_mask); the chain above then runs on the kept
     points exactly as if they had been given as `src`.  The result gains raw_index (int32 [V]: for every raw point its row
     among the kept points, -1 = none; see raw_index and carry_labels) and count (int32: raw points behind each kept one),
-    and with return_kept also kept_xyz / kept_rgb, the kept points before centring and scaling."""
+    and with return_kept also kept_xyz / kept_rgb, the kept points before centring and scaling.
+
+    An annotated scan: `sem_label` and `ins_label` (both or neither; one per raw point; integer arrays or tensors, or the
+    float64 arrays the reference's `.npy` files hold; negative = unannotated) are voted down to the kept points over the
+    final raw_index (vote_labels, `n_classes`): a raw point whose cell was dropped as an outlier votes for the kept
+    neighbour that speaks for it, a point with -1 for nobody.  The result gains sem_label, ins_label (int64, -100 =
+    unannotated, instance ids renumbered 0..I'-1), votes, members and ins_old_id (vote_labels' old_id).  Without pitch
+    and outlier_ratio the labels pass through with the renumbering only (sem_label, ins_label, ins_old_id)."""
     if isinstance(src, (str, bytes)) or hasattr(src, "__fspath__"):
         xyz, colours = read_ply_points(src)
     else:
         xyz, colours = (t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t) for t in src)
+    if (sem_label is None) != (ins_label is None):
+        raise ValueError("decode_points: give both sem_label and ins_label, or neither")
     dev = torch.device(device)
+    labels = None
+    if sem_label is not None:
+        n_raw = int(np.asarray(xyz).reshape(-1, 3).shape[0])
+        labels = [_raw_labels(name, v, n_raw) for name, v in (("sem_label", sem_label), ("ins_label", ins_label))]
+        labels = [torch.from_numpy(a).to(dev) for a in labels]
     raw = None
     if pitch is not None or outlier_ratio is not None:
         xyz, colours, *raw = _kept_points(xyz, colours, dev, k, pitch, outlier_ratio)
@@ -546,16 +639,29 @@ def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpo
         out.update(raw_index=raw[0], count=raw[1])
         if return_kept:
             out.update(kept_xyz=torch.from_numpy(xyz).to(dev), kept_rgb=torch.from_numpy(colours).to(dev))
+    if labels is not None:
+        m = int(xyz_d.shape[0])
+        rows = raw[0] if raw is not None else torch.arange(m, dtype=torch.int32, device=dev)
+        v = vote_labels(rows, labels[0], labels[1], m=m, n_classes=n_classes)
+        out.update(sem_label=v["sem_label"], ins_label=v["ins_label"], ins_old_id=v["old_id"])
+        if raw is not None:
+            out.update(votes=v["votes"], members=v["members"])
     return out
+
+
+SCENE_BOOKKEEPING = ("votes", "members", "ins_old_id", "raw_index", "count")       # of a decode, not of a scene on disk
 
 
 def save_decoded(npy_dir, scene, decoded, sem_label=None, ins_label=None):
     """Write a decode_mesh result under the reference's names (`<scene>_xyz.npy` ...).  Without labels (a test-split scene
-    or a user's own room) only xyz, rgb, nl, face and sup are written, as decode_scannet.py f_test does."""
-    arrays = {k: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in decoded.items()}
+    or a user's own room) only xyz, rgb, nl, face and sup are written, as decode_scannet.py f_test does.  A decode_points
+    result that carries its own sem_label / ins_label (an annotated scan) is written with them when none are passed; the
+    bookkeeping arrays of a raw scan (votes, members, ins_old_id, raw_index, count) are never scene files."""
+    arrays = {k: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in decoded.items()
+              if k not in SCENE_BOOKKEEPING}
     if (sem_label is None) != (ins_label is None):
         raise ValueError("save_decoded: give both sem_label and ins_label, or neither")
     if sem_label is not None:
         scene_io.save_scene(npy_dir, scene, sem_label=sem_label, ins_label=ins_label, **arrays)
     else:
-        scene_io.save_arrays(npy_dir, scene, **arrays)
+        scene_io.save_arrays(npy_dir, scene, **arrays)          # the dict's own labels included; a scan has no face file
