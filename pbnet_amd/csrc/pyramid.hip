@@ -112,7 +112,8 @@ __global__ __launch_bounds__(TPB) void k_unique_keys(const int* __restrict__ coo
     __syncthreads();
     const int n = real_n(n_dev, n_max);
     const KeyPlan kp = key_plan(plan);
-    if (blockIdx.x == 0 && threadIdx.x == 0 && kp.nbits > MAX_PASSES * RADIX_BITS) atomicOr(status, PBN_STATUS_KEY_BITS);
+    // (no rows -- a device-side count of 0 --: the box is still the fill pattern, not a box too wide)
+    if (blockIdx.x == 0 && threadIdx.x == 0 && n > 0 && kp.nbits > MAX_PASSES * RADIX_BITS) atomicOr(status, PBN_STATUS_KEY_BITS);
     const SortPlan sp = sort_plan(min(kp.nbits, MAX_PASSES * RADIX_BITS));
     const int passes = sp.passes;
     const unsigned dmask = (1u << sp.dbits) - 1u;
@@ -572,7 +573,7 @@ __global__ __launch_bounds__(TPB) void k_pyramid(const u64* __restrict__ keys_a,
             if ((f[k] >> (l - 1)) & 1) {                                 // first row of the level-l voxel: its coordinates
                 const int m = ~((1 << l) - 1);
                 reinterpret_cast<int4*>(o.coords[l])[id[l - 1]] = make_int4(cc.x, cc.y & m, cc.z & m, cc.w & m);
-                if (l >= 2) o.lkeys[l - 2][id[l - 1]] = key[k] >> (3 * l);
+                if (l >= 2) o.lkeys[l - 2][id[l - 1]] = key[k] >> (3 * min(l, kp.e));
             }
             row = id[l - 1];
         }
@@ -586,7 +587,9 @@ __device__ __forceinline__ void cube_offset(int k, int ksize, int x_fastest, int
     dx = x_fastest ? a : c; dy = b; dz = x_fastest ? c : a;
 }
 
-// levels 2..4 (k = 3): binary search in the level's sorted keys
+// levels 2..4 (k = 3): binary search in the level's sorted keys.  A level's key is the row's key without the 3 * l lowest bits of
+// its SPATIAL part only: a box narrower than a level-l voxel (e < l) holds one voxel per batch, and the batch bits above 3 * e
+// must stay or the voxels of all batches share one key
 struct TopJobs { const int* coords[3]; const u64* lkeys[3]; int* nbr[3]; const int* counts; int n_max, x_fastest; };
 __global__ __launch_bounds__(TPB) void k_maps_top(const TopJobs jb, const int* __restrict__ plan) {
     const KeyPlan kp = key_plan(plan);
@@ -607,7 +610,7 @@ __global__ __launch_bounds__(TPB) void k_maps_top(const TopJobs jb, const int* _
         const int lim = 1 << kp.e;
         if (x >= 0 && y >= 0 && z >= 0 && x < lim && y < lim && z < lim) {
             const u64 want = (((u64)(unsigned)(cc.x - kp.b0) << (3 * kp.e)) | spread3((unsigned)x) | (spread3((unsigned)y) << 1) |
-                              (spread3((unsigned)z) << 2)) >> (3 * l);
+                              (spread3((unsigned)z) << 2)) >> (3 * min(l, kp.e));
             const u64* keys = jb.lkeys[j];
             int lo = 0, hi = min(jb.counts[l], jb.n_max);
             while (lo < hi) {

@@ -18,96 +18,9 @@ import pbnet_amd.MinkowskiEngine as ME
 from pbnet_amd import _native as N
 from pbnet_amd import synth
 from pbnet_amd.MinkowskiEngine import conventions as CV
+from pyramid_ref import DEV, _arrays, _is_z_ordered, _prepare, _view, canonical as _canonical
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def _prepare(coords, which, n_dev=None, want_k5=1):
-    lib = N.lib()
-    n = int(coords.shape[0])
-    P = N.PrepareLayout()
-    nbytes = lib.pbn_coords_prepare_bytes(n, want_k5, ctypes.byref(P))
-    arena = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
-    fn = lib.pbn_coords_prepare_hash if which == "hash" else lib.pbn_coords_prepare_dev
-    if which == "sorted" and n_dev is None:
-        rc = lib.pbn_coords_prepare(N.ptr(coords), n, want_k5, int(CV.X_FASTEST), N.ptr(arena), nbytes, ctypes.byref(P),
-                                    N.current_stream())
-    else:
-        rc = fn(N.ptr(coords), None if n_dev is None else N.ptr(n_dev), n, want_k5, int(CV.X_FASTEST), N.ptr(arena), nbytes,
-                ctypes.byref(P), N.current_stream())
-    N.check(rc, "prepare " + which)
-    torch.cuda.synchronize()
-    return arena, P
-
-
-def _view(arena, off, count, dtype):
-    nb = count * torch.empty(0, dtype=dtype).element_size()
-    return arena[off:off + nb].view(dtype).cpu().numpy()
-
-
-def _arrays(arena, P, n, n_in=None):
-    """Every output of the contract (include/pbnet_hip.h: pbn_prepare_layout), cut to its meaningful extent."""
-    L = P.pyramid
-    counts = _view(arena, L.counts, 5, torch.int32)
-    out = {"counts": counts.copy(), "n_unique": _view(arena, P.n_unique, 1, torch.int32).copy()}
-    if counts[0] < 0:
-        return out
-    n1 = int(counts[0])
-    out["unique_index"] = _view(arena, P.unique_index, n, torch.int64)[:n1]
-    out["inverse"] = _view(arena, P.inverse, n, torch.int64)[:n if n_in is None else n_in]      # one entry per INPUT row
-    out["perm"] = _view(arena, P.perm, n, torch.int64)[:n1]
-    out["inv_perm"] = _view(arena, P.inv_perm, n, torch.int64)[:n1]
-    out["ucoords"] = _view(arena, P.ucoords, n * 4, torch.int32).reshape(n, 4)[:n1]
-    for l in range(5):
-        nl = int(counts[l])
-        out["coords%d" % l] = _view(arena, L.coords[l], n * 4, torch.int32).reshape(n, 4)[:nl]
-        out["k3_%d" % l] = _view(arena, L.k3[l], n * 27, torch.int32).reshape(n, 27)[:nl]
-    out["k5"] = _view(arena, L.k5, n * 125, torch.int32).reshape(n, 125)[:n1]
-    for l in range(4):
-        nf, nc = int(counts[l]), int(counts[l + 1])
-        out["parent_row%d" % l] = _view(arena, L.parent_row[l], n, torch.int32)[:nf]
-        out["child_k%d" % l] = _view(arena, L.child_k[l], n, torch.int32)[:nf]
-        out["nbr_down%d" % l] = _view(arena, L.nbr_down[l], n * 8, torch.int32).reshape(n, 8)[:nc]
-        out["up%d" % l] = _view(arena, L.up[l], n * 8, torch.int32).reshape(n, 8)[:nf]
-    return out
-
-
-def _pk(c):
-    """[n,4] coordinates -> one int64 per row (order-preserving per field)."""
-    c = c.astype(np.int64)
-    return (c[:, 0] << 48) | ((c[:, 1] + 32768) << 32) | ((c[:, 2] + 32768) << 16) | (c[:, 3] + 32768)
-
-
-def _canonical(a):
-    """The same contract with every row REFERENCE replaced by the coordinate key of the row it names, and the rows of every
-    level put in coordinate-key order: equal for any two Z-orders of the same lineage.  (The origin of the Z-order curve is an
-    implementation choice: the hash pipeline interleaves x + 32768, pyramid.hip x - box minimum rounded to 16; both keep the
-    children of a voxel contiguous, and convolution results do not depend on the row order.)"""
-    out = {k: a[k] for k in ("counts", "n_unique", "unique_index", "inverse", "ucoords")}
-    keys = [_pk(a["coords%d" % l]) for l in range(5)]
-    order = [np.argsort(k, kind="stable") for k in keys]
-    ref = lambda l, idx: np.where(idx >= 0, keys[l][np.maximum(idx, 0)], -1)           # row ids of level l -> coordinate keys
-    assert np.array_equal(a["inv_perm"][a["perm"]], np.arange(len(a["perm"])))
-    for l in range(5):
-        out["coords%d" % l] = a["coords%d" % l][order[l]]
-        out["k3_%d" % l] = ref(l, a["k3_%d" % l])[order[l]]
-    out["k5"] = ref(0, a["k5"])[order[0]]
-    for l in range(4):
-        out["parent_row%d" % l] = ref(l + 1, a["parent_row%d" % l])[order[l]]
-        out["child_k%d" % l] = a["child_k%d" % l][order[l]]
-        out["nbr_down%d" % l] = ref(l, a["nbr_down%d" % l])[order[l + 1]]
-        out["up%d" % l] = ref(l + 1, a["up%d" % l])[order[l]]
-    return out
-
-
-def _is_z_ordered(a):
-    """Children of a voxel are contiguous at every level and parents are numbered in the order of their first child."""
-    for l in range(4):
-        p = a["parent_row%d" % l]
-        if len(p) and not (p[0] == 0 and np.all(np.diff(p) >= 0) and np.all(np.diff(p) <= 1)):
-            return False
-    return True
 
 
 def _compare(coords_np, n_dev=None, exact=False):
