@@ -46,17 +46,13 @@
 // sweeps (no data-dependent loop); flipped towards the viewpoint; rounded to float32.  |S| < 3 gives the zero vector.
 #include <cmath>
 
-#include "coords_dev.h"
+#include "sort_dev.h"
 
 namespace pbn {
 namespace {
 
-typedef unsigned long long u64;
-constexpr int RADIX_U32 = 1 << RADIX_U32_DIGIT_BITS;
-constexpr int CLOUD_MAX_K = 32;
-constexpr int CLOUD_MAX_POINTS = 1 << 28;
 constexpr int CLOUD_AXIS_CELLS = 1024;
-constexpr int CLOUD_NONFINITE = 1;                // status bit: a coordinate is NaN or infinite
+constexpr int CLOUD_EVENTS = 5;                   // around: box + grid | keys + sort | table | search
 constexpr u64 CLOUD_PAD_KEY = ((u64)0x7f800000u << 32) | 0xffffffffu;   // d2 = +inf, idx = -1: after every real candidate
 constexpr int JACOBI_SWEEPS = 10;
 constexpr double BOUND_SLACK = 1.0 / 274877906944.0;          // 2^-38 (see the header)
@@ -68,14 +64,6 @@ struct CloudGrid {
     int dim[3];
     int pad;
 };
-
-__device__ __forceinline__ unsigned okey32(float v) {
-    const unsigned b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float okey32_val(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 
 // the ONE expression behind both the cell assignment and the stopping bound
 __device__ __forceinline__ double cloud_t(double p, double mn, double inv) { return (p - mn) * inv; }
@@ -106,7 +94,7 @@ __global__ __launch_bounds__(TPB) void k_cloud_box(const float* __restrict__ xyz
     if (lane_id() == 0) {
         atomicMin(&box[0], lo0); atomicMin(&box[1], lo1); atomicMin(&box[2], lo2);
         atomicMax(&box[3], hi0); atomicMax(&box[4], hi1); atomicMax(&box[5], hi2);
-        if (bad) atomicOr(status, CLOUD_NONFINITE);
+        if (bad) atomicOr(status, SCAN_NONFINITE);
     }
 }
 
@@ -159,7 +147,7 @@ __global__ __launch_bounds__(TPB) void k_cloud_keys(const float* __restrict__ xy
                                                     u64* __restrict__ keys, int* __restrict__ vals,
                                                     unsigned* __restrict__ ghist) {
     __shared__ unsigned s_hist[RADIX_U32_PASSES][RADIX_U32];
-    for (int e = threadIdx.x; e < RADIX_U32_PASSES * RADIX_U32; e += TPB) (&s_hist[0][0])[e] = 0u;
+    hist_clear(s_hist);
     __syncthreads();
     const double m0 = g->mn[0], m1 = g->mn[1], m2 = g->mn[2], inv = g->inv;
     const int d0 = g->dim[0], d1 = g->dim[1], d2 = g->dim[2];
@@ -170,15 +158,10 @@ __global__ __launch_bounds__(TPB) void k_cloud_keys(const float* __restrict__ xy
         const unsigned key = ((unsigned)cz << 20) | ((unsigned)cy << 10) | (unsigned)cx;
         keys[i] = (u64)key;
         vals[i] = i;
-#pragma unroll
-        for (int p = 0; p < RADIX_U32_PASSES; ++p)
-            atomicAdd(&s_hist[p][(key >> (p * RADIX_U32_DIGIT_BITS)) & (RADIX_U32 - 1)], 1u);
+        hist_add(s_hist, key);
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < RADIX_U32_PASSES * RADIX_U32; e += TPB) {
-        const unsigned v = (&s_hist[0][0])[e];
-        if (v) atomicAdd(&ghist[e], v);
-    }
+    hist_flush(s_hist, ghist);
 }
 
 // ---- table -------------------------------------------------------------------------------------------------------------
@@ -356,8 +339,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 4))) voi
 
 // ---- workspace -------------------------------------------------------------------------------------------------------
 struct CloudWs {
-    unsigned* box; CloudGrid* grid; u64* keys_a; u64* keys_b; int* vals_a; int* vals_b; unsigned* ghist;
-    void* sort_scratch; size_t sort_bytes; float4* pts; int* table; int t_cap;
+    unsigned* box; CloudGrid* grid; SortBufs sort; float4* pts; int* table; int t_cap;
 };
 
 int table_cap(int n) {
@@ -370,11 +352,7 @@ CloudWs carve(Carver& cv, int n) {
     const size_t N = (size_t)(n > 0 ? n : 1);
     w.box = cv.take<unsigned>(64);
     w.grid = cv.take<CloudGrid>(1);
-    w.keys_a = cv.take<u64>(N); w.keys_b = cv.take<u64>(N);
-    w.vals_a = cv.take<int>(N); w.vals_b = cv.take<int>(N);
-    w.ghist = cv.take<unsigned>((size_t)RADIX_U32_PASSES * RADIX_U32);
-    w.sort_bytes = radix_sort_u32_scratch_bytes((int)N);
-    w.sort_scratch = cv.take<char>(w.sort_bytes);
+    w.sort = sort_carve(cv, N, 1);
     w.pts = cv.take<float4>(N);
     w.t_cap = table_cap(n);
     w.table = cv.take<int>(2 * (size_t)w.t_cap);
@@ -387,43 +365,41 @@ size_t ws_bytes(int n) {
     return cv.off + 256;
 }
 
-int grid_for(long long n) { const long long b = (n + TPB - 1) / TPB; return (int)(b < 1 ? 1 : b > 1024 ? 1024 : b); }
+bool bad_sizes(int n, int k) { return n < 0 || n > SCAN_MAX_POINTS || k < 1 || k > SCAN_MAX_K; }
 
-bool bad_sizes(int n, int k) { return n < 0 || n > CLOUD_MAX_POINTS || k < 1 || k > CLOUD_MAX_K; }
-
-// ev (optional): 5 events around box + grid | keys + sort | table | search
+// ev (optional): CLOUD_EVENTS events
 int cloud_knn(const float* xyz, int n, int k, float cell, int32_t* idx, float* d2, int32_t* status, void* workspace,
               size_t workspace_bytes, hipStream_t st, hipEvent_t* ev) {
     Carver cv(workspace, workspace_bytes);
     const CloudWs w = carve(cv, n);
     if (!cv.ok) return PBN_ERR_WORKSPACE;
     const FillRange fr[] = {{status, sizeof(int32_t), 0}, {w.box, 3 * sizeof(unsigned), 0xff},
-                            {w.box + 3, 3 * sizeof(unsigned), 0},
-                            {w.ghist, (size_t)RADIX_U32_PASSES * RADIX_U32 * sizeof(unsigned), 0},
+                            {w.box + 3, 3 * sizeof(unsigned), 0}, sort_hist_fill(w.sort, 0),
                             {w.table, 2 * (size_t)w.t_cap * sizeof(int), 0}};
     int rc = fill_ranges(fr, n > 0 ? 5 : 1, st);
     if (rc != PBN_OK) return rc;
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[0], st));
     if (n == 0) {
-        if (ev) for (int i = 1; i < 5; ++i) PBN_HIP_CHECK(hipEventRecord(ev[i], st));
+        if (ev) for (int i = 1; i < CLOUD_EVENTS; ++i) PBN_HIP_CHECK(hipEventRecord(ev[i], st));
         return PBN_OK;
     }
     hipLaunchKernelGGL(k_cloud_box, dim3(grid_for(n)), dim3(TPB), 0, st, xyz, n, w.box, status);
     hipLaunchKernelGGL(k_cloud_grid, dim3(1), dim3(64), 0, st, w.box, status, n, k, cell, w.t_cap, w.grid);
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[1], st));
-    hipLaunchKernelGGL(k_cloud_keys, dim3(grid_for(n)), dim3(TPB), 0, st, xyz, n, w.grid, w.keys_a, w.vals_a, w.ghist);
+    hipLaunchKernelGGL(k_cloud_keys, dim3(grid_for(n)), dim3(TPB), 0, st, xyz, n, w.grid, w.sort.keys_a, w.sort.vals_a,
+                       w.sort.ghist[0]);
     PBN_LAUNCH_CHECK();
-    rc = radix_sort_u32(w.keys_a, w.keys_b, w.vals_a, w.vals_b, n, w.ghist, status, w.sort_scratch, w.sort_bytes, st);
+    rc = sort_run(w.sort, 0, n, status, st);
     if (rc != PBN_OK) return rc;
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[2], st));
-    hipLaunchKernelGGL(k_cloud_table, dim3(grid_for(n)), dim3(TPB), 0, st, w.keys_b, w.vals_b, n, xyz, w.grid, w.t_cap, w.table,
-                       w.pts);
+    hipLaunchKernelGGL(k_cloud_table, dim3(grid_for(n)), dim3(TPB), 0, st, w.sort.keys_b, w.sort.vals_b, n, xyz, w.grid, w.t_cap,
+                       w.table, w.pts);
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[3], st));
     const size_t lds = (size_t)k * TPB * sizeof(u64);
     static const bool lds_attr = (hipFuncSetAttribute((const void*)k_cloud_search, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                      (int)(CLOUD_MAX_K * TPB * sizeof(u64))) == hipSuccess);
+                                                      (int)(SCAN_MAX_K * TPB * sizeof(u64))) == hipSuccess);
     if (!lds_attr) return PBN_ERR_HIP;
-    hipLaunchKernelGGL(k_cloud_search, dim3((unsigned)cdiv(n, TPB)), dim3(TPB), lds, st, w.pts, w.keys_b,
+    hipLaunchKernelGGL(k_cloud_search, dim3((unsigned)cdiv(n, TPB)), dim3(TPB), lds, st, w.pts, w.sort.keys_b,
                        reinterpret_cast<const int2*>(w.table), w.grid, status, n, k, idx, d2);
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[4], st));
     PBN_LAUNCH_CHECK();
@@ -450,7 +426,7 @@ int cloud_box(const float* xyz, int n, unsigned* box, int32_t* status, hipStream
 
 using namespace pbn;
 
-extern "C" int pbn_cloud_max_k(void) { return CLOUD_MAX_K; }
+extern "C" int pbn_cloud_max_k(void) { return SCAN_MAX_K; }
 
 extern "C" size_t pbn_cloud_workspace_bytes(int n_points, int k) {
     if (bad_sizes(n_points, k)) return 0;
@@ -470,18 +446,9 @@ extern "C" int pbn_cloud_knn_timed(const float* xyz, int n_points, int k, float 
     if (rc != PBN_OK) return rc;
     if (!times_ms) return PBN_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    hipEvent_t ev[5];
-    int made = 0;
-    hipError_t e = hipSuccess;
-    for (; made < 5 && e == hipSuccess; ++made) e = hipEventCreate(&ev[made]);
-    int out = PBN_OK;
-    if (e != hipSuccess) { --made; g_last_hip_error = (int)e; out = PBN_ERR_HIP; }
-    if (out == PBN_OK) out = cloud_knn(xyz, n_points, k, cell, idx, d2, status, workspace, workspace_bytes, st, ev);
-    if (out == PBN_OK && (e = hipStreamSynchronize(st)) != hipSuccess) { g_last_hip_error = (int)e; out = PBN_ERR_HIP; }
-    for (int i = 0; i < 4 && out == PBN_OK; ++i)
-        if ((e = hipEventElapsedTime(&times_ms[i], ev[i], ev[i + 1])) != hipSuccess) { g_last_hip_error = (int)e; out = PBN_ERR_HIP; }
-    for (int i = 0; i < made; ++i) (void)hipEventDestroy(ev[i]);
-    return out;
+    return timed_stages<CLOUD_EVENTS>(st, times_ms, [&](hipEvent_t* ev) {
+        return cloud_knn(xyz, n_points, k, cell, idx, d2, status, workspace, workspace_bytes, st, ev);
+    });
 }
 
 extern "C" int pbn_cloud_normals(const float* xyz, int n_points, const int32_t* idx, int k, const float* viewpoint, float* nl,

@@ -25,21 +25,15 @@
 #include <cmath>
 #include <vector>
 
-#include "coords_dev.h"
+#include "sort_dev.h"
 
 namespace pbn {
 namespace {
 
-typedef unsigned long long u64;
-constexpr int RADIX_U32 = 1 << RADIX_U32_DIGIT_BITS;
-constexpr int MESH_BAD_INDEX = 1;                 // status bit: an index outside [0, V)
-constexpr int MESH_SORT_SPIN = 8;                 // status bit raised by radix_sort_u32
+constexpr int MESH_BAD_INDEX = 1;                 // status bit: an index outside [0, V); shares the word with SCAN_SORT_SPIN
+constexpr int MESH_GRID = 4096;                   // cap of the striding grids (k_edge_weights keeps grid_for's 1024)
 
 enum { MODE_NORMALS = 0, MODE_SEGMENT = 1, MODE_POINT = 2 };
-
-__device__ __forceinline__ long long load_index(const void* p, int i64, long long i) {
-    return i64 ? reinterpret_cast<const long long*>(p)[i] : (long long)reinterpret_cast<const int*>(p)[i];
-}
 
 __device__ __forceinline__ float3 ld3(const float* __restrict__ p, int i) {
     return make_float3(p[3 * (size_t)i], p[3 * (size_t)i + 1], p[3 * (size_t)i + 2]);
@@ -171,7 +165,7 @@ __global__ __launch_bounds__(TPB) void k_edge_weights(const float* __restrict__ 
                                                       float* __restrict__ w_out, u64* __restrict__ keys,
                                                       int* __restrict__ vals, unsigned* __restrict__ ghist) {
     __shared__ unsigned s_hist[RADIX_U32_PASSES][RADIX_U32];
-    for (int e = threadIdx.x; e < RADIX_U32_PASSES * RADIX_U32; e += TPB) (&s_hist[0][0])[e] = 0u;
+    hist_clear(s_hist);
     __syncthreads();
     for (int e = blockIdx.x * TPB + threadIdx.x; e < n_edges; e += gridDim.x * TPB) {
         int a, b;
@@ -191,15 +185,10 @@ __global__ __launch_bounds__(TPB) void k_edge_weights(const float* __restrict__ 
         const unsigned key = order_key(ww);
         keys[e] = (u64)key;
         vals[e] = e;
-#pragma unroll
-        for (int p = 0; p < RADIX_U32_PASSES; ++p)
-            atomicAdd(&s_hist[p][(key >> (p * RADIX_U32_DIGIT_BITS)) & (RADIX_U32 - 1)], 1u);
+        hist_add(s_hist, key);
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < RADIX_U32_PASSES * RADIX_U32; e += TPB) {
-        const unsigned v = (&s_hist[0][0])[e];
-        if (v) atomicAdd(&ghist[e], v);
-    }
+    hist_flush(s_hist, ghist);
 }
 
 // sorted edge i -> (a, b, w) in the read-back block (int32 a[E], int32 b[E], float w[E])
@@ -274,8 +263,7 @@ void sweep(int n_vertices, int n_edges, const int* ea, const int* eb, const floa
 // ---- workspace -------------------------------------------------------------------------------------------------------
 struct MeshWs {
     int* status; int* idx32; int* cnt; int* cur; int* off; int* scan_tmp; int* inc; float* nfa; float* snf; float* sn;
-    float* w; u64* keys_a; u64* keys_b; int* vals_a; int* vals_b; unsigned* ghist; void* sort_scratch; size_t sort_bytes;
-    int* readback; int* root; int* rank;
+    float* w; SortBufs sort; int* readback; int* root; int* rank;
 };
 
 // n_elems: faces (mesh modes) or edges (MODE_POINT)
@@ -302,11 +290,7 @@ MeshWs carve(Carver& cv, int mode, int n_vertices, int n_elems) {
     if (mode != MODE_NORMALS) {
         const size_t EE = E ? E : 1;
         w.w = cv.take<float>(EE);
-        w.keys_a = cv.take<u64>(EE); w.keys_b = cv.take<u64>(EE);
-        w.vals_a = cv.take<int>(EE); w.vals_b = cv.take<int>(EE);
-        w.ghist = cv.take<unsigned>((size_t)RADIX_U32_PASSES * RADIX_U32);
-        w.sort_bytes = radix_sort_u32_scratch_bytes((int)EE);
-        w.sort_scratch = cv.take<char>(w.sort_bytes);
+        w.sort = sort_carve(cv, EE, 1);
         w.readback = cv.take<int>(3 * EE);
         w.root = cv.take<int>(V);
         w.rank = cv.take<int>(V + 1);
@@ -319,8 +303,6 @@ size_t ws_bytes(int mode, int n_vertices, int n_elems) {
     carve(cv, mode, n_vertices, n_elems);
     return cv.off + 256;
 }
-
-int grid_for(long long n) { const long long b = (n + TPB - 1) / TPB; return (int)(b < 1 ? 1 : b > 4096 ? 4096 : b); }
 
 bool bad_sizes(int mode, int n_vertices, int n_elems) {
     if (n_vertices < 0 || n_elems < 0) return true;
@@ -335,14 +317,14 @@ int mesh_normals(const MeshWs& w, const float* xyz, int V, const void* faces, in
                             {w.cur, (size_t)(V > 0 ? V : 1) * sizeof(int), 0}};
     int rc = fill_ranges(fr, 3, st);
     if (rc != PBN_OK) return rc;
-    if (n_idx) hipLaunchKernelGGL(k_mesh_index, dim3(grid_for(n_idx)), dim3(TPB), 0, st, faces, i64, n_idx, V, w.idx32, w.cnt,
+    if (n_idx) hipLaunchKernelGGL(k_mesh_index, dim3(grid_for(n_idx, MESH_GRID)), dim3(TPB), 0, st, faces, i64, n_idx, V, w.idx32, w.cnt,
                                   w.status);
     rc = scan_exclusive_i32(w.cnt, w.off, V, w.scan_tmp, w.off + V, st);
     if (rc != PBN_OK) return rc;
-    if (n_idx) hipLaunchKernelGGL(k_mesh_fill, dim3(grid_for(n_idx)), dim3(TPB), 0, st, w.idx32, n_idx, w.off, w.cur, w.inc);
+    if (n_idx) hipLaunchKernelGGL(k_mesh_fill, dim3(grid_for(n_idx, MESH_GRID)), dim3(TPB), 0, st, w.idx32, n_idx, w.off, w.cur, w.inc);
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[1], st));
-    if (F) hipLaunchKernelGGL(k_face_normals, dim3(grid_for(F)), dim3(TPB), 0, st, xyz, w.idx32, F, w.nfa, w.snf);
-    if (V) hipLaunchKernelGGL(k_vertex_normals, dim3(grid_for(V)), dim3(TPB), 0, st, w.off, w.inc, V, w.nfa, w.snf, nl, w.sn);
+    if (F) hipLaunchKernelGGL(k_face_normals, dim3(grid_for(F, MESH_GRID)), dim3(TPB), 0, st, xyz, w.idx32, F, w.nfa, w.snf);
+    if (V) hipLaunchKernelGGL(k_vertex_normals, dim3(grid_for(V, MESH_GRID)), dim3(TPB), 0, st, w.off, w.inc, V, w.nfa, w.snf, nl, w.sn);
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[2], st));
     PBN_LAUNCH_CHECK();
     return PBN_OK;
@@ -352,17 +334,19 @@ int mesh_normals(const MeshWs& w, const float* xyz, int V, const void* faces, in
 int mesh_segment(const MeshWs& w, int mode, const float* xyz, const float* nrm, int V, int E, float c, int min_size,
                  int64_t* sup, hipStream_t st, hipEvent_t* ev, float* times_ms) {
     if (E) {
-        const int frc = fill_bytes(w.ghist, 0, (size_t)RADIX_U32_PASSES * RADIX_U32 * sizeof(unsigned), st);
+        const FillRange fr = sort_hist_fill(w.sort, 0);
+        const int frc = fill_ranges(&fr, 1, st);
         if (frc != PBN_OK) return frc;
-        hipLaunchKernelGGL(k_edge_weights, dim3(grid_for(E) < 1024 ? grid_for(E) : 1024), dim3(TPB), 0, st, xyz, nrm, w.idx32,
-                           mode, E, w.w, w.keys_a, w.vals_a, w.ghist);
+        hipLaunchKernelGGL(k_edge_weights, dim3(grid_for(E)), dim3(TPB), 0, st, xyz, nrm, w.idx32, mode, E, w.w, w.sort.keys_a,
+                           w.sort.vals_a, w.sort.ghist[0]);
         PBN_LAUNCH_CHECK();
     }
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[3], st));
-    int rc = radix_sort_u32(w.keys_a, w.keys_b, w.vals_a, w.vals_b, E, w.ghist, w.status, w.sort_scratch, w.sort_bytes, st);
+    int rc = sort_run(w.sort, 0, E, w.status, st);
     if (rc != PBN_OK) return rc;
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[4], st));
-    if (E) hipLaunchKernelGGL(k_edge_gather, dim3(grid_for(E)), dim3(TPB), 0, st, w.vals_b, w.idx32, mode, E, w.w, w.readback);
+    if (E) hipLaunchKernelGGL(k_edge_gather, dim3(grid_for(E, MESH_GRID)), dim3(TPB), 0, st, w.sort.vals_b, w.idx32, mode, E, w.w,
+                              w.readback);
     PBN_LAUNCH_CHECK();
     std::vector<int> host(3 * (size_t)E + 1);
     int status = 0;
@@ -371,7 +355,7 @@ int mesh_segment(const MeshWs& w, int mode, const float* xyz, const float* nrm, 
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[5], st));
     PBN_HIP_CHECK(hipStreamSynchronize(st));
     if (status & MESH_BAD_INDEX) return PBN_ERR_RANGE;
-    if (status & MESH_SORT_SPIN) return PBN_ERR_HIP;
+    if (status & SCAN_SORT_SPIN) return PBN_ERR_HIP;
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<int> root((size_t)(V > 0 ? V : 1));
     sweep(V, E, host.data(), host.data() + E, reinterpret_cast<const float*>(host.data() + 2 * (size_t)E), c, min_size,
@@ -380,10 +364,10 @@ int mesh_segment(const MeshWs& w, int mode, const float* xyz, const float* nrm, 
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[6], st));
     if (V) {
         PBN_HIP_CHECK(hipMemcpyAsync(w.root, root.data(), (size_t)V * sizeof(int), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_root_flags, dim3(grid_for(V)), dim3(TPB), 0, st, w.root, V, w.rank);
+        hipLaunchKernelGGL(k_root_flags, dim3(grid_for(V, MESH_GRID)), dim3(TPB), 0, st, w.root, V, w.rank);
         rc = scan_exclusive_i32(w.rank, w.rank, V, w.scan_tmp, nullptr, st);
         if (rc != PBN_OK) return rc;
-        hipLaunchKernelGGL(k_root_rank, dim3(grid_for(V)), dim3(TPB), 0, st, w.root, w.rank, V, sup);
+        hipLaunchKernelGGL(k_root_rank, dim3(grid_for(V, MESH_GRID)), dim3(TPB), 0, st, w.root, w.rank, V, sup);
         PBN_LAUNCH_CHECK();
     }
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[7], st));
@@ -399,16 +383,6 @@ int mesh_segment(const MeshWs& w, int mode, const float* xyz, const float* nrm, 
     }
     return PBN_OK;
 }
-
-struct Events {
-    hipEvent_t ev[8];
-    int n = 0;
-    ~Events() { for (int i = 0; i < n; ++i) (void)hipEventDestroy(ev[i]); }
-    hipError_t make() {
-        for (; n < 8; ++n) { const hipError_t e = hipEventCreate(&ev[n]); if (e != hipSuccess) return e; }
-        return hipSuccess;
-    }
-};
 
 }  // namespace
 }  // namespace pbn
@@ -445,7 +419,7 @@ extern "C" int pbn_mesh_segment(const float* xyz, int n_vertices, const void* fa
     Carver cv(workspace, workspace_bytes);
     const MeshWs w = carve(cv, MODE_SEGMENT, n_vertices, n_faces);
     if (!cv.ok) return PBN_ERR_WORKSPACE;
-    Events evs;
+    StageEvents<8> evs;
     if (times_ms) {
         PBN_HIP_CHECK(evs.make());
         PBN_HIP_CHECK(hipEventRecord(evs.ev[0], st));
@@ -469,7 +443,7 @@ extern "C" int pbn_mesh_segment_point(const float* xyz, const float* normals, in
     const int rc = fill_bytes(w.status, 0, 64 * sizeof(int), st);
     if (rc != PBN_OK) return rc;
     const long long n_idx = 2LL * n_edges;
-    if (n_idx) hipLaunchKernelGGL(k_mesh_index, dim3(grid_for(n_idx)), dim3(TPB), 0, st, edges, edges_i64, n_idx, n_points,
+    if (n_idx) hipLaunchKernelGGL(k_mesh_index, dim3(grid_for(n_idx, MESH_GRID)), dim3(TPB), 0, st, edges, edges_i64, n_idx, n_points,
                                   w.idx32, (int*)nullptr, w.status);
     PBN_LAUNCH_CHECK();
     return mesh_segment(w, MODE_POINT, xyz, normals, n_points, n_edges, k_thresh, seg_min_verts, sup, st, nullptr, nullptr);

@@ -52,6 +52,21 @@ __device__ __forceinline__ int wave_reduce_add(int v) {
     return v;
 }
 
+// element i of an int32 or int64 vector
+__device__ __forceinline__ long long load_index(const void* p, int is_i64, long long i) {
+    return is_i64 ? ((const long long*)p)[i] : (long long)((const int*)p)[i];
+}
+
+// order-preserving key of a float32 (augment.hip's okey for 32 bits): a < b  <=>  okey32(a) < okey32(b) as unsigned, so
+// integer atomicMin / atomicMax give a float minimum / maximum; NaN has no place in the order
+__device__ __forceinline__ unsigned okey32(float v) {
+    const unsigned b = __float_as_uint(v);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float okey32_val(unsigned k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
 // 64-bit finalizer (splitmix64) -> table slot
 __device__ __forceinline__ uint32_t hash64(uint64_t k) {
     k ^= k >> 30;
@@ -119,13 +134,14 @@ int coords_prepare_sorted(const int32_t* coords, const int32_t* n_dev, int n, in
                           const pbn_prepare_layout* P, hipStream_t stream);
 // pyramid.hip: its LSD radix sort (k_sort_pass's digit pass) for 32-bit keys in the low half of u64 keys, values carried;
 // stable, so ties keep the input order.  ghist: RADIX_U32_PASSES x 2048 digit histograms (digit p = key >> 11p & 2047),
-// filled by the caller; the result lands in keys_b / vals_b.  A chained scan that gives up ORs 8 into *status.
+// filled by the caller; the result lands in keys_b / vals_b.  A chained scan that gives up ORs SCAN_SORT_SPIN (8) into
+// *status.  sort_dev.h holds that name and what the callers share: histogram helpers, SortBufs, sort_run.
 constexpr int RADIX_U32_DIGIT_BITS = 11, RADIX_U32_PASSES = 3;
 size_t radix_sort_u32_scratch_bytes(int n);
 int radix_sort_u32(unsigned long long* keys_a, unsigned long long* keys_b, int32_t* vals_a, int32_t* vals_b, int n,
                    const unsigned* ghist, int32_t* status, void* scratch, size_t scratch_bytes, hipStream_t stream);
 // cloud.hip: k_cloud_box for thin.hip -- box[0..2] / box[3..5] = minimum / maximum per axis as order-preserving u32 keys
-// (the caller fills them with 0xff / 0 first), status |= 1 when a coordinate is NaN or infinite; n > 0
+// (the caller fills them with 0xff / 0 first), status |= SCAN_NONFINITE when a coordinate is NaN or infinite; n > 0
 int cloud_box(const float* xyz, int n, unsigned* box, int32_t* status, hipStream_t stream);
 // prepare.hip: device radix sort of (key, value) pairs; temp from sort_pairs_temp_bytes(n)
 size_t sort_pairs_temp_bytes(int n);

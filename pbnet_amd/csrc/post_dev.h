@@ -19,11 +19,6 @@ inline int stride_blocks(long long n) {
     return (int)(b < 1 ? 1 : (b > POST_STRIDE_BLOCKS ? POST_STRIDE_BLOCKS : b));
 }
 
-// element i of an int32 or int64 vector
-__device__ __forceinline__ long long load_index(const void* p, int is_i64, long long i) {
-    return is_i64 ? ((const long long*)p)[i] : (long long)((const int*)p)[i];
-}
-
 // exclusive position of `flag` among the 256 threads of the block, in thread order; *total = flags set.  s_wave: 4 ints.
 __device__ __forceinline__ int block_flag_scan(bool flag, int* s_wave, int* total) {
     const unsigned long long b = __ballot(flag);

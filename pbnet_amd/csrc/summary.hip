@@ -34,13 +34,6 @@ constexpr float COORD_LIMIT = 32768.0f, COORD_SCALE = 65536.0f;
 __host__ __device__ constexpr int acc_stride(int n_cls) { return (ACC_HIST + n_cls + 1) & ~1; }
 __host__ __device__ constexpr unsigned acc_init(int word) { return word >= ACC_MIN && word < ACC_MAX ? 0xffffffffu : 0u; }
 
-// order-preserving key of a float32 (augment.hip's okey for 32 bits): a < b  <=>  fkey(a) < fkey(b) as unsigned, no NaN goes in
-__device__ __forceinline__ unsigned fkey(float v) {
-    const unsigned b = __float_as_uint(v);
-    return (b >> 31) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float fkey_val(unsigned k) { return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k); }
-
 template <typename T>
 __device__ __forceinline__ float widen(T v) {
     if constexpr (sizeof(T) == 4) return v;
@@ -77,8 +70,8 @@ __device__ __forceinline__ void acc_point(unsigned* row, int cls, bool with_xyz,
     const float v[3] = {x, y, z};
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
-        atomicMin(&row[ACC_MIN + d], fkey(v[d]));
-        atomicMax(&row[ACC_MAX + d], fkey(v[d]));
+        atomicMin(&row[ACC_MIN + d], okey32(v[d]));
+        atomicMax(&row[ACC_MAX + d], okey32(v[d]));
         // |x| < 2^15, so x * 2^16 is exact and below 2^31 in magnitude; rintf rounds ties to even
         const long long q = (long long)rintf(v[d] * COORD_SCALE);
         atomicAdd((unsigned long long*)&row[ACC_SUM + 2 * d], (unsigned long long)q);
@@ -192,8 +185,8 @@ __global__ __launch_bounds__(TPB) void k_summary_final(const unsigned* __restric
 #pragma unroll
             for (int d = 0; d < 3; ++d) {
                 if (valid) {
-                    bx[d] = fkey_val(row[ACC_MIN + d]);
-                    bx[3 + d] = fkey_val(row[ACC_MAX + d]);
+                    bx[d] = okey32_val(row[ACC_MIN + d]);
+                    bx[3 + d] = okey32_val(row[ACC_MAX + d]);
                     const long long q = *(const long long*)&row[ACC_SUM + 2 * d];
                     ct[d] = (float)((double)q / (double)valid / 65536.0);
                 } else {

@@ -9,7 +9,7 @@
 //
 // Thinning.  Origin o[a] = the float32 minimum of axis a (cloud.hip's box kernel, with its non-finite flag).  Cell
 // c[a] = floor((double(p[a]) - double(o[a])) / pitch), one subtraction and one correctly rounded division; the quotient is
-// never negative.  c >= 2^21 on any axis raises THIN_EXTENT.  key = cz << 42 | cy << 21 | cx (63 bits).  Order (key, index):
+// never negative.  c >= 2^21 on any axis raises SCAN_EXTENT.  key = cz << 42 | cy << 21 | cx (63 bits).  Order (key, index):
 // radix_sort_u32 is stable and sorts 32-bit keys, so the low word goes first with values 0..n-1, then the high word with
 // the first sort's order as values; ties of the second keep the first's order, ties of both keep the index order.  Runs of
 // equal keys in that order are the cells: head flags, scan_exclusive_i32, and output row t is the t-th occupied cell in
@@ -24,37 +24,15 @@
 // mu = sum m_i / n_valid; sigma = sqrt(sum (m_i - mu)^2 / n_valid), a second pass; keep_i = m_i <= mu + ratio * sigma.
 #include <cmath>
 
-#include "coords_dev.h"
+#include "sort_dev.h"
 
 namespace pbn {
 namespace {
 
-typedef unsigned long long u64;
-constexpr int RADIX_U32 = 1 << RADIX_U32_DIGIT_BITS;
-constexpr int THIN_MAX_POINTS = 1 << 28;           // cloud.hip's CLOUD_MAX_POINTS
-constexpr int THIN_MAX_K = 32;                     // cloud.hip's CLOUD_MAX_K
-constexpr int THIN_NONFINITE = 1;                  // status bit of k_cloud_box
-constexpr int THIN_EXTENT = 2;                     // status bit: an axis spans 2^21 cells or more
 constexpr int THIN_AXIS_BITS = 21;
 constexpr double THIN_AXIS_CELLS = 2097152.0;      // 2^21
 
-__device__ __forceinline__ float okey32_val(unsigned k) {      // cloud.hip's decoding of its box keys
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
 __device__ __forceinline__ int in_rows(int j, int n) { return (unsigned)j < (unsigned)n ? j : 0; }   // only after a failed sort (flagged)
-
-// digit histograms of radix_sort_u32 for the low 32 bits of `key`
-__device__ __forceinline__ void hist_add(unsigned (*s_hist)[RADIX_U32], unsigned key) {
-#pragma unroll
-    for (int p = 0; p < RADIX_U32_PASSES; ++p) atomicAdd(&s_hist[p][(key >> (p * RADIX_U32_DIGIT_BITS)) & (RADIX_U32 - 1)], 1u);
-}
-__device__ __forceinline__ void hist_flush(unsigned (*s_hist)[RADIX_U32], unsigned* __restrict__ ghist) {
-    for (int e = threadIdx.x; e < RADIX_U32_PASSES * RADIX_U32; e += TPB) {
-        const unsigned v = (&s_hist[0][0])[e];
-        if (v) atomicAdd(&ghist[e], v);
-    }
-}
 
 // ---- thinning ----------------------------------------------------------------------------------------------------------
 // Keys are written whatever the status (0 for every point after a non-finite coordinate, 0 for a point outside the 2^21
@@ -63,9 +41,9 @@ __global__ __launch_bounds__(TPB) void k_thin_keys(const float* __restrict__ xyz
                                                    int* __restrict__ status, double pitch, u64* __restrict__ cellkey,
                                                    u64* __restrict__ keys, int* __restrict__ vals, unsigned* __restrict__ ghist) {
     __shared__ unsigned s_hist[RADIX_U32_PASSES][RADIX_U32];
-    for (int e = threadIdx.x; e < RADIX_U32_PASSES * RADIX_U32; e += TPB) (&s_hist[0][0])[e] = 0u;
+    hist_clear(s_hist);
     __syncthreads();
-    const bool bad = (*status & THIN_NONFINITE) != 0;                        // the box kernel's word: final before this launch
+    const bool bad = (*status & SCAN_NONFINITE) != 0;                        // the box kernel's word: final before this launch
     const double o0 = (double)okey32_val(box[0]), o1 = (double)okey32_val(box[1]), o2 = (double)okey32_val(box[2]);
     bool over = false;
     for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) {
@@ -84,7 +62,7 @@ __global__ __launch_bounds__(TPB) void k_thin_keys(const float* __restrict__ xyz
         vals[i] = i;
         hist_add(s_hist, (unsigned)key);
     }
-    if (over) atomicOr(status, THIN_EXTENT);
+    if (over) atomicOr(status, SCAN_EXTENT);
     __syncthreads();
     hist_flush(s_hist, ghist);
 }
@@ -93,7 +71,7 @@ __global__ __launch_bounds__(TPB) void k_thin_keys(const float* __restrict__ xyz
 __global__ __launch_bounds__(TPB) void k_thin_high(const u64* __restrict__ cellkey, const int* __restrict__ order, int n,
                                                    u64* __restrict__ keys, int* __restrict__ vals, unsigned* __restrict__ ghist) {
     __shared__ unsigned s_hist[RADIX_U32_PASSES][RADIX_U32];
-    for (int e = threadIdx.x; e < RADIX_U32_PASSES * RADIX_U32; e += TPB) (&s_hist[0][0])[e] = 0u;
+    hist_clear(s_hist);
     __syncthreads();
     for (int s = blockIdx.x * TPB + threadIdx.x; s < n; s += gridDim.x * TPB) {
         const int j = in_rows(order[s], n);
@@ -142,8 +120,7 @@ __global__ __launch_bounds__(TPB) void k_thin_cells(const float* __restrict__ xy
 }
 
 struct ThinWs {
-    unsigned* box; u64* cellkey; u64* keys_a; u64* keys_b; int* vals_a; int* vals_b; unsigned* ghist_lo; unsigned* ghist_hi;
-    void* sort_scratch; size_t sort_bytes; int* head; int* before; int* scan_tmp;
+    unsigned* box; u64* cellkey; SortBufs sort; int* head; int* before; int* scan_tmp;      // sort 0: low word, sort 1: high word
 };
 
 ThinWs thin_carve(Carver& cv, int n) {
@@ -151,12 +128,7 @@ ThinWs thin_carve(Carver& cv, int n) {
     const size_t N = (size_t)(n > 0 ? n : 1);
     w.box = cv.take<unsigned>(64);
     w.cellkey = cv.take<u64>(N);
-    w.keys_a = cv.take<u64>(N); w.keys_b = cv.take<u64>(N);
-    w.vals_a = cv.take<int>(N); w.vals_b = cv.take<int>(N);
-    w.ghist_lo = cv.take<unsigned>((size_t)RADIX_U32_PASSES * RADIX_U32);
-    w.ghist_hi = cv.take<unsigned>((size_t)RADIX_U32_PASSES * RADIX_U32);
-    w.sort_bytes = radix_sort_u32_scratch_bytes((int)N);
-    w.sort_scratch = cv.take<char>(w.sort_bytes);
+    w.sort = sort_carve(cv, N, 2);
     w.head = cv.take<int>(N); w.before = cv.take<int>(N);
     w.scan_tmp = cv.take<int>(scan_tmp_ints((long long)N));
     return w;
@@ -168,8 +140,6 @@ size_t thin_ws_bytes(int n) {
     return cv.off + 256;
 }
 
-int grid_for(long long n) { const long long b = (n + TPB - 1) / TPB; return (int)(b < 1 ? 1 : b > 1024 ? 1024 : b); }
-
 constexpr int THIN_EVENTS = 6;      // around: box + keys | low sort | high keys + sort | heads + scan | cells
 
 int thin_points(const float* xyz, const float* rgb, int n, double pitch, float* out_xyz, float* out_rgb, int32_t* count,
@@ -178,9 +148,8 @@ int thin_points(const float* xyz, const float* rgb, int n, double pitch, float* 
     Carver cv(workspace, workspace_bytes);
     const ThinWs w = thin_carve(cv, n);
     if (!cv.ok) return PBN_ERR_WORKSPACE;
-    const size_t hist_bytes = (size_t)RADIX_U32_PASSES * RADIX_U32 * sizeof(unsigned);
     const FillRange fr[] = {{result, 2 * sizeof(int32_t), 0}, {w.box, 3 * sizeof(unsigned), 0xff},
-                            {w.box + 3, 3 * sizeof(unsigned), 0}, {w.ghist_lo, hist_bytes, 0}, {w.ghist_hi, hist_bytes, 0}};
+                            {w.box + 3, 3 * sizeof(unsigned), 0}, sort_hist_fill(w.sort, 0), sort_hist_fill(w.sort, 1)};
     int rc = fill_ranges(fr, n > 0 ? 5 : 1, st);
     if (rc != PBN_OK) return rc;
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[0], st));
@@ -192,24 +161,26 @@ int thin_points(const float* xyz, const float* rgb, int n, double pitch, float* 
     const dim3 grid(grid_for(n)), block(TPB);
     rc = cloud_box(xyz, n, w.box, status, st);
     if (rc != PBN_OK) return rc;
-    hipLaunchKernelGGL(k_thin_keys, grid, block, 0, st, xyz, n, w.box, status, pitch, w.cellkey, w.keys_a, w.vals_a, w.ghist_lo);
+    hipLaunchKernelGGL(k_thin_keys, grid, block, 0, st, xyz, n, w.box, status, pitch, w.cellkey, w.sort.keys_a,
+                       w.sort.vals_a, w.sort.ghist[0]);
     PBN_LAUNCH_CHECK();
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[1], st));
-    rc = radix_sort_u32(w.keys_a, w.keys_b, w.vals_a, w.vals_b, n, w.ghist_lo, status, w.sort_scratch, w.sort_bytes, st);
+    rc = sort_run(w.sort, 0, n, status, st);
     if (rc != PBN_OK) return rc;
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[2], st));
-    hipLaunchKernelGGL(k_thin_high, grid, block, 0, st, w.cellkey, w.vals_b, n, w.keys_a, w.vals_a, w.ghist_hi);
+    hipLaunchKernelGGL(k_thin_high, grid, block, 0, st, w.cellkey, w.sort.vals_b, n, w.sort.keys_a, w.sort.vals_a,
+                       w.sort.ghist[1]);
     PBN_LAUNCH_CHECK();
-    rc = radix_sort_u32(w.keys_a, w.keys_b, w.vals_a, w.vals_b, n, w.ghist_hi, status, w.sort_scratch, w.sort_bytes, st);
+    rc = sort_run(w.sort, 1, n, status, st);
     if (rc != PBN_OK) return rc;
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[3], st));
-    hipLaunchKernelGGL(k_thin_heads, grid, block, 0, st, w.cellkey, w.vals_b, n, w.head);
+    hipLaunchKernelGGL(k_thin_heads, grid, block, 0, st, w.cellkey, w.sort.vals_b, n, w.head);
     PBN_LAUNCH_CHECK();
     rc = scan_exclusive_i32(w.head, w.before, n, w.scan_tmp, result + 1, st);
     if (rc != PBN_OK) return rc;
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[4], st));
-    hipLaunchKernelGGL(k_thin_cells, grid, block, 0, st, xyz, rgb, n, w.vals_b, w.head, w.before, status, out_xyz, out_rgb,
-                       count, first, inverse);
+    hipLaunchKernelGGL(k_thin_cells, grid, block, 0, st, xyz, rgb, n, w.sort.vals_b, w.head, w.before, status, out_xyz,
+                       out_rgb, count, first, inverse);
     PBN_LAUNCH_CHECK();
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[5], st));
     return PBN_OK;
@@ -218,7 +189,7 @@ int thin_points(const float* xyz, const float* rgb, int n, double pitch, float* 
 int thin_args(const float* xyz, const float* rgb, int n, double pitch, const float* out_xyz, const float* out_rgb,
               const int32_t* count, const int32_t* first, const int32_t* inverse, const int32_t* result, const void* workspace,
               size_t workspace_bytes) {
-    if (n < 0 || n > THIN_MAX_POINTS || !(pitch > 0.0) || !std::isfinite(pitch)) return PBN_ERR_ARG;
+    if (n < 0 || n > SCAN_MAX_POINTS || !(pitch > 0.0) || !std::isfinite(pitch)) return PBN_ERR_ARG;
     if ((n && (!xyz || !out_xyz || !count || !first || !inverse)) || (n && rgb && !out_rgb) || !result || !workspace)
         return PBN_ERR_ARG;
     if (workspace_bytes < thin_ws_bytes(n)) return PBN_ERR_WORKSPACE;
@@ -374,7 +345,7 @@ size_t raw_ws_bytes(int m) {
 using namespace pbn;
 
 extern "C" size_t pbn_thin_workspace_bytes(int n_points) {
-    if (n_points < 0 || n_points > THIN_MAX_POINTS) return 0;
+    if (n_points < 0 || n_points > SCAN_MAX_POINTS) return 0;
     return thin_ws_bytes(n_points);
 }
 
@@ -394,29 +365,20 @@ extern "C" int pbn_thin_points_timed(const float* xyz, const float* rgb, int n_p
     if (rc != PBN_OK) return rc;
     if (!times_ms) return PBN_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    hipEvent_t ev[THIN_EVENTS];
-    int made = 0;
-    hipError_t e = hipSuccess;
-    for (; made < THIN_EVENTS && e == hipSuccess; ++made) e = hipEventCreate(&ev[made]);
-    int out = PBN_OK;
-    if (e != hipSuccess) { --made; g_last_hip_error = (int)e; out = PBN_ERR_HIP; }
-    if (out == PBN_OK)
-        out = thin_points(xyz, rgb, n_points, pitch, out_xyz, out_rgb, count, first, inverse, result, workspace, workspace_bytes, st, ev);
-    if (out == PBN_OK && (e = hipStreamSynchronize(st)) != hipSuccess) { g_last_hip_error = (int)e; out = PBN_ERR_HIP; }
-    for (int i = 0; i + 1 < THIN_EVENTS && out == PBN_OK; ++i)
-        if ((e = hipEventElapsedTime(&times_ms[i], ev[i], ev[i + 1])) != hipSuccess) { g_last_hip_error = (int)e; out = PBN_ERR_HIP; }
-    for (int i = 0; i < made; ++i) (void)hipEventDestroy(ev[i]);
-    return out;
+    return timed_stages<THIN_EVENTS>(st, times_ms, [&](hipEvent_t* ev) {
+        return thin_points(xyz, rgb, n_points, pitch, out_xyz, out_rgb, count, first, inverse, result, workspace, workspace_bytes, st,
+                           ev);
+    });
 }
 
 extern "C" size_t pbn_cloud_outlier_workspace_bytes(int n_points) {
-    if (n_points < 0 || n_points > THIN_MAX_POINTS) return 0;
+    if (n_points < 0 || n_points > SCAN_MAX_POINTS) return 0;
     return outlier_ws_bytes(n_points);
 }
 
 extern "C" int pbn_cloud_outlier_mask(const float* d2, int n_points, int k, double ratio, uint8_t* keep, double* stats,
                                       void* workspace, size_t workspace_bytes, pbn_stream_t stream) {
-    if (n_points < 0 || n_points > THIN_MAX_POINTS || k < 1 || k > THIN_MAX_K || !(ratio >= 0.0) || !std::isfinite(ratio))
+    if (n_points < 0 || n_points > SCAN_MAX_POINTS || k < 1 || k > SCAN_MAX_K || !(ratio >= 0.0) || !std::isfinite(ratio))
         return PBN_ERR_ARG;
     if ((n_points && (!d2 || !keep)) || !stats || !workspace) return PBN_ERR_ARG;
     if (workspace_bytes < outlier_ws_bytes(n_points)) return PBN_ERR_WORKSPACE;
@@ -437,13 +399,13 @@ extern "C" int pbn_cloud_outlier_mask(const float* d2, int n_points, int k, doub
 }
 
 extern "C" size_t pbn_cloud_raw_index_workspace_bytes(int n_points) {
-    if (n_points < 0 || n_points > THIN_MAX_POINTS) return 0;
+    if (n_points < 0 || n_points > SCAN_MAX_POINTS) return 0;
     return raw_ws_bytes(n_points);
 }
 
 extern "C" int pbn_cloud_raw_index(const int32_t* inverse, int n_raw, const uint8_t* keep, const int32_t* idx, int n_points, int k,
                                    int32_t* raw_index, void* workspace, size_t workspace_bytes, pbn_stream_t stream) {
-    if (n_raw < 0 || n_raw > THIN_MAX_POINTS || n_points < 0 || n_points > THIN_MAX_POINTS || k < 1 || k > THIN_MAX_K)
+    if (n_raw < 0 || n_raw > SCAN_MAX_POINTS || n_points < 0 || n_points > SCAN_MAX_POINTS || k < 1 || k > SCAN_MAX_K)
         return PBN_ERR_ARG;
     if ((n_raw && (!inverse || !raw_index)) || (n_points && (!keep || !idx)) || !workspace) return PBN_ERR_ARG;
     if (workspace_bytes < raw_ws_bytes(n_points)) return PBN_ERR_WORKSPACE;

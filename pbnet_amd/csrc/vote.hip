@@ -20,32 +20,18 @@
 // Compaction.  The winners' instance ids are marked in a table over the id range by plain stores of 1, the table is
 // scanned, out_ins is renumbered in place and old_id[new] = old is written: ascending old-id order.  result[0] = status,
 // result[1] = I', one read-back.
-#include "coords_dev.h"
+#include "sort_dev.h"
 
 namespace pbn {
 namespace {
 
-typedef unsigned long long u64;
 typedef long long i64;
-constexpr int RADIX_U32 = 1 << RADIX_U32_DIGIT_BITS;
-constexpr int VOTE_MAX_POINTS = 1 << 28;           // thin.hip's THIN_MAX_POINTS
 constexpr int VOTE_MAX_CLASSES = 1023;
 constexpr int VOTE_INS_BITS = 21;
 constexpr int VOTE_INS_NONE = (1 << VOTE_INS_BITS) - 1;      // the code of an unannotated instance; ids are 0 .. 2^21 - 2
 constexpr int VOTE_IDS = 1 << VOTE_INS_BITS;       // entries of the id table (the last one is never marked)
-constexpr int VOTE_SEM_RANGE = 1, VOTE_INS_RANGE = 2, VOTE_ROW_RANGE = 4;      // status bits (8: a sort gave up)
+constexpr int VOTE_SEM_RANGE = 1, VOTE_INS_RANGE = 2, VOTE_ROW_RANGE = 4;      // status bits; the word is shared with SCAN_SORT_SPIN
 constexpr i64 VOTE_NONE = -100;                    // the reference's ignore label
-
-__device__ __forceinline__ void hist_add(unsigned (*s_hist)[RADIX_U32], unsigned key) {
-#pragma unroll
-    for (int p = 0; p < RADIX_U32_PASSES; ++p) atomicAdd(&s_hist[p][(key >> (p * RADIX_U32_DIGIT_BITS)) & (RADIX_U32 - 1)], 1u);
-}
-__device__ __forceinline__ void hist_flush(unsigned (*s_hist)[RADIX_U32], unsigned* __restrict__ ghist) {
-    for (int e = threadIdx.x; e < RADIX_U32_PASSES * RADIX_U32; e += TPB) {
-        const unsigned v = (&s_hist[0][0])[e];
-        if (v) atomicAdd(&ghist[e], v);
-    }
-}
 
 // Rows nobody votes for keep this: -100, -100, 0, 0.
 __global__ __launch_bounds__(TPB) void k_vote_fill(int m, i64* __restrict__ out_sem, i64* __restrict__ out_ins,
@@ -62,7 +48,7 @@ __global__ __launch_bounds__(TPB) void k_vote_keys(const int* __restrict__ rows,
                                                    int* __restrict__ status, u64* __restrict__ keys, int* __restrict__ vals,
                                                    unsigned* __restrict__ ghist) {
     __shared__ unsigned s_hist[RADIX_U32_PASSES][RADIX_U32];
-    for (int e = threadIdx.x; e < RADIX_U32_PASSES * RADIX_U32; e += TPB) (&s_hist[0][0])[e] = 0u;
+    hist_clear(s_hist);
     __syncthreads();
     int bad = 0;
     for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) {
@@ -88,7 +74,7 @@ __global__ __launch_bounds__(TPB) void k_vote_keys(const int* __restrict__ rows,
 __global__ __launch_bounds__(TPB) void k_vote_rows(const u64* __restrict__ skey, const int* __restrict__ srow, int n,
                                                    u64* __restrict__ keys, int* __restrict__ vals, unsigned* __restrict__ ghist) {
     __shared__ unsigned s_hist[RADIX_U32_PASSES][RADIX_U32];
-    for (int e = threadIdx.x; e < RADIX_U32_PASSES * RADIX_U32; e += TPB) (&s_hist[0][0])[e] = 0u;
+    hist_clear(s_hist);
     __syncthreads();
     for (int s = blockIdx.x * TPB + threadIdx.x; s < n; s += gridDim.x * TPB) {
         const unsigned rp = (unsigned)srow[s];
@@ -165,19 +151,14 @@ __global__ __launch_bounds__(TPB) void k_vote_renumber(i64* __restrict__ out_ins
 }
 
 struct VoteWs {
-    u64* keys_a; u64* keys_b; int* vals_a; int* vals_b; unsigned* ghist_key; unsigned* ghist_row; void* sort_scratch;
-    size_t sort_bytes; int* head; int* before; int* start; int* scan_tmp; int* table; int* newid; int* n_runs;
+    SortBufs sort;                                  // sort 0: by vote key, sort 1: by row + 1
+    int* head; int* before; int* start; int* scan_tmp; int* table; int* newid; int* n_runs;
 };
 
 VoteWs vote_carve(Carver& cv, int n) {
     VoteWs w{};
     const size_t N = (size_t)(n > 0 ? n : 1);
-    w.keys_a = cv.take<u64>(N); w.keys_b = cv.take<u64>(N);
-    w.vals_a = cv.take<int>(N); w.vals_b = cv.take<int>(N);
-    w.ghist_key = cv.take<unsigned>((size_t)RADIX_U32_PASSES * RADIX_U32);
-    w.ghist_row = cv.take<unsigned>((size_t)RADIX_U32_PASSES * RADIX_U32);
-    w.sort_bytes = radix_sort_u32_scratch_bytes((int)N);
-    w.sort_scratch = cv.take<char>(w.sort_bytes);
+    w.sort = sort_carve(cv, N, 2);
     w.head = cv.take<int>(N); w.before = cv.take<int>(N); w.start = cv.take<int>(N);
     w.scan_tmp = cv.take<int>(scan_tmp_ints((long long)(N > (size_t)VOTE_IDS ? N : (size_t)VOTE_IDS)));
     w.table = cv.take<int>(VOTE_IDS); w.newid = cv.take<int>(VOTE_IDS);
@@ -191,14 +172,12 @@ size_t vote_ws_bytes(int n) {
     return cv.off + 256;
 }
 
-int grid_for(long long n) { const long long b = (n + TPB - 1) / TPB; return (int)(b < 1 ? 1 : b > 1024 ? 1024 : b); }
-
 constexpr int VOTE_EVENTS = 7;      // around: zeroing + fill + keys | key sort | row pairs + row sort | heads + scan + starts | pick | compaction
 
 int vote_args(const int32_t* rows, const int32_t* sem, int n_raw, int m, int n_classes, const int64_t* out_sem,
               const int64_t* out_ins, const int32_t* votes, const int32_t* members, const int32_t* result, const void* workspace,
               size_t workspace_bytes) {
-    if (n_raw < 0 || n_raw > VOTE_MAX_POINTS || m < 0 || m > VOTE_MAX_POINTS || n_classes < 1 || n_classes > VOTE_MAX_CLASSES)
+    if (n_raw < 0 || n_raw > SCAN_MAX_POINTS || m < 0 || m > SCAN_MAX_POINTS || n_classes < 1 || n_classes > VOTE_MAX_CLASSES)
         return PBN_ERR_ARG;
     if ((n_raw && (!rows || !sem)) || (m && (!out_sem || !out_ins || !votes || !members)) || !result || !workspace)
         return PBN_ERR_ARG;
@@ -213,8 +192,7 @@ int vote_labels(const int32_t* rows, const int32_t* sem, const int32_t* ins, int
     const VoteWs w = vote_carve(cv, n);
     if (!cv.ok) return PBN_ERR_WORKSPACE;
     const bool sorts = n > 0 && m > 0, compact = sorts && old_id != nullptr;
-    const size_t hist_bytes = (size_t)RADIX_U32_PASSES * RADIX_U32 * sizeof(unsigned);
-    const FillRange fr[] = {{result, 2 * sizeof(int32_t), 0}, {w.ghist_key, hist_bytes, 0}, {w.ghist_row, hist_bytes, 0},
+    const FillRange fr[] = {{result, 2 * sizeof(int32_t), 0}, sort_hist_fill(w.sort, 0), sort_hist_fill(w.sort, 1),
                             {w.n_runs, sizeof(int), 0}, {w.table, (size_t)VOTE_IDS * sizeof(int), 0}};
     int at = 0;                                                              // the next event
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[at++], st));                     // the zeroing of the id table is timed too
@@ -227,28 +205,29 @@ int vote_labels(const int32_t* rows, const int32_t* sem, const int32_t* ins, int
     const dim3 grid(grid_for(n)), block(TPB);
     if (n > 0) {                                                             // m == 0: the range checks alone
         hipLaunchKernelGGL(k_vote_keys, grid, block, 0, st, rows, sem, ins, n, m, n_classes, result,
-                           sorts ? w.keys_a : (u64*)nullptr, w.vals_a, w.ghist_key);
+                           sorts ? w.sort.keys_a : (u64*)nullptr, w.sort.vals_a, w.sort.ghist[0]);
         PBN_LAUNCH_CHECK();
     }
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[at++], st));
     if (sorts) {
-        rc = radix_sort_u32(w.keys_a, w.keys_b, w.vals_a, w.vals_b, n, w.ghist_key, result, w.sort_scratch, w.sort_bytes, st);
+        rc = sort_run(w.sort, 0, n, result, st);
         if (rc != PBN_OK) return rc;
         if (ev) PBN_HIP_CHECK(hipEventRecord(ev[at++], st));
-        hipLaunchKernelGGL(k_vote_rows, grid, block, 0, st, w.keys_b, w.vals_b, n, w.keys_a, w.vals_a, w.ghist_row);
+        hipLaunchKernelGGL(k_vote_rows, grid, block, 0, st, w.sort.keys_b, w.sort.vals_b, n, w.sort.keys_a, w.sort.vals_a,
+                           w.sort.ghist[1]);
         PBN_LAUNCH_CHECK();
-        rc = radix_sort_u32(w.keys_a, w.keys_b, w.vals_a, w.vals_b, n, w.ghist_row, result, w.sort_scratch, w.sort_bytes, st);
+        rc = sort_run(w.sort, 1, n, result, st);
         if (rc != PBN_OK) return rc;
         if (ev) PBN_HIP_CHECK(hipEventRecord(ev[at++], st));
-        hipLaunchKernelGGL(k_vote_heads, grid, block, 0, st, w.keys_b, w.vals_b, n, w.head);
+        hipLaunchKernelGGL(k_vote_heads, grid, block, 0, st, w.sort.keys_b, w.sort.vals_b, n, w.head);
         PBN_LAUNCH_CHECK();
         rc = scan_exclusive_i32(w.head, w.before, n, w.scan_tmp, w.n_runs, st);
         if (rc != PBN_OK) return rc;
         hipLaunchKernelGGL(k_vote_starts, grid, block, 0, st, w.head, w.before, n, w.start);
         PBN_LAUNCH_CHECK();
         if (ev) PBN_HIP_CHECK(hipEventRecord(ev[at++], st));
-        hipLaunchKernelGGL(k_vote_pick, grid, block, 0, st, w.keys_b, w.vals_b, n, m, n_classes, w.start, w.n_runs, out_sem,
-                           out_ins, votes, members);
+        hipLaunchKernelGGL(k_vote_pick, grid, block, 0, st, w.sort.keys_b, w.sort.vals_b, n, m, n_classes, w.start, w.n_runs,
+                           out_sem, out_ins, votes, members);
         PBN_LAUNCH_CHECK();
         if (ev) PBN_HIP_CHECK(hipEventRecord(ev[at++], st));
     }
@@ -270,7 +249,7 @@ int vote_labels(const int32_t* rows, const int32_t* sem, const int32_t* ins, int
 using namespace pbn;
 
 extern "C" size_t pbn_cloud_vote_workspace_bytes(int n_raw, int m) {
-    if (n_raw < 0 || n_raw > VOTE_MAX_POINTS || m < 0 || m > VOTE_MAX_POINTS) return 0;
+    if (n_raw < 0 || n_raw > SCAN_MAX_POINTS || m < 0 || m > SCAN_MAX_POINTS) return 0;
     return vote_ws_bytes(n_raw);
 }
 
@@ -291,18 +270,8 @@ extern "C" int pbn_cloud_vote_labels_timed(const int32_t* rows, const int32_t* s
     if (rc != PBN_OK) return rc;
     if (!times_ms) return PBN_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    hipEvent_t ev[VOTE_EVENTS];
-    int made = 0;
-    hipError_t e = hipSuccess;
-    for (; made < VOTE_EVENTS && e == hipSuccess; ++made) e = hipEventCreate(&ev[made]);
-    int out = PBN_OK;
-    if (e != hipSuccess) { --made; g_last_hip_error = (int)e; out = PBN_ERR_HIP; }
-    if (out == PBN_OK)
-        out = vote_labels(rows, sem, ins, n_raw, m, n_classes, (i64*)out_sem, (i64*)out_ins, votes, members, result, (i64*)old_id,
-                          workspace, workspace_bytes, st, ev);
-    if (out == PBN_OK && (e = hipStreamSynchronize(st)) != hipSuccess) { g_last_hip_error = (int)e; out = PBN_ERR_HIP; }
-    for (int i = 0; i + 1 < VOTE_EVENTS && out == PBN_OK; ++i)
-        if ((e = hipEventElapsedTime(&times_ms[i], ev[i], ev[i + 1])) != hipSuccess) { g_last_hip_error = (int)e; out = PBN_ERR_HIP; }
-    for (int i = 0; i < made; ++i) (void)hipEventDestroy(ev[i]);
-    return out;
+    return timed_stages<VOTE_EVENTS>(st, times_ms, [&](hipEvent_t* ev) {
+        return vote_labels(rows, sem, ins, n_raw, m, n_classes, (i64*)out_sem, (i64*)out_ins, votes, members, result, (i64*)old_id,
+                           workspace, workspace_bytes, st, ev);
+    });
 }

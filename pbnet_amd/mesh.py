@@ -47,6 +47,9 @@ from . import scene_io
 
 MESH_NORMALS, MESH_SEGMENT, MESH_SEGMENT_POINT = 0, 1, 2
 STAGES = ("incidence", "normals", "weights", "sort", "read-back", "host sweep", "relabel")
+# The status bits that every stage of the scan chain shares (csrc/sort_dev.h: SCAN_NONFINITE, SCAN_EXTENT, SCAN_SORT_SPIN):
+# a coordinate is NaN or infinite; an axis spans 2^21 cells or more of thin_points' pitch; the device sort gave up.
+CLOUD_NONFINITE, CLOUD_EXTENT, CLOUD_SORT_SPIN = 1, 2, 8
 
 
 def _check_xyz(name, t):
@@ -68,6 +71,23 @@ def _workspace(mode, n_vertices, n_elems, dev):
     if nbytes == 0:
         raise ValueError("mesh too large for the library: %d vertices, %d elements" % (n_vertices, n_elems))
     return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def _scan_workspace(nbytes, dev, what):
+    """The workspace of a stage of the scan chain; 0 bytes is the library's refusal of the size."""
+    if nbytes == 0:
+        raise ValueError("point cloud too large for the library: %s" % what)
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def _staged_call(entry, args, stages, times):
+    """pbn_<entry>, or with `times` (a dict) pbn_<entry>_timed, which synchronises and adds its time per stage in ms."""
+    if times is None:
+        N.check(getattr(N.lib(), "pbn_" + entry)(*args), "pbn_" + entry)
+        return
+    t = (ctypes.c_float * len(stages))()
+    N.check(getattr(N.lib(), "pbn_%s_timed" % entry)(*args, t), "pbn_%s_timed" % entry)
+    times.update({name: float(t[i]) for i, name in enumerate(stages)})
 
 
 def _raise(rc, what):
@@ -131,7 +151,6 @@ def segment_point(vertices, normals, edges, kThresh=0.01, segMinVerts=20):
 
 # ---------------------------------------------------------------------------------------------------- point clouds
 CLOUD_STAGES = ("box", "keys + sort", "cell table", "search")
-CLOUD_NONFINITE, CLOUD_SORT_SPIN = 1, 8          # status bits of pbn_cloud_knn
 
 
 def knn_graph(xyz, k=16, cell=None, times=None):
@@ -144,11 +163,8 @@ def knn_graph(xyz, k=16, cell=None, times=None):
     lib = N.lib()
     if not 1 <= k <= lib.pbn_cloud_max_k():
         raise ValueError("knn_graph: k must lie in 1..%d, got %d" % (lib.pbn_cloud_max_k(), k))
-    nbytes = lib.pbn_cloud_workspace_bytes(n, k)
-    if nbytes == 0:
-        raise ValueError("point cloud too large for the library: %d points" % n)
     dev = xyz.device
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _scan_workspace(lib.pbn_cloud_workspace_bytes(n, k), dev, "%d points" % n)
     idx = torch.empty(n, k, dtype=torch.int32, device=dev)
     d2 = torch.empty(n, k, dtype=torch.float32, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -156,16 +172,11 @@ def knn_graph(xyz, k=16, cell=None, times=None):
     if cell is not None and not h > 0.0:
         raise ValueError("knn_graph: cell must be positive, got %r" % (cell,))
     args = (N.ptr(xyz), n, k, h, N.ptr(idx), N.ptr(d2), N.ptr(status), N.ptr(ws), ws.numel(), N.current_stream())
-    if times is None:
-        N.check(lib.pbn_cloud_knn(*args), "pbn_cloud_knn")
-    else:
-        t = (ctypes.c_float * len(CLOUD_STAGES))()
-        N.check(lib.pbn_cloud_knn_timed(*args, t), "pbn_cloud_knn_timed")
-        times.update({name: float(t[i]) for i, name in enumerate(CLOUD_STAGES)})
+    _staged_call("cloud_knn", args, CLOUD_STAGES, times)
     st = int(status.item())
     if st & CLOUD_NONFINITE:
         raise ValueError("knn_graph: a coordinate is NaN or infinite")
-    if st:
+    if st:                                                   # CLOUD_SORT_SPIN
         raise RuntimeError("knn_graph: the device sort gave up (status %d)" % st)
     return idx, d2
 
@@ -206,7 +217,6 @@ def knn_edges(idx):
 
 # ------------------------------------------------------------------------------------------------------- raw scans
 THIN_STAGES = ("box + keys", "low-word sort", "high-word keys + sort", "run heads + scan", "cells")
-CLOUD_EXTENT = 2                                 # status bit of pbn_thin_points: an axis spans 2^21 cells or more
 
 
 def thin_points(xyz, colours=None, pitch=0.02, times=None):
@@ -224,30 +234,21 @@ def thin_points(xyz, colours=None, pitch=0.02, times=None):
     n = int(xyz.shape[0])
     if rgb is not None and rgb.shape[0] != n:
         raise ValueError("thin_points: %d colours for %d points" % (rgb.shape[0], n))
-    lib = N.lib()
-    nbytes = lib.pbn_thin_workspace_bytes(n)
-    if nbytes == 0:
-        raise ValueError("point cloud too large for the library: %d points" % n)
     dev = xyz.device
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _scan_workspace(N.lib().pbn_thin_workspace_bytes(n), dev, "%d points" % n)
     out_xyz = torch.empty(n, 3, dtype=torch.float32, device=dev)
     out_rgb = torch.empty(n, 3, dtype=torch.float32, device=dev) if rgb is not None else None
     count, first, inverse = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
     result = torch.empty(2, dtype=torch.int32, device=dev)
     args = (N.ptr(xyz), N.ptr(rgb), n, pitch, N.ptr(out_xyz), N.ptr(out_rgb), N.ptr(count), N.ptr(first), N.ptr(inverse),
             N.ptr(result), N.ptr(ws), ws.numel(), N.current_stream())
-    if times is None:
-        N.check(lib.pbn_thin_points(*args), "pbn_thin_points")
-    else:
-        t = (ctypes.c_float * len(THIN_STAGES))()
-        N.check(lib.pbn_thin_points_timed(*args, t), "pbn_thin_points_timed")
-        times.update({name: float(t[i]) for i, name in enumerate(THIN_STAGES)})
+    _staged_call("thin_points", args, THIN_STAGES, times)
     st, m = (int(v) for v in result.tolist())                # the one read-back
     if st & CLOUD_NONFINITE:
         raise ValueError("thin_points: a coordinate is NaN or infinite")
     if st & CLOUD_EXTENT:
         raise ValueError("thin_points: the cloud spans 2^21 cells or more of pitch %r on an axis" % (pitch,))
-    if st:
+    if st:                                                   # CLOUD_SORT_SPIN
         raise RuntimeError("thin_points: the device sort gave up (status %d)" % st)
     out = {"xyz": out_xyz[:m], "count": count[:m], "first": first[:m], "inverse": inverse}
     if rgb is not None:
@@ -271,11 +272,8 @@ def outlier_mask(d2, ratio=2.0):
     lib = N.lib()
     if not 1 <= k <= lib.pbn_cloud_max_k():
         raise ValueError("outlier_mask: k must lie in 1..%d, got %d" % (lib.pbn_cloud_max_k(), k))
-    nbytes = lib.pbn_cloud_outlier_workspace_bytes(n)
-    if nbytes == 0:
-        raise ValueError("point cloud too large for the library: %d points" % n)
     dev = d2.device
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _scan_workspace(lib.pbn_cloud_outlier_workspace_bytes(n), dev, "%d points" % n)
     keep = torch.empty(n, dtype=torch.bool, device=dev)
     stats = torch.empty(3, dtype=torch.float64, device=dev)
     N.check(lib.pbn_cloud_outlier_mask(N.ptr(d2), n, k, ratio, N.ptr(keep), N.ptr(stats), N.ptr(ws), ws.numel(),
@@ -301,10 +299,7 @@ def raw_index(inverse, keep, idx):
     lib = N.lib()
     if not 1 <= k <= lib.pbn_cloud_max_k():
         raise ValueError("raw_index: k must lie in 1..%d, got %d" % (lib.pbn_cloud_max_k(), k))
-    nbytes = lib.pbn_cloud_raw_index_workspace_bytes(m)
-    if nbytes == 0:
-        raise ValueError("point cloud too large for the library: %d points" % m)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=inverse.device)
+    ws = _scan_workspace(lib.pbn_cloud_raw_index_workspace_bytes(m), inverse.device, "%d points" % m)
     out = torch.empty(n_raw, dtype=torch.int32, device=inverse.device)
     N.check(lib.pbn_cloud_raw_index(N.ptr(inverse), n_raw, N.ptr(keep), N.ptr(idx), m, k, N.ptr(out), N.ptr(ws), ws.numel(),
                                     N.current_stream()), "pbn_cloud_raw_index")
@@ -325,7 +320,7 @@ def carry_labels(labels, raw_index, fill=-1):
 
 
 # ------------------------------------------------------------------------------------------------- annotated scans
-VOTE_SEM_RANGE, VOTE_INS_RANGE, VOTE_ROW_RANGE = 1, 2, 4     # status bits of pbn_cloud_vote_labels (8: a sort gave up)
+VOTE_SEM_RANGE, VOTE_INS_RANGE, VOTE_ROW_RANGE = 1, 2, 4     # pbn_cloud_vote_labels' own status bits, next to CLOUD_SORT_SPIN
 VOTE_MAX_CLASSES, VOTE_MAX_INS = 1023, (1 << 21) - 1         # n_classes in 1..1023; instance ids in 0..2^21 - 2
 VOTE_STAGES = ("fill + keys", "key sort", "row pairs + row sort", "run heads + scan + starts", "pick", "compaction")
 
@@ -354,24 +349,15 @@ def vote_labels(rows, sem, ins=None, m=None, n_classes=20, compact=True, times=N
     N.require_cuda(rows, sem, ins)
     m = int(m) if m is not None else (int(rows.max().item()) + 1 if n_raw else 0)
     rows, sem, ins = rows.contiguous(), sem.contiguous(), None if ins is None else ins.contiguous()
-    lib = N.lib()
-    nbytes = lib.pbn_cloud_vote_workspace_bytes(n_raw, m)
-    if nbytes == 0:
-        raise ValueError("point cloud too large for the library: %d raw points, %d rows" % (n_raw, m))
     dev = rows.device
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _scan_workspace(N.lib().pbn_cloud_vote_workspace_bytes(n_raw, m), dev, "%d raw points, %d rows" % (n_raw, m))
     out_sem, out_ins = (torch.empty(m, dtype=torch.int64, device=dev) for _ in range(2))
     votes, members = (torch.empty(m, dtype=torch.int32, device=dev) for _ in range(2))
     old_id = torch.empty(max(1, min(m, VOTE_MAX_INS + 1)), dtype=torch.int64, device=dev) if compact else None
     result = torch.empty(2, dtype=torch.int32, device=dev)
     args = (N.ptr(rows), N.ptr(sem), N.ptr(ins), n_raw, m, n_classes, N.ptr(out_sem), N.ptr(out_ins), N.ptr(votes),
             N.ptr(members), N.ptr(result), N.ptr(old_id), N.ptr(ws), ws.numel(), N.current_stream())
-    if times is None:
-        N.check(lib.pbn_cloud_vote_labels(*args), "pbn_cloud_vote_labels")
-    else:
-        t = (ctypes.c_float * len(VOTE_STAGES))()
-        N.check(lib.pbn_cloud_vote_labels_timed(*args, t), "pbn_cloud_vote_labels_timed")
-        times.update({name: float(t[i]) for i, name in enumerate(VOTE_STAGES)})
+    _staged_call("cloud_vote_labels", args, VOTE_STAGES, times)
     st, n_ins = (int(v) for v in result.tolist())            # the one read-back
     if st & VOTE_SEM_RANGE:
         raise ValueError("vote_labels: a semantic label is %d or more" % n_classes)
@@ -379,7 +365,7 @@ def vote_labels(rows, sem, ins=None, m=None, n_classes=20, compact=True, times=N
         raise ValueError("vote_labels: an instance label is %d or more" % VOTE_MAX_INS)
     if st & VOTE_ROW_RANGE:
         raise ValueError("vote_labels: a row lies outside [-1, %d)" % m)
-    if st:
+    if st:                                                   # CLOUD_SORT_SPIN
         raise RuntimeError("vote_labels: the device sort gave up (status %d)" % st)
     return {"sem_label": out_sem, "ins_label": out_ins, "votes": votes, "members": members,
             "old_id": old_id[:n_ins] if compact else torch.empty(0, dtype=torch.int64, device=dev)}
@@ -407,6 +393,54 @@ _PLY_SCALARS = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short
                 "double": "f8", "float64": "f8"}
 
 
+def _read_ply_header(fh, path):
+    """The header of an open PLY file: (fmt, elements, body) -- the words after `format`, a list of (name, count,
+    properties) with every property as the tuple of its words, and the bytes after end_header."""
+    if fh.readline().strip() != b"ply":
+        raise ValueError("%s: not a PLY file" % path)
+    elements, fmt = [], None
+    while True:
+        line = fh.readline()
+        if not line:
+            raise ValueError("%s: no end_header" % path)
+        words = line.decode("ascii", "replace").split()
+        if not words or words[0] in ("comment", "obj_info"):
+            continue
+        if words[0] == "end_header":
+            break
+        if words[0] == "format":
+            fmt = words[1:]
+        elif words[0] == "element" and len(words) == 3:
+            elements.append((words[1], int(words[2]), []))
+        elif words[0] == "property":
+            if not elements:
+                raise ValueError("%s: property before any element" % path)
+            elements[-1][2].append(tuple(words[1:]))
+        else:
+            raise ValueError("%s: unsupported header line %r" % (path, line))
+    if fmt != ["binary_little_endian", "1.0"]:
+        raise ValueError("%s: only binary_little_endian 1.0 is supported, got %s" % (path, fmt))
+    return fmt, elements, fh.read()
+
+
+def _vertex_dtype(path, vprops):
+    """The record of a vertex under the accepted property rules."""
+    names = [p[-1] for p in vprops]
+    types = [p[0] for p in vprops]
+    if names not in (["x", "y", "z", "red", "green", "blue"], ["x", "y", "z", "red", "green", "blue", "alpha"]) or \
+            any(_PLY_SCALARS.get(t) != "f4" for t in types[:3]) or any(_PLY_SCALARS.get(t) != "u1" for t in types[3:]):
+        raise ValueError("%s: vertex properties must be float x y z + uchar red green blue [alpha], got %s" % (path, vprops))
+    return np.dtype([(n, "<f4" if i < 3 else "u1") for i, n in enumerate(names)])
+
+
+def _vertex_arrays(body, vdt, nv):
+    """xyz float32 [V, 3] and colours uint8 [V, 3] of the nv vertex records at the start of `body`."""
+    vert = np.frombuffer(body, vdt, nv, 0)
+    xyz = np.stack([vert["x"], vert["y"], vert["z"]], axis=1).astype(np.float32)
+    rgb = np.stack([vert["red"], vert["green"], vert["blue"]], axis=1).astype(np.uint8)
+    return xyz, rgb
+
+
 def read_ply(path):
     """ScanNet's `_vh_clean_2.ply`: returns (xyz float32 [V, 3], colours uint8 [V, 3], faces int64 [F, 3]).
 
@@ -414,54 +448,22 @@ def read_ply(path):
     and an optional `uchar alpha`; element face with exactly `list uchar int vertex_indices` (or `uint`), triangles only.
     Anything else raises ValueError."""
     with open(path, "rb") as fh:
-        if fh.readline().strip() != b"ply":
-            raise ValueError("%s: not a PLY file" % path)
-        elements, fmt = [], None
-        while True:
-            line = fh.readline()
-            if not line:
-                raise ValueError("%s: no end_header" % path)
-            words = line.decode("ascii", "replace").split()
-            if not words or words[0] in ("comment", "obj_info"):
-                continue
-            if words[0] == "end_header":
-                break
-            if words[0] == "format":
-                fmt = words[1:]
-            elif words[0] == "element":
-                elements.append((words[1], int(words[2]), []))
-            elif words[0] == "property":
-                if not elements:
-                    raise ValueError("%s: property before any element" % path)
-                elements[-1][2].append(tuple(words[1:]))
-            else:
-                raise ValueError("%s: unsupported header line %r" % (path, line))
-        body = fh.read()
-    if fmt != ["binary_little_endian", "1.0"]:
-        raise ValueError("%s: only binary_little_endian 1.0 is supported, got %s" % (path, fmt))
+        _, elements, body = _read_ply_header(fh, path)
     if [e[0] for e in elements] != ["vertex", "face"]:
         raise ValueError("%s: expected elements [vertex, face], got %s" % (path, [e[0] for e in elements]))
     (_, nv, vprops), (_, nf, fprops) = elements
-    names = [p[-1] for p in vprops]
-    types = [p[0] for p in vprops]
-    if names not in (["x", "y", "z", "red", "green", "blue"], ["x", "y", "z", "red", "green", "blue", "alpha"]) or \
-            any(_PLY_SCALARS.get(t) != "f4" for t in types[:3]) or any(_PLY_SCALARS.get(t) != "u1" for t in types[3:]):
-        raise ValueError("%s: vertex properties must be float x y z + uchar red green blue [alpha], got %s" % (path, vprops))
+    vdt = _vertex_dtype(path, vprops)
     if len(fprops) != 1 or fprops[0][0] != "list" or fprops[0][-1] != "vertex_indices" or \
             _PLY_SCALARS.get(fprops[0][1]) != "u1" or _PLY_SCALARS.get(fprops[0][2]) not in ("i4", "u4"):
         raise ValueError("%s: face must be `list uchar int|uint vertex_indices`, got %s" % (path, fprops))
-    vdt = np.dtype([(n, "<f4" if i < 3 else "u1") for i, n in enumerate(names)])
     fdt = np.dtype([("n", "u1"), ("i", "<" + _PLY_SCALARS[fprops[0][2]], (3,))])
     need = nv * vdt.itemsize + nf * fdt.itemsize
     if len(body) < need:
         raise ValueError("%s: truncated body (%d bytes, need %d for triangles)" % (path, len(body), need))
-    vert = np.frombuffer(body, vdt, nv, 0)
     face = np.frombuffer(body, fdt, nf, nv * vdt.itemsize)
     if nf and not np.all(face["n"] == 3):
         raise ValueError("%s: only triangle faces are supported" % path)
-    xyz = np.stack([vert["x"], vert["y"], vert["z"]], axis=1).astype(np.float32)
-    rgb = np.stack([vert["red"], vert["green"], vert["blue"]], axis=1).astype(np.uint8)
-    return xyz, rgb, face["i"].astype(np.int64).reshape(-1, 3)
+    return _vertex_arrays(body, vdt, nv) + (face["i"].astype(np.int64).reshape(-1, 3),)
 
 
 def read_ply_points(path):
@@ -471,44 +473,14 @@ def read_ply_points(path):
     z`, `uchar red, green, blue`, an optional `uchar alpha`).  Anything else raises ValueError; a file with faces is a mesh
     and belongs to read_ply."""
     with open(path, "rb") as fh:
-        if fh.readline().strip() != b"ply":
-            raise ValueError("%s: not a PLY file" % path)
-        elements, fmt = [], None
-        while True:
-            line = fh.readline()
-            if not line:
-                raise ValueError("%s: no end_header" % path)
-            words = line.decode("ascii", "replace").split()
-            if not words or words[0] in ("comment", "obj_info"):
-                continue
-            if words[0] == "end_header":
-                break
-            if words[0] == "format":
-                fmt = words[1:]
-            elif words[0] == "element" and len(words) == 3:
-                elements.append((words[1], int(words[2]), []))
-            elif words[0] == "property" and elements:
-                elements[-1][2].append(tuple(words[1:]))
-            else:
-                raise ValueError("%s: unsupported header line %r" % (path, line))
-        body = fh.read()
-    if fmt != ["binary_little_endian", "1.0"]:
-        raise ValueError("%s: only binary_little_endian 1.0 is supported, got %s" % (path, fmt))
+        _, elements, body = _read_ply_header(fh, path)
     if [e[0] for e in elements] != ["vertex"]:
         raise ValueError("%s: expected the vertex element only, got %s" % (path, [e[0] for e in elements]))
     _, nv, vprops = elements[0]
-    names = [p[-1] for p in vprops]
-    types = [p[0] for p in vprops]
-    if names not in (["x", "y", "z", "red", "green", "blue"], ["x", "y", "z", "red", "green", "blue", "alpha"]) or \
-            any(_PLY_SCALARS.get(t) != "f4" for t in types[:3]) or any(_PLY_SCALARS.get(t) != "u1" for t in types[3:]):
-        raise ValueError("%s: vertex properties must be float x y z + uchar red green blue [alpha], got %s" % (path, vprops))
-    vdt = np.dtype([(n, "<f4" if i < 3 else "u1") for i, n in enumerate(names)])
+    vdt = _vertex_dtype(path, vprops)
     if nv < 0 or len(body) < nv * vdt.itemsize:
         raise ValueError("%s: truncated body (%d bytes, need %d)" % (path, len(body), nv * vdt.itemsize))
-    vert = np.frombuffer(body, vdt, nv, 0)
-    xyz = np.stack([vert["x"], vert["y"], vert["z"]], axis=1).astype(np.float32)
-    rgb = np.stack([vert["red"], vert["green"], vert["blue"]], axis=1).astype(np.uint8)
-    return xyz, rgb
+    return _vertex_arrays(body, vdt, nv)
 
 
 def write_ply(path, xyz, colours, faces, index_type="int", alpha=True):

@@ -85,6 +85,21 @@ def test_two_runs_give_the_same_bytes():
     assert torch.equal(n1.view(torch.int32), n2.view(torch.int32))
 
 
+@pytest.mark.parametrize("name,k", [("n0", 6), ("n2", 1), ("n65", 6)])
+def test_timed_entry_gives_the_plain_bytes_and_four_stage_times(name, k):
+    """pbn_cloud_knn_timed against pbn_cloud_knn.  n2 at k = 1 is the smallest designed cloud whose automatic grid has
+    more than one cell (1 x 3 x 1: h = sqrt(area * k / 2n) is below the y extent); n65 at k = 6 has 2 x 2 x 3 cells and
+    more than one wave; n0 takes the entry's short form, which still records every event."""
+    x = torch.from_numpy(C.CASES[name][0]).to(DEV)
+    plain = mesh.knn_graph(x, k=k)
+    times = {}
+    timed = mesh.knn_graph(x, k=k, times=times)
+    _same(tuple(t.cpu().numpy() for t in timed), tuple(t.cpu().numpy() for t in plain))
+    _same(tuple(t.cpu().numpy() for t in timed), _want(name, k))
+    assert tuple(times) == mesh.CLOUD_STAGES and len(times) == 4
+    assert all(np.isfinite(v) and v >= 0.0 for v in times.values()), times
+
+
 def test_non_finite_coordinates_raise():
     for bad in (np.nan, np.inf, -np.inf):
         pts = C.CASES["n257"][0].copy()
