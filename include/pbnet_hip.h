@@ -1118,6 +1118,36 @@ int pbn_cloud_raw_index(const int32_t* inverse, int n_raw, const uint8_t* keep, 
                         int32_t* raw_index, void* workspace, size_t workspace_bytes, pbn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Fixed-radius queries (csrc/cloud.hip): the neighbour count behind radius outlier removal, and the way back from the kept
+ * points to the raw ones without a kNN graph.  pbn_cloud_knn's grid front and d2; rf = `radius` (float32, finite and > 0),
+ * r2 = fl(rf * rf); j is a neighbour of i when j != i and d2(i,j) <= r2 (coincident points are neighbours at 0; an r2 that
+ * underflows to 0 counts only those).  cell > 0 is the grid's cell size, anything else a hair above the radius; the result
+ * never depends on it.  status int32[1] (device): 0, or bit 1 when a coordinate is not finite and bit 8 when the sort gave
+ * up; no row is written then.  Argument checks run on the host before any launch (sizes in 0..2^28, radius, cap >= 1,
+ * pointers: PBN_ERR_ARG); only the _timed entry synchronises.  No atomics besides the front's: two runs, the same bytes;
+ * tests/radius_ref.py restates each output in numpy.
+ * ------------------------------------------------------------------------------------------------------------ */
+/* bytes of workspace for pbn_cloud_radius_count; 0 = n_points out of range */
+size_t pbn_cloud_radius_workspace_bytes(int n_points);
+/* count int32[n], in the caller's point order: min(number of neighbours, cap), cap in 1..2^31 - 1; a query stops scanning
+ * at cap.  n_points == 0 launches nothing; one point counts 0. */
+int pbn_cloud_radius_count(const float* xyz, int n_points, float radius, int cap, float cell, int32_t* count, int32_t* status,
+                           void* workspace, size_t workspace_bytes, pbn_stream_t stream);
+/* Measurement variant: HIP events around the stages, SYNCHRONISES; times_ms (host float[4]): box + grid, keys + sort,
+ * cell table, count. */
+int pbn_cloud_radius_count_timed(const float* xyz, int n_points, float radius, int cap, float cell, int32_t* count,
+                                 int32_t* status, void* workspace, size_t workspace_bytes, pbn_stream_t stream, float* times_ms);
+/* bytes of workspace for pbn_cloud_radius_raw_index; 0 = n_points or n_raw out of range */
+size_t pbn_cloud_radius_raw_index_workspace_bytes(int n_points, int n_raw);
+/* raw_index int32[n_raw]: with t = inverse[i] (a row of the n_points points xyz and keep speak of) and rank = the exclusive
+ * scan of keep (uint8 0 / 1): rank[t] when keep[t]; else rank[j] of the KEPT point j with the smallest key (bits of
+ * d2(t,j), j) among those with d2(t,j) <= r2 -- a dropped point is never an answer; else -1 (also for t outside
+ * [0, n_points)). */
+int pbn_cloud_radius_raw_index(const float* xyz, int n_points, const uint8_t* keep, float radius, float cell,
+                               const int32_t* inverse, int n_raw, int32_t* raw_index, int32_t* status, void* workspace,
+                               size_t workspace_bytes, pbn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Annotated raw scans (csrc/vote.hip): the raw points' labels voted down to the kept points.  Integers only: two runs
  * give the same bytes, and tests/vote_ref.py restates the contract in numpy.  Argument checks run on the host before any
  * launch (n_classes in 1..1023, n_raw and m in 0..2^28, else PBN_ERR_ARG); nothing synchronises.

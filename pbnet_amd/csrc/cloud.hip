@@ -44,6 +44,18 @@
 // Normals: one lane per point, float64, no atomics.  S = the point, then its valid neighbours in rank order; mean, then
 // the six covariance sums, in that order; the eigenvector of the smallest eigenvalue by a FIXED number of cyclic Jacobi
 // sweeps (no data-dependent loop); flipped towards the viewpoint; rounded to float32.  |S| < 3 gives the zero vector.
+//
+// Fixed radius (pbn_cloud_radius_count / pbn_cloud_radius_raw_index): the same grid front (cloud_front below, which
+// pbn_cloud_knn runs too) with a cell a hair above the radius, and the same shell walk without a k-th neighbour.
+// rf = the caller's float32 radius, r2 = fl(rf * rf), j is a neighbour of i when j != i and d2(i, j) <= r2.  By the
+// argument above every unscanned point has a computed d2 >= bound2, so a query stops when bound2 is STRICTLY above r2
+// (an unscanned point exactly at r2 is a neighbour), when the block covers the grid, or when it has what it came for:
+//   count   count[i] = min(neighbours, cap), in a register; the lane stops at cap;
+//   route   for a dropped point the kept point with the smallest (d2 bits, j) within r2, one 64-bit key in registers; it
+//           also stops once its best d2 is strictly below bound2, as a search for k = 1 would.  Kept lanes write their own
+//           rank at once.  keep is read in SORTED order (k_radius_sorted_keep gathers it once through the order), so a
+//           candidate's flag lies next to its neighbours' like the candidate itself.
+// Neither has LDS, a per-lane array or an atomic.
 #include <cmath>
 
 #include "sort_dev.h"
@@ -195,6 +207,35 @@ __device__ __forceinline__ float face_bound2(double gap, double inv) {
     return f * f;
 }
 
+// Cell and t() of a query, as the walks below hold them.
+struct CloudQuery {
+    int cx, cy, cz, d0, d1, d2;
+    double tx, ty, tz, inv;
+};
+
+__device__ __forceinline__ CloudQuery cloud_query(const float4 q, unsigned key, const CloudGrid* __restrict__ g) {
+    CloudQuery c;
+    c.cx = (int)(key & 1023u); c.cy = (int)((key >> 10) & 1023u); c.cz = (int)(key >> 20);
+    c.d0 = g->dim[0]; c.d1 = g->dim[1]; c.d2 = g->dim[2];
+    c.inv = g->inv;
+    c.tx = cloud_t((double)q.x, g->mn[0], c.inv); c.ty = cloud_t((double)q.y, g->mn[1], c.inv);
+    c.tz = cloud_t((double)q.z, g->mn[2], c.inv);
+    return c;
+}
+
+// bound2 of the block of shells 0..r (see the header): the smallest over its faces inside the grid; false when it has none
+__device__ __forceinline__ bool block_bound2(const CloudQuery& c, int r, float& bound2) {
+    bound2 = __uint_as_float(0x7f800000u);
+    bool inner = false;                                                      // does the block have a face inside the grid?
+    if (c.cx - r > 0) { inner = true; bound2 = fminf(bound2, face_bound2(c.tx - (double)(c.cx - r), c.inv)); }
+    if (c.cy - r > 0) { inner = true; bound2 = fminf(bound2, face_bound2(c.ty - (double)(c.cy - r), c.inv)); }
+    if (c.cz - r > 0) { inner = true; bound2 = fminf(bound2, face_bound2(c.tz - (double)(c.cz - r), c.inv)); }
+    if (c.cx + r < c.d0 - 1) { inner = true; bound2 = fminf(bound2, face_bound2((double)(c.cx + r + 1) - c.tx, c.inv)); }
+    if (c.cy + r < c.d1 - 1) { inner = true; bound2 = fminf(bound2, face_bound2((double)(c.cy + r + 1) - c.ty, c.inv)); }
+    if (c.cz + r < c.d2 - 1) { inner = true; bound2 = fminf(bound2, face_bound2((double)(c.cz + r + 1) - c.tz, c.inv)); }
+    return inner;
+}
+
 __global__ __launch_bounds__(TPB) void k_cloud_search(const float4* __restrict__ pts, const u64* __restrict__ keys,
                                                       const int2* __restrict__ table, const CloudGrid* __restrict__ g,
                                                       const int* __restrict__ status, int n, int k,
@@ -210,12 +251,8 @@ __global__ __launch_bounds__(TPB) void k_cloud_search(const float4* __restrict__
 
     const float4 q = pts[t];
     const int qi = __float_as_int(q.w);
-    const unsigned key = (unsigned)keys[t];
-    const int cx = (int)(key & 1023u), cy = (int)((key >> 10) & 1023u), cz = (int)(key >> 20);
-    const int d0 = g->dim[0], d1 = g->dim[1], d2 = g->dim[2];
-    const double inv = g->inv;
-    const double tx = cloud_t((double)q.x, g->mn[0], inv), ty = cloud_t((double)q.y, g->mn[1], inv),
-                 tz = cloud_t((double)q.z, g->mn[2], inv);
+    const CloudQuery c0 = cloud_query(q, (unsigned)keys[t], g);
+    const int cx = c0.cx, cy = c0.cy, cz = c0.cz, d0 = c0.d0, d1 = c0.d1, d2 = c0.d2;
 
     for (int r = 0; r < CLOUD_AXIS_CELLS; ++r) {
         const int xlo = max(cx - r, 0), xhi = min(cx + r, d0 - 1);
@@ -251,21 +288,112 @@ __global__ __launch_bounds__(TPB) void k_cloud_search(const float4* __restrict__
                 }
             }
         }
-        float bound2 = __uint_as_float(0x7f800000u);
-        bool inner = false;                                                  // does the block have a face inside the grid?
-        if (cx - r > 0) { inner = true; bound2 = fminf(bound2, face_bound2(tx - (double)(cx - r), inv)); }
-        if (cy - r > 0) { inner = true; bound2 = fminf(bound2, face_bound2(ty - (double)(cy - r), inv)); }
-        if (cz - r > 0) { inner = true; bound2 = fminf(bound2, face_bound2(tz - (double)(cz - r), inv)); }
-        if (cx + r < d0 - 1) { inner = true; bound2 = fminf(bound2, face_bound2((double)(cx + r + 1) - tx, inv)); }
-        if (cy + r < d1 - 1) { inner = true; bound2 = fminf(bound2, face_bound2((double)(cy + r + 1) - ty, inv)); }
-        if (cz + r < d2 - 1) { inner = true; bound2 = fminf(bound2, face_bound2((double)(cz + r + 1) - tz, inv)); }
-        if (!inner) break;                                                   // the block covers the grid
+        float bound2;
+        if (!block_bound2(c0, r, bound2)) break;                             // the block covers the grid
         if (__uint_as_float((unsigned)(worst >> 32)) < bound2) break;
     }
     for (int r = 0; r < k; ++r) {
         const u64 b = best[r * TPB];
         idx[(size_t)qi * k + r] = (int)(unsigned)b;
         d2_out[(size_t)qi * k + r] = __uint_as_float((unsigned)(b >> 32));
+    }
+}
+
+// ---- fixed radius ------------------------------------------------------------------------------------------------------
+// k_cloud_search's walk for a fixed radius.  visit(i, pts[i]) sees every point of the scanned cells, the query included,
+// and returns false once the lane needs no more; after each shell the walk ends when the block covers the grid, when
+// bound2 > r2, or when enough(bound2) says so.
+template <typename Visit, typename Enough>
+__device__ __forceinline__ void radius_walk(const float4* __restrict__ pts, const int2* __restrict__ table,
+                                            const CloudQuery& c, float r2, Visit visit, Enough enough) {
+    const int cx = c.cx, cy = c.cy, cz = c.cz;
+    bool more = true;
+    for (int r = 0; r < CLOUD_AXIS_CELLS; ++r) {
+        const int xlo = max(cx - r, 0), xhi = min(cx + r, c.d0 - 1);
+        const int ylo = max(cy - r, 0), yhi = min(cy + r, c.d1 - 1);
+        const int zlo = max(cz - r, 0), zhi = min(cz + r, c.d2 - 1);
+        for (int z = zlo; z <= zhi && more; ++z) {
+            for (int y = ylo; y <= yhi && more; ++y) {
+                // a row on the shell's y / z faces is scanned whole, an inner row only at its two ends
+                const bool full = (z - cz == r) || (cz - z == r) || (y - cy == r) || (cy - y == r);
+                int x = full ? xlo : (cx - r >= 0 ? cx - r : cx + r);
+                while (x <= xhi && more) {
+                    const int2 se = table[(size_t)(z * c.d1 + y) * c.d0 + x];
+                    for (int i = se.x; i < se.y && more; ++i) more = visit(i, pts[i]);
+                    x = full ? x + 1 : (x < cx + r ? cx + r : xhi + 1);
+                }
+            }
+        }
+        float bound2;
+        if (!more || !block_bound2(c, r, bound2) || bound2 > r2 || enough(bound2)) break;
+    }
+}
+
+// One lane per query in sorted order; count[query] = min(points j != query with d2 <= r2, cap).
+__global__ __launch_bounds__(TPB) void k_radius_count(const float4* __restrict__ pts, const u64* __restrict__ keys,
+                                                      const int2* __restrict__ table, const CloudGrid* __restrict__ g,
+                                                      const int* __restrict__ status, int n, float r2, int cap,
+                                                      int* __restrict__ count) {
+    if (*status != 0) return;                                                // non-finite input or a failed sort: no row is written
+    const int t = blockIdx.x * TPB + threadIdx.x;
+    if (t >= n) return;
+    const float4 q = pts[t];
+    const int qi = __float_as_int(q.w);
+    int cnt = 0;
+    radius_walk(pts, table, cloud_query(q, (unsigned)keys[t], g), r2,
+                [&](int, const float4 c) {
+                    const float dx = c.x - q.x, dy = c.y - q.y, dz = c.z - q.z;
+                    const float dd = (dx * dx + dy * dy) + dz * dz;
+                    cnt += (int)(__float_as_int(c.w) != qi && dd <= r2);     // self goes by index, not by distance
+                    return cnt < cap;
+                },
+                [](float) { return false; });
+    count[qi] = cnt;
+}
+
+// keep in sorted order for the walk, and as the 0 / 1 ints the scan takes
+__global__ __launch_bounds__(TPB) void k_radius_sorted_keep(const float4* __restrict__ pts, const unsigned char* __restrict__ keep,
+                                                            const int* __restrict__ status, int n,
+                                                            unsigned char* __restrict__ skeep, int* __restrict__ flag) {
+    if (*status != 0) return;                                                // pts is not trusted
+    for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) {
+        skeep[i] = keep[__float_as_int(pts[i].w)] ? 1 : 0;
+        flag[i] = keep[i] ? 1 : 0;
+    }
+}
+
+// One lane per point in sorted order; route[point] = its rank when kept, else the rank of the kept point with the smallest
+// (d2 bits, index) among those with d2 <= r2, else -1.  rank[] is the exclusive scan of keep in the caller's order.
+__global__ __launch_bounds__(TPB) void k_radius_route(const float4* __restrict__ pts, const u64* __restrict__ keys,
+                                                      const int2* __restrict__ table, const CloudGrid* __restrict__ g,
+                                                      const int* __restrict__ status, int n, float r2,
+                                                      const unsigned char* __restrict__ skeep, const int* __restrict__ rank,
+                                                      int* __restrict__ route) {
+    if (*status != 0) return;
+    const int t = blockIdx.x * TPB + threadIdx.x;
+    if (t >= n) return;
+    const float4 q = pts[t];
+    const int qi = __float_as_int(q.w);
+    if (skeep[t]) { route[qi] = rank[qi]; return; }
+    u64 best = CLOUD_PAD_KEY;
+    radius_walk(pts, table, cloud_query(q, (unsigned)keys[t], g), r2,
+                [&](int i, const float4 c) {
+                    const float dx = c.x - q.x, dy = c.y - q.y, dz = c.z - q.z;
+                    const float dd = (dx * dx + dy * dy) + dz * dz;
+                    const u64 ck = ((u64)__float_as_uint(dd) << 32) | (unsigned)__float_as_int(c.w);
+                    if (skeep[i] && dd <= r2 && ck < best) best = ck;        // the query itself is dropped: never a candidate
+                    return true;
+                },
+                [&](float bound2) { return __uint_as_float((unsigned)(best >> 32)) < bound2; });
+    route[qi] = best == CLOUD_PAD_KEY ? -1 : rank[(int)(unsigned)best];
+}
+
+__global__ __launch_bounds__(TPB) void k_radius_gather(const int* __restrict__ inverse, int n_raw, const int* __restrict__ route,
+                                                       int n, const int* __restrict__ status, int* __restrict__ out) {
+    if (*status != 0) return;                                                // no row is written
+    for (int i = blockIdx.x * TPB + threadIdx.x; i < n_raw; i += gridDim.x * TPB) {
+        const int t = inverse[i];
+        out[i] = (unsigned)t < (unsigned)n ? route[t] : -1;
     }
 }
 
@@ -367,12 +495,12 @@ size_t ws_bytes(int n) {
 
 bool bad_sizes(int n, int k) { return n < 0 || n > SCAN_MAX_POINTS || k < 1 || k > SCAN_MAX_K; }
 
-// ev (optional): CLOUD_EVENTS events
-int cloud_knn(const float* xyz, int n, int k, float cell, int32_t* idx, float* d2, int32_t* status, void* workspace,
-              size_t workspace_bytes, hipStream_t st, hipEvent_t* ev) {
-    Carver cv(workspace, workspace_bytes);
-    const CloudWs w = carve(cv, n);
-    if (!cv.ok) return PBN_ERR_WORKSPACE;
+// The grid front of every search in this file: status zeroed, then box -> grid -> keys -> sort -> table, after which
+// w.pts, w.sort.keys_b, w.table and w.grid describe the cloud.  `k` only feeds the automatic cell size (cell <= 0).
+// ev (optional): ev[0..3] are recorded around box + grid | keys + sort | table; ev[4..n_events) are the caller's, and with
+// n == 0 (status zeroed, nothing else launched) they are recorded here too.
+int cloud_front(const float* xyz, int n, int k, float cell, int32_t* status, const CloudWs& w, hipStream_t st, hipEvent_t* ev,
+                int n_events) {
     const FillRange fr[] = {{status, sizeof(int32_t), 0}, {w.box, 3 * sizeof(unsigned), 0xff},
                             {w.box + 3, 3 * sizeof(unsigned), 0}, sort_hist_fill(w.sort, 0),
                             {w.table, 2 * (size_t)w.t_cap * sizeof(int), 0}};
@@ -380,7 +508,7 @@ int cloud_knn(const float* xyz, int n, int k, float cell, int32_t* idx, float* d
     if (rc != PBN_OK) return rc;
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[0], st));
     if (n == 0) {
-        if (ev) for (int i = 1; i < CLOUD_EVENTS; ++i) PBN_HIP_CHECK(hipEventRecord(ev[i], st));
+        if (ev) for (int i = 1; i < n_events; ++i) PBN_HIP_CHECK(hipEventRecord(ev[i], st));
         return PBN_OK;
     }
     hipLaunchKernelGGL(k_cloud_box, dim3(grid_for(n)), dim3(TPB), 0, st, xyz, n, w.box, status);
@@ -395,6 +523,17 @@ int cloud_knn(const float* xyz, int n, int k, float cell, int32_t* idx, float* d
     hipLaunchKernelGGL(k_cloud_table, dim3(grid_for(n)), dim3(TPB), 0, st, w.sort.keys_b, w.sort.vals_b, n, xyz, w.grid, w.t_cap,
                        w.table, w.pts);
     if (ev) PBN_HIP_CHECK(hipEventRecord(ev[3], st));
+    return PBN_OK;
+}
+
+// ev (optional): CLOUD_EVENTS events
+int cloud_knn(const float* xyz, int n, int k, float cell, int32_t* idx, float* d2, int32_t* status, void* workspace,
+              size_t workspace_bytes, hipStream_t st, hipEvent_t* ev) {
+    Carver cv(workspace, workspace_bytes);
+    const CloudWs w = carve(cv, n);
+    if (!cv.ok) return PBN_ERR_WORKSPACE;
+    const int rc = cloud_front(xyz, n, k, cell, status, w, st, ev, CLOUD_EVENTS);
+    if (rc != PBN_OK || n == 0) return rc;
     const size_t lds = (size_t)k * TPB * sizeof(u64);
     static const bool lds_attr = (hipFuncSetAttribute((const void*)k_cloud_search, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                       (int)(SCAN_MAX_K * TPB * sizeof(u64))) == hipSuccess);
@@ -411,6 +550,60 @@ int knn_args(const float* xyz, int n, int k, const int32_t* idx, const float* d2
     if (bad_sizes(n, k)) return PBN_ERR_ARG;
     if ((n && (!xyz || !idx || !d2)) || !status || !workspace) return PBN_ERR_ARG;
     if (workspace_bytes < ws_bytes(n)) return PBN_ERR_WORKSPACE;
+    return PBN_OK;
+}
+
+// ---- fixed radius: host ------------------------------------------------------------------------------------------------
+constexpr int RADIUS_EVENTS = 5;                  // around: box + grid | keys + sort | table | count
+constexpr float RADIUS_CELL_SCALE = 1.0f + 1.0f / 1024.0f;   // the automatic cell: a hair above the radius
+
+struct RadiusWs {
+    CloudWs cloud; unsigned char* skeep; int* flag; int* rank; int* scan_tmp; int* route;     // the five: the routing alone
+};
+
+RadiusWs radius_carve(Carver& cv, int n, bool routing) {
+    RadiusWs w{};
+    w.cloud = carve(cv, n);
+    if (!routing) return w;
+    const size_t N = (size_t)(n > 0 ? n : 1);
+    w.skeep = cv.take<unsigned char>(N);
+    w.flag = cv.take<int>(N); w.rank = cv.take<int>(N);
+    w.scan_tmp = cv.take<int>(scan_tmp_ints((long long)N));
+    w.route = cv.take<int>(N);
+    return w;
+}
+
+size_t radius_ws_bytes(int n, bool routing) {
+    Carver cv(nullptr, 0);
+    radius_carve(cv, n, routing);
+    return cv.off + 256;
+}
+
+bool bad_points(int n) { return n < 0 || n > SCAN_MAX_POINTS; }
+bool bad_radius(float radius) { return !(radius > 0.0f) || !std::isfinite(radius); }
+// the cell handed to k_cloud_grid, which enlarges it until the grid fits: never the result, only the speed
+float radius_cell(float radius, float cell) { return cell > 0.0f ? cell : radius * RADIUS_CELL_SCALE; }
+
+// ev (optional): RADIUS_EVENTS events
+int radius_count(const float* xyz, int n, float radius, int cap, float cell, int32_t* count, int32_t* status, void* workspace,
+                 size_t workspace_bytes, hipStream_t st, hipEvent_t* ev) {
+    Carver cv(workspace, workspace_bytes);
+    const CloudWs w = radius_carve(cv, n, false).cloud;
+    if (!cv.ok) return PBN_ERR_WORKSPACE;
+    const int rc = cloud_front(xyz, n, 1, radius_cell(radius, cell), status, w, st, ev, RADIUS_EVENTS);
+    if (rc != PBN_OK || n == 0) return rc;
+    hipLaunchKernelGGL(k_radius_count, dim3((unsigned)cdiv(n, TPB)), dim3(TPB), 0, st, w.pts, w.sort.keys_b,
+                       reinterpret_cast<const int2*>(w.table), w.grid, status, n, radius * radius, cap, count);
+    if (ev) PBN_HIP_CHECK(hipEventRecord(ev[4], st));
+    PBN_LAUNCH_CHECK();
+    return PBN_OK;
+}
+
+int radius_count_args(const float* xyz, int n, float radius, int cap, const int32_t* count, const int32_t* status,
+                      const void* workspace, size_t workspace_bytes) {
+    if (bad_points(n) || bad_radius(radius) || cap < 1) return PBN_ERR_ARG;
+    if ((n && (!xyz || !count)) || !status || !workspace) return PBN_ERR_ARG;
+    if (workspace_bytes < radius_ws_bytes(n, false)) return PBN_ERR_WORKSPACE;
     return PBN_OK;
 }
 
@@ -458,6 +651,64 @@ extern "C" int pbn_cloud_normals(const float* xyz, int n_points, const int32_t* 
     if (n_points == 0) return PBN_OK;
     hipLaunchKernelGGL(k_cloud_normals, dim3(grid_for(n_points)), dim3(TPB), 0, (hipStream_t)stream, xyz, n_points, idx, k,
                        viewpoint, nl);
+    PBN_LAUNCH_CHECK();
+    return PBN_OK;
+}
+
+extern "C" size_t pbn_cloud_radius_workspace_bytes(int n_points) {
+    if (bad_points(n_points)) return 0;
+    return radius_ws_bytes(n_points, false);
+}
+
+extern "C" int pbn_cloud_radius_count(const float* xyz, int n_points, float radius, int cap, float cell, int32_t* count,
+                                      int32_t* status, void* workspace, size_t workspace_bytes, pbn_stream_t stream) {
+    const int rc = radius_count_args(xyz, n_points, radius, cap, count, status, workspace, workspace_bytes);
+    if (rc != PBN_OK) return rc;
+    return radius_count(xyz, n_points, radius, cap, cell, count, status, workspace, workspace_bytes, (hipStream_t)stream, nullptr);
+}
+
+extern "C" int pbn_cloud_radius_count_timed(const float* xyz, int n_points, float radius, int cap, float cell, int32_t* count,
+                                            int32_t* status, void* workspace, size_t workspace_bytes, pbn_stream_t stream,
+                                            float* times_ms) {
+    const int rc = radius_count_args(xyz, n_points, radius, cap, count, status, workspace, workspace_bytes);
+    if (rc != PBN_OK) return rc;
+    if (!times_ms) return PBN_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    return timed_stages<RADIUS_EVENTS>(st, times_ms, [&](hipEvent_t* ev) {
+        return radius_count(xyz, n_points, radius, cap, cell, count, status, workspace, workspace_bytes, st, ev);
+    });
+}
+
+extern "C" size_t pbn_cloud_radius_raw_index_workspace_bytes(int n_points, int n_raw) {
+    if (bad_points(n_points) || bad_points(n_raw)) return 0;
+    return radius_ws_bytes(n_points, true);
+}
+
+extern "C" int pbn_cloud_radius_raw_index(const float* xyz, int n_points, const uint8_t* keep, float radius, float cell,
+                                          const int32_t* inverse, int n_raw, int32_t* raw_index, int32_t* status,
+                                          void* workspace, size_t workspace_bytes, pbn_stream_t stream) {
+    const int n = n_points;
+    if (bad_points(n) || bad_points(n_raw) || bad_radius(radius)) return PBN_ERR_ARG;
+    if ((n && (!xyz || !keep)) || (n_raw && (!inverse || !raw_index)) || !status || !workspace) return PBN_ERR_ARG;
+    if (workspace_bytes < radius_ws_bytes(n, true)) return PBN_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    Carver cv(workspace, workspace_bytes);
+    const RadiusWs w = radius_carve(cv, n, true);
+    if (!cv.ok) return PBN_ERR_WORKSPACE;
+    if (n_raw == 0 || n == 0) {                                              // nothing to route, or nobody to route to
+        const FillRange fr[] = {{status, sizeof(int32_t), 0}, {raw_index, (size_t)n_raw * sizeof(int32_t), 0xff}};
+        return fill_ranges(fr, n_raw > 0 ? 2 : 1, st);
+    }
+    int rc = cloud_front(xyz, n, 1, radius_cell(radius, cell), status, w.cloud, st, nullptr, 0);
+    if (rc != PBN_OK) return rc;
+    const int2* table = reinterpret_cast<const int2*>(w.cloud.table);
+    hipLaunchKernelGGL(k_radius_sorted_keep, dim3(grid_for(n)), dim3(TPB), 0, st, w.cloud.pts, keep, status, n, w.skeep, w.flag);
+    PBN_LAUNCH_CHECK();
+    rc = scan_exclusive_i32(w.flag, w.rank, n, w.scan_tmp, nullptr, st);
+    if (rc != PBN_OK) return rc;
+    hipLaunchKernelGGL(k_radius_route, dim3((unsigned)cdiv(n, TPB)), dim3(TPB), 0, st, w.cloud.pts, w.cloud.sort.keys_b, table,
+                       w.cloud.grid, status, n, radius * radius, w.skeep, w.rank, w.route);
+    hipLaunchKernelGGL(k_radius_gather, dim3(grid_for(n_raw)), dim3(TPB), 0, st, inverse, n_raw, w.route, n, status, raw_index);
     PBN_LAUNCH_CHECK();
     return PBN_OK;
 }

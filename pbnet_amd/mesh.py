@@ -19,6 +19,8 @@ Raw sensor scans (csrc/thin.hip): to the network's pitch and back.
 thin_points      one float64 centroid per occupied cell of a grid, bit for bit tests/thin_ref.py
 outlier_mask     statistical outlier removal over knn_graph's d2, sums of a fixed shape
 raw_index        for every raw point its row among the kept points (itself, or its first kept neighbour)
+radius_count     how many other points lie within a radius of each point (csrc/cloud.hip), bit for bit tests/radius_ref.py
+radius_outlier_mask, radius_raw_index   the radius filter on top of it and its raw_index: no kNN graph
 carry_labels     per-point results of the kept points gathered back to the raw ones
 vote_labels      the other direction (csrc/vote.hip): an annotated raw scan's (semantic, instance) pairs voted down to the
                  kept points, surviving instance ids renumbered densely; bit for bit tests/vote_ref.py
@@ -306,6 +308,91 @@ def raw_index(inverse, keep, idx):
     return out
 
 
+RADIUS_STAGES = ("box", "keys + sort", "cell table", "count")
+RADIUS_MAX_CAP = (1 << 31) - 1
+
+
+def _radius_args(what, xyz, radius, cell):
+    """The checks the fixed-radius functions share, values and dtypes before the device: (xyz, float32 radius, cell)."""
+    with np.errstate(over="ignore"):
+        rf = np.float32(radius)
+    if not (np.isfinite(rf) and rf > 0):
+        raise ValueError("%s: radius must be positive and finite as a float32, got %r" % (what, radius))
+    h = 0.0 if cell is None else float(cell)
+    if cell is not None and not h > 0.0:
+        raise ValueError("%s: cell must be positive, got %r" % (what, cell))
+    if not torch.is_tensor(xyz) or xyz.dtype != torch.float32 or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise TypeError("xyz must be a float32 [n, 3] tensor, got %s" % (
+            "%s %s" % (xyz.dtype, tuple(xyz.shape)) if torch.is_tensor(xyz) else type(xyz).__name__))
+    return float(rf), h
+
+
+def _scan_status(what, status):
+    st = int(status.item())                                  # the one read-back
+    if st & CLOUD_NONFINITE:
+        raise ValueError("%s: a coordinate is NaN or infinite" % what)
+    if st:                                                   # CLOUD_SORT_SPIN
+        raise RuntimeError("%s: the device sort gave up (status %d)" % (what, st))
+
+
+def radius_count(xyz, radius, cap=None, cell=None, times=None):
+    """The number of other points within `radius` of every point (csrc/cloud.hip): count int32 [N] on the device, in the
+    caller's point order.  rf = float32(radius), r2 = rf * rf in float32; j counts for i when j != i and knn_graph's
+    d2(i, j) <= r2, so coincident points count at 0.  count = min(neighbours, cap): `cap` is an int in 1..2^31 - 1 (None =
+    2^31 - 1) at which a query stops looking.  `cell` (the grid's cell size; None = a hair above the radius) changes the
+    speed, never the result.  One read-back (the status); a non-finite coordinate raises ValueError.  `times` (a dict)
+    takes the stage times of the measurement entry, which synchronises."""
+    rf, h = _radius_args("radius_count", xyz, radius, cell)
+    cap = RADIUS_MAX_CAP if cap is None else cap
+    if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 1 <= int(cap) <= RADIUS_MAX_CAP:
+        raise ValueError("radius_count: cap must be an int in 1..2^31 - 1, got %r" % (cap,))
+    xyz = _check_xyz("xyz", xyz)
+    n, dev = int(xyz.shape[0]), xyz.device
+    ws = _scan_workspace(N.lib().pbn_cloud_radius_workspace_bytes(n), dev, "%d points" % n)
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    args = (N.ptr(xyz), n, rf, int(cap), h, N.ptr(count), N.ptr(status), N.ptr(ws), ws.numel(), N.current_stream())
+    _staged_call("cloud_radius_count", args, RADIUS_STAGES, times)
+    _scan_status("radius_count", status)
+    return count
+
+
+def radius_outlier_mask(xyz, radius, min_pts, cell=None):
+    """Radius outlier removal (PCL's RadiusOutlierRemoval, Open3D's remove_radius_outlier): keep bool [N] on the device,
+    keep[i] = at least `min_pts` (>= 1) other points lie within `radius` of point i.  It is
+    radius_count(xyz, radius, cap=min_pts) >= min_pts: the count stops at min_pts, and the comparison is a torch
+    expression on the device."""
+    if isinstance(min_pts, bool) or not isinstance(min_pts, (int, np.integer)) or not 1 <= int(min_pts) <= RADIUS_MAX_CAP:
+        raise ValueError("radius_outlier_mask: min_pts must be an int in 1..2^31 - 1, got %r" % (min_pts,))
+    return radius_count(xyz, radius, cap=int(min_pts), cell=cell) >= int(min_pts)
+
+
+def radius_raw_index(inverse, keep, xyz, radius, cell=None):
+    """raw_index without a kNN graph: int32 [N_raw] on the device.  With t = inverse[i]: t's row among the kept points (the
+    exclusive scan of keep) when keep[t]; else the row of the KEPT point j with the smallest (bits of d2(t, j), j) among
+    those with d2(t, j) <= r2 (radius_count's d2 and r2) -- a dropped point is never an answer, however near; else -1.
+    `inverse` int32 [N_raw] (thin_points), `keep` bool [M] (radius_outlier_mask), `xyz` f32 [M, 3] (the same M points).
+    One read-back (the status)."""
+    rf, h = _radius_args("radius_raw_index", xyz, radius, cell)
+    if not torch.is_tensor(inverse) or inverse.dtype != torch.int32 or inverse.dim() != 1:
+        raise TypeError("inverse must be an int32 [n] tensor, got %s %s" % (inverse.dtype, tuple(inverse.shape)))
+    m = int(xyz.shape[0])
+    if not torch.is_tensor(keep) or keep.dtype != torch.bool or keep.dim() != 1 or keep.shape[0] != m:
+        raise TypeError("keep must be a bool [%d] tensor, got %s %s" % (m, keep.dtype, tuple(keep.shape)))
+    N.require_cuda(inverse, keep, xyz)
+    inverse, keep, xyz = inverse.contiguous(), keep.contiguous(), xyz.contiguous()
+    n_raw, dev = int(inverse.shape[0]), inverse.device
+    ws = _scan_workspace(N.lib().pbn_cloud_radius_raw_index_workspace_bytes(m, n_raw), dev,
+                         "%d points, %d raw points" % (m, n_raw))
+    out = torch.empty(n_raw, dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    N.check(N.lib().pbn_cloud_radius_raw_index(N.ptr(xyz), m, N.ptr(keep), rf, h, N.ptr(inverse), n_raw, N.ptr(out),
+                                               N.ptr(status), N.ptr(ws), ws.numel(), N.current_stream()),
+            "pbn_cloud_radius_raw_index")
+    _scan_status("radius_raw_index", status)
+    return out
+
+
 def carry_labels(labels, raw_index, fill=-1):
     """The gather that goes with raw_index: out[i] = labels[raw_index[i]], `fill` where raw_index[i] is -1.  `labels` is
     any integer tensor whose first axis is the kept points; the result has raw_index's length on that axis."""
@@ -541,10 +628,12 @@ def decode_mesh(src, device="cuda", kThresh=0.01, segMinVerts=20):
             "face": face_d, "sup": sup}
 
 
-def _kept_points(xyz, colours, dev, k, pitch, outlier_ratio):
-    """decode_points' front for a raw scan: upload, thin_points (pitch), knn_graph -> outlier_mask -> compact
-    (outlier_ratio).  Returns the kept points' (xyz, colours) as host float32 arrays -- centre_and_scale is a host numpy
-    expression, so the kept M x 6 floats make one extra round trip -- and raw_index / count on the device."""
+def _kept_points(xyz, colours, dev, k, pitch, outlier_ratio, outlier_radius=None, outlier_min_pts=None):
+    """decode_points' front for a raw scan: upload, thin_points (pitch), then knn_graph -> outlier_mask -> raw_index
+    (outlier_ratio) or radius_outlier_mask -> radius_raw_index (outlier_radius, outlier_min_pts: no graph over the
+    unfiltered points), and the compaction.  Returns the kept points' (xyz, colours) as host float32 arrays --
+    centre_and_scale is a host numpy expression, so the kept M x 6 floats make one extra round trip -- and raw_index /
+    count on the device."""
     xyz_d = torch.from_numpy(np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)).to(dev)
     col_d = torch.from_numpy(np.ascontiguousarray(colours, np.float32).reshape(-1, 3)).to(dev)
     n_raw = int(xyz_d.shape[0])
@@ -559,11 +648,16 @@ def _kept_points(xyz, colours, dev, k, pitch, outlier_ratio):
         keep, _ = outlier_mask(d2, outlier_ratio)
         inverse = raw_index(inverse, keep, idx)
         xyz_d, col_d, count = xyz_d[keep], col_d[keep], count[keep]
+    elif outlier_radius is not None:
+        keep = radius_outlier_mask(xyz_d, outlier_radius, outlier_min_pts)
+        inverse = radius_raw_index(inverse, keep, xyz_d, outlier_radius)
+        xyz_d, col_d, count = xyz_d[keep], col_d[keep], count[keep]
     return xyz_d.cpu().numpy(), col_d.cpu().numpy(), inverse, count
 
 
 def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpoint=None, return_graph=False, pitch=None,
-                  outlier_ratio=None, return_kept=False, sem_label=None, ins_label=None, n_classes=20):
+                  outlier_ratio=None, return_kept=False, sem_label=None, ins_label=None, n_classes=20, outlier_radius=None,
+                  outlier_min_pts=None):
     """decode_mesh for a scan without faces: `src` is a vertex-only `.ply` path or (xyz [V,3], colours [V,3] 0..255).
     centre_and_scale -> knn_graph -> point_normals -> knn_edges -> segment_point.  Returns xyz (mean-centred), rgb, nl and
     sup on `device` -- what SceneCache and save_decoded take (no `face`) -- plus idx and d2 when return_graph is set.
@@ -575,6 +669,11 @@ def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpo
     points exactly as if they had been given as `src`.  The result gains raw_index (int32 [V]: for every raw point its row
     among the kept points, -1 = none; see raw_index and carry_labels) and count (int32: raw points behind each kept one),
     and with return_kept also kept_xyz / kept_rgb, the kept points before centring and scaling.
+
+    `outlier_radius` and `outlier_min_pts` (both or neither, and not together with `outlier_ratio`) are the other standard
+    filter, for flying pixels: a point is kept when at least outlier_min_pts other points lie within outlier_radius
+    (radius_outlier_mask), and a dropped point is spoken for by its nearest KEPT point within that radius
+    (radius_raw_index).  No kNN graph is built over the unfiltered points; everything behind the front is the same.
 
     An annotated scan: `sem_label` and `ins_label` (both or neither; one per raw point; integer arrays or tensors, or the
     float64 arrays the reference's `.npy` files hold; negative = unannotated) are voted down to the kept points over the
@@ -588,6 +687,10 @@ def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpo
         xyz, colours = (t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t) for t in src)
     if (sem_label is None) != (ins_label is None):
         raise ValueError("decode_points: give both sem_label and ins_label, or neither")
+    if (outlier_radius is None) != (outlier_min_pts is None):
+        raise ValueError("decode_points: give both outlier_radius and outlier_min_pts, or neither")
+    if outlier_radius is not None and outlier_ratio is not None:
+        raise ValueError("decode_points: outlier_radius / outlier_min_pts and outlier_ratio are two filters, give one")
     dev = torch.device(device)
     labels = None
     if sem_label is not None:
@@ -595,10 +698,10 @@ def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpo
         labels = [_raw_labels(name, v, n_raw) for name, v in (("sem_label", sem_label), ("ins_label", ins_label))]
         labels = [torch.from_numpy(a).to(dev) for a in labels]
     raw = None
-    if pitch is not None or outlier_ratio is not None:
-        xyz, colours, *raw = _kept_points(xyz, colours, dev, k, pitch, outlier_ratio)
+    if pitch is not None or outlier_ratio is not None or outlier_radius is not None:
+        xyz, colours, *raw = _kept_points(xyz, colours, dev, k, pitch, outlier_ratio, outlier_radius, outlier_min_pts)
     elif return_kept:
-        raise ValueError("decode_points: return_kept needs pitch or outlier_ratio")
+        raise ValueError("decode_points: return_kept needs pitch, outlier_ratio or outlier_radius")
     xyz_c, rgb = centre_and_scale(xyz, colours)
     xyz_d = torch.from_numpy(np.ascontiguousarray(xyz_c, np.float32)).to(dev)
     idx, d2 = knn_graph(xyz_d, k=k)
