@@ -1148,6 +1148,39 @@ int pbn_cloud_radius_raw_index(const float* xyz, int n_points, const uint8_t* ke
                                size_t workspace_bytes, pbn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Normal orientation (csrc/orient.hip): the signs of a cloud's normals made consistent over its kNN graph, by propagation
+ * along the minimum spanning forest under the weight 1 - |n_i . n_j| (Hoppe et al. 1992).  tests/orient_ref.py restates
+ * this contract in numpy with a sequential Kruskal.
+ *   Sizes    nl float32[n,3], idx int32[n,k], 1 <= k <= pbn_cloud_max_k(), n >= 0, n * k <= 2^31 - 1; else PBN_ERR_ARG.
+ *   Null     a point is null when a component of its normal is not finite or all three are +-0.  It has no edges, its row
+ *            is copied unchanged, it is never flipped, and it is a tree of its own.
+ *   Edges    slot e = i * k + r is an edge between i and j = idx[i,r] when 0 <= j < n, j != i and neither end is null; any
+ *            other j is no neighbour.  The graph is undirected: slots i->j and j->i are two edges, equal weight, two ids.
+ *   Key      d_e = (nx_i*nx_j + ny_i*ny_j) + nz_i*nz_j in float32, every operation rounded; w_e = 1.0f - fabsf(d_e);
+ *            f_e = d_e < 0.0f; key_e = (u64(order_key(w_e)) << 32) | e, order_key the order-preserving bits of a float32
+ *            with NaN last and -0 tied with +0 (pbn_mesh_segment's edge order).  Keys are distinct: the order is strict.
+ *   Forest   F = the minimum spanning forest under ascending key (Kruskal's).  It is unique, so nothing below depends on
+ *            how it is found.
+ *   Signs    within a tree s_i in {0,1} with s_a ^ s_b = f_e for every edge of F, which fixes s up to one flip per tree:
+ *            of the two, the one with more points at s_i = 0; on a tie the one that keeps the tree's lowest-index point.
+ *   Outputs  nl_out float32[n,3]: the input row with the sign bit of all three components inverted where s_i = 1;
+ *            flipped uint8[n] = s_i; tree int32[n] = the lowest point index of i's tree; stats int32[4] = trees among
+ *            the non-null points, flipped points, null points, 0.
+ *   Status   int32[2] (device): [0] is 0, or bit 16 when a link chain did not end within n hops (an internal error: no
+ *            output is to be trusted); [1] = the rounds that merged something.
+ * Integer atomics only: two runs give the same bytes.  n_points == 0 is valid.  Argument checks run on the host before any
+ * launch; only the _timed entry synchronises.
+ * ------------------------------------------------------------------------------------------------------------ */
+/* bytes of workspace for pbn_cloud_orient; 0 = sizes out of range */
+size_t pbn_cloud_orient_workspace_bytes(int n_points, int k);
+int pbn_cloud_orient(const float* nl, int n_points, const int32_t* idx, int k, float* nl_out, uint8_t* flipped, int32_t* tree,
+                     int32_t* stats, int32_t* status, void* workspace, size_t workspace_bytes, pbn_stream_t stream);
+/* Measurement variant: HIP events around the stages, SYNCHRONISES; times_ms (host float[3]): edge codes, rounds, tail. */
+int pbn_cloud_orient_timed(const float* nl, int n_points, const int32_t* idx, int k, float* nl_out, uint8_t* flipped,
+                           int32_t* tree, int32_t* stats, int32_t* status, void* workspace, size_t workspace_bytes,
+                           pbn_stream_t stream, float* times_ms);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Annotated raw scans (csrc/vote.hip): the raw points' labels voted down to the kept points.  Integers only: two runs
  * give the same bytes, and tests/vote_ref.py restates the contract in numpy.  Argument checks run on the host before any
  * launch (n_classes in 1..1023, n_raw and m in 0..2^28, else PBN_ERR_ARG); nothing synchronises.

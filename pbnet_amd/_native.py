@@ -313,6 +313,10 @@ SIGNATURES = {
     "pbn_cloud_radius_raw_index_workspace_bytes": (c_size, [c_int, c_int]),
     "pbn_cloud_radius_raw_index": (c_int, [c_f32p, c_int, c_vp, c_float, c_float, c_i32p, c_int, c_i32p, c_i32p, c_vp, c_size,
                                            c_vp]),
+    "pbn_cloud_orient_workspace_bytes": (c_size, [c_int, c_int]),
+    "pbn_cloud_orient": (c_int, [c_f32p, c_int, c_i32p, c_int, c_f32p, c_vp, c_i32p, c_i32p, c_i32p, c_vp, c_size, c_vp]),
+    "pbn_cloud_orient_timed": (c_int, [c_f32p, c_int, c_i32p, c_int, c_f32p, c_vp, c_i32p, c_i32p, c_i32p, c_vp, c_size, c_vp,
+                                       ctypes.POINTER(ctypes.c_float)]),
     "pbn_cloud_vote_workspace_bytes": (c_size, [c_int, c_int]),
     "pbn_cloud_vote_labels": (c_int, [c_i32p, c_i32p, c_i32p, c_int, c_int, c_int, c_vp, c_vp, c_i32p, c_i32p, c_i32p, c_vp, c_vp,
                                       c_size, c_vp]),

@@ -1,4 +1,4 @@
-// sort_dev.h -- what the stages of the scan-decode chain (mesh.hip, cloud.hip, thin.hip, vote.hip) share around
+// sort_dev.h -- what the stages of the scan-decode chain (mesh.hip, cloud.hip, thin.hip, vote.hip, orient.hip) share around
 // radix_sort_u32: the digit histograms its caller fills, the buffers of a sort, the launch grid, the chain's limits and
 // status bits, and the stage timing of the *_timed entry points.  Integer helpers and host code only: nothing here depends
 // on a translation unit's -ffp-contract setting.
@@ -18,6 +18,7 @@ enum : int {
     SCAN_NONFINITE = 1,                           // k_cloud_box: a coordinate is NaN or infinite
     SCAN_EXTENT = 2,                              // k_thin_keys: an axis spans 2^21 cells or more
     SCAN_SORT_SPIN = 8,                           // radix_sort_u32: a chained scan gave up
+    SCAN_WALK_CAP = 16,                           // k_orient_jump: a link chain did not end within n hops
 };
 
 // blocks of a striding grid over n items: at least one, at most cap

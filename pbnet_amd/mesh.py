@@ -12,6 +12,7 @@ Scans without a mesh (csrc/cloud.hip): segment_point's normals and edges from th
 knn_graph        the exact k nearest neighbours over a uniform grid, bit for bit a float32 brute force
 point_normals    float64 PCA normals over each point and its neighbours, turned towards a viewpoint
 knn_edges        the graph as segment_point's E x 2 edges
+orient_normals   point_normals' signs made consistent over the graph (csrc/orient.hip), bit for bit tests/orient_ref.py
 read_ply_points  the vertex-only counterpart of read_ply
 decode_points    decode_mesh without faces: xyz, rgb, nl, sup
 
@@ -215,6 +216,55 @@ def knn_edges(idx):
     dst = idx.reshape(-1).to(torch.int64)
     keep = dst >= 0
     return torch.stack([src[keep], dst[keep]], dim=1)
+
+
+ORIENT_STAGES = ("edge codes", "rounds", "tail")
+CLOUD_WALK_CAP = 16                                          # csrc/sort_dev.h: SCAN_WALK_CAP
+CLOUD_MAX_K = 32                                             # csrc/sort_dev.h: SCAN_MAX_K = pbn_cloud_max_k(), known without the library
+
+
+def orient_normals(nl, idx, times=None):
+    """Consistent signs for a cloud's normals (csrc/orient.hip; Hoppe et al. 1992, PCL / Open3D's
+    orient_normals_consistent_tangent_plane).  `nl` f32 [N, 3] (point_normals), `idx` int32 [N, k] (knn_graph, -1 or
+    anything outside [0, N) = no neighbour).  Slot e = i * k + r is an edge (i, idx[i, r]) of weight 1 - |n_i . n_j| in
+    float32 and key (order bits of the weight, e); the signs are propagated along the minimum spanning forest under that
+    key -- unique, because the keys are distinct -- with s_a ^ s_b = (n_a . n_b < 0) on its edges.  Per tree the assignment
+    that keeps more input signs wins, and on a tie the one that keeps the tree's lowest-index point.  A point whose normal
+    is zero or not finite is null: no edges, never flipped, a tree of its own.
+
+    Returns a dict on the device: nl f32 [N, 3] (rows negated exactly where flipped), flipped bool [N], tree int32 [N]
+    (the lowest point index of the point's tree), stats int32 [4] (trees among the non-null points, flipped points, null
+    points, 0) and rounds (int: the Boruvka rounds that merged something).  One read-back (status and rounds); integer
+    atomics only, so two runs give the same bytes.  `times` (a dict) takes the stage times of the measurement entry, which
+    synchronises."""
+    if not torch.is_tensor(nl) or nl.dtype != torch.float32 or nl.dim() != 2 or nl.shape[1] != 3:
+        raise TypeError("nl must be a float32 [n, 3] tensor, got %s" % (
+            "%s %s" % (nl.dtype, tuple(nl.shape)) if torch.is_tensor(nl) else type(nl).__name__))
+    n = int(nl.shape[0])
+    if not torch.is_tensor(idx) or idx.dtype != torch.int32 or idx.dim() != 2 or idx.shape[0] != n:
+        raise TypeError("idx must be an int32 [%d, k] tensor, got %s" % (
+            n, "%s %s" % (idx.dtype, tuple(idx.shape)) if torch.is_tensor(idx) else type(idx).__name__))
+    k = int(idx.shape[1])
+    if not 1 <= k <= CLOUD_MAX_K:
+        raise ValueError("orient_normals: k must lie in 1..%d, got %d" % (CLOUD_MAX_K, k))
+    if n * k > (1 << 31) - 1:
+        raise ValueError("orient_normals: %d points x %d neighbours exceed 2^31 - 1 edge slots" % (n, k))
+    N.require_cuda(nl, idx)
+    nl, idx = nl.contiguous(), idx.contiguous()
+    dev = nl.device
+    ws = _scan_workspace(N.lib().pbn_cloud_orient_workspace_bytes(n, k), dev, "%d points, k = %d" % (n, k))
+    out = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    flipped = torch.empty(n, dtype=torch.bool, device=dev)
+    tree = torch.empty(n, dtype=torch.int32, device=dev)
+    stats = torch.empty(4, dtype=torch.int32, device=dev)
+    status = torch.zeros(2, dtype=torch.int32, device=dev)
+    args = (N.ptr(nl), n, N.ptr(idx), k, N.ptr(out), N.ptr(flipped), N.ptr(tree), N.ptr(stats), N.ptr(status), N.ptr(ws),
+            ws.numel(), N.current_stream())
+    _staged_call("cloud_orient", args, ORIENT_STAGES, times)
+    st, rounds = (int(v) for v in status.tolist())           # the one read-back
+    if st:                                                   # CLOUD_WALK_CAP
+        raise RuntimeError("orient_normals: a link chain did not end (status %d)" % st)
+    return {"nl": out, "flipped": flipped, "tree": tree, "stats": stats, "rounds": rounds}
 
 
 # ------------------------------------------------------------------------------------------------------- raw scans
@@ -657,11 +707,16 @@ def _kept_points(xyz, colours, dev, k, pitch, outlier_ratio, outlier_radius=None
 
 def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpoint=None, return_graph=False, pitch=None,
                   outlier_ratio=None, return_kept=False, sem_label=None, ins_label=None, n_classes=20, outlier_radius=None,
-                  outlier_min_pts=None):
+                  outlier_min_pts=None, orient=None):
     """decode_mesh for a scan without faces: `src` is a vertex-only `.ply` path or (xyz [V,3], colours [V,3] 0..255).
     centre_and_scale -> knn_graph -> point_normals -> knn_edges -> segment_point.  Returns xyz (mean-centred), rgb, nl and
     sup on `device` -- what SceneCache and save_decoded take (no `face`) -- plus idx and d2 when return_graph is set.
     `viewpoint` is given in the centred frame; None is the cloud's mean.
+
+    `orient="graph"` makes the normals' signs consistent over the kNN graph before the segmentation (orient_normals between
+    point_normals and segment_point): towards one viewpoint, a surface seen edge-on gets its signs from noise, and
+    segment_point cuts between two neighbours of opposite sign.  The result gains flipped (bool) and tree (int32).  None
+    leaves the normals as point_normals gives them; any other value raises ValueError.
 
     A raw sensor scan (uneven density, flying pixels) is brought to the network's pitch first: with `pitch` the points are
     thinned to one centroid per cell (thin_points), with `outlier_ratio` the points whose mean neighbour distance exceeds
@@ -685,6 +740,8 @@ def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpo
         xyz, colours = read_ply_points(src)
     else:
         xyz, colours = (t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t) for t in src)
+    if orient is not None and orient != "graph":
+        raise ValueError("decode_points: orient must be None or \"graph\", got %r" % (orient,))
     if (sem_label is None) != (ins_label is None):
         raise ValueError("decode_points: give both sem_label and ins_label, or neither")
     if (outlier_radius is None) != (outlier_min_pts is None):
@@ -706,8 +763,13 @@ def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpo
     xyz_d = torch.from_numpy(np.ascontiguousarray(xyz_c, np.float32)).to(dev)
     idx, d2 = knn_graph(xyz_d, k=k)
     nl = point_normals(xyz_d, idx, viewpoint)
+    oriented = orient_normals(nl, idx) if orient is not None else None
+    if oriented is not None:
+        nl = oriented["nl"]
     sup = segment_point(xyz_d, nl, knn_edges(idx), kThresh, segMinVerts)
     out = {"xyz": xyz_d, "rgb": torch.from_numpy(np.ascontiguousarray(rgb, np.float32)).to(dev), "nl": nl, "sup": sup}
+    if oriented is not None:
+        out.update(flipped=oriented["flipped"], tree=oriented["tree"])
     if return_graph:
         out.update(idx=idx, d2=d2)
     if raw is not None:
@@ -724,14 +786,14 @@ def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpo
     return out
 
 
-SCENE_BOOKKEEPING = ("votes", "members", "ins_old_id", "raw_index", "count")       # of a decode, not of a scene on disk
+SCENE_BOOKKEEPING = ("votes", "members", "ins_old_id", "raw_index", "count", "flipped", "tree")   # of a decode, not of a scene on disk
 
 
 def save_decoded(npy_dir, scene, decoded, sem_label=None, ins_label=None):
     """Write a decode_mesh result under the reference's names (`<scene>_xyz.npy` ...).  Without labels (a test-split scene
     or a user's own room) only xyz, rgb, nl, face and sup are written, as decode_scannet.py f_test does.  A decode_points
     result that carries its own sem_label / ins_label (an annotated scan) is written with them when none are passed; the
-    bookkeeping arrays of a raw scan (votes, members, ins_old_id, raw_index, count) are never scene files."""
+    bookkeeping arrays of a raw scan (votes, members, ins_old_id, raw_index, count, flipped, tree) are never scene files."""
     arrays = {k: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in decoded.items()
               if k not in SCENE_BOOKKEEPING}
     if (sem_label is None) != (ins_label is None):
