@@ -1307,6 +1307,35 @@ int pbn_optim_sgd(const void* table, int n_chunks, float lr, float momentum, flo
  * one wave, lane j owns term j; k in [0, 1024]. */
 int pbn_loss_meter_update(const float* terms, const double* weights, double* acc, int k, pbn_stream_t stream);
 
+/* ---- Self-test entry points ------------------------------------------------------------------------------------------------
+ * The device primitives every stage starts from -- the range fill, the two exclusive scans, the 32-bit radix sort -- called
+ * on their own, exactly as the stages call them, so that tests/test_prims_gpu.py can pin them at their tile edges.  No
+ * product path uses these.  All are asynchronous on `stream`; argument checks run on the host before any launch
+ * (PBN_ERR_ARG: a negative or oversized n, a missing pointer; PBN_ERR_WORKSPACE: a workspace that is too small).
+ *
+ * pbn_selftest_workspace_bytes  what = 0 the three-launch scan, 1 the chained scan, 2 the sort; n elements in 0..2^28.  Host
+ *                               only; 0 for a bad argument.
+ * pbn_selftest_sort_tile        keys per workgroup of a digit pass of the sort in this build.  Host only.
+ * pbn_selftest_fill             ONE fill_ranges call over n_ranges (0..64) ranges base + offset[i], bytes[i], value[i]; the
+ *                               three arrays are on the host; offset -1 is a null pointer.  The caller keeps the ranges inside
+ *                               its buffer.
+ * pbn_selftest_scan             out[i] = in[0] + .. + in[i-1] (int32), *total = the sum when total is not null.  chained = 0:
+ *                               the three-launch form; 1: the one-launch form, whose state words and *total this entry zeroes
+ *                               first and which ORs 16 into *status (required, cleared by the caller) when a workgroup gives
+ *                               up waiting.  in may alias out, total may be out + n; both are passed through as given.
+ * pbn_selftest_sort_u32         stable sort of n (key, value) pairs by key: keys_out[i] = the i-th key in ascending order as a
+ *                               64-bit word, vals_out[i] its value; ties keep the input order.  ORs 8 into *status (cleared by
+ *                               the caller) when a workgroup gives up waiting.  Only the histogram is zeroed here: a second
+ *                               call into a used workspace must give the same bytes. */
+size_t pbn_selftest_workspace_bytes(int what, int n);
+int pbn_selftest_sort_tile(void);
+int pbn_selftest_fill(uint8_t* base, const int64_t* offset, const int64_t* bytes, const uint8_t* value, int n_ranges,
+                      pbn_stream_t stream);
+int pbn_selftest_scan(const int32_t* in, int32_t* out, int n, int chained, int32_t* total, int32_t* status, void* ws,
+                      size_t ws_bytes, pbn_stream_t stream);
+int pbn_selftest_sort_u32(const uint32_t* keys, const int32_t* vals, int n, uint64_t* keys_out, int32_t* vals_out,
+                          int32_t* status, void* ws, size_t ws_bytes, pbn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -335,6 +335,11 @@ SIGNATURES = {
                                c_int, c_vp]),
     "pbn_optim_sgd": (c_int, [c_vp, c_int, c_float, c_float, c_float, c_int, c_vp]),
     "pbn_loss_meter_update": (c_int, [c_f32p, c_vp, c_vp, c_int, c_vp]),
+    "pbn_selftest_workspace_bytes": (c_size, [c_int, c_int]),
+    "pbn_selftest_sort_tile": (c_int, []),
+    "pbn_selftest_fill": (c_int, [c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_uint8), c_int, c_vp]),
+    "pbn_selftest_scan": (c_int, [c_i32p, c_i32p, c_int, c_int, c_i32p, c_i32p, c_vp, c_size, c_vp]),
+    "pbn_selftest_sort_u32": (c_int, [c_vp, c_i32p, c_int, c_vp, c_i32p, c_i32p, c_vp, c_size, c_vp]),
 }
 
 PBN_OK, PBN_ERR_ARG, PBN_ERR_WORKSPACE, PBN_ERR_HIP, PBN_ERR_RANGE, PBN_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5

@@ -170,7 +170,7 @@ int fill_ranges(const FillRange* ranges, int n, hipStream_t stream) {
 // flag << 32 | value (flag 1: the workgroup's own sum, 2: the inclusive prefix over workgroups 0..b) + a ticket word, all
 // ZEROED by the caller before the launch; every word is written by ONE agent-scope atomic store (payload and flag share the
 // 8-byte granule: no fences), read by agent-scope atomic loads, 64 predecessors per poll (lane j looks at workgroup p - j);
-// polls are bounded: a scan that gives up raises *status bit 16 instead of spinning.
+// polls are bounded: a scan that gives up raises SCAN_CHAIN_SPIN in *status instead of spinning.
 __global__ __launch_bounds__(SCAN_THREADS) void k_scan_chained(const int* in, int* out, int n, unsigned long long* state,
                                                                int* ticket, int* __restrict__ total, int* __restrict__ status) {
     __shared__ int wtot[SCAN_THREADS / 64];
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_chained(const int* in, in
             ex += wave_reduce_add((lane < upto && pp >= 0) ? (int)(unsigned)w : 0);
             if (stop) break;
             if (upto == 0) {
-                if (++spins > (1u << 24)) { if (lane == 0 && status) atomicOr(status, 16); break; }
+                if (++spins > (1u << 24)) { if (lane == 0 && status) atomicOr(status, SCAN_CHAIN_SPIN); break; }
                 __builtin_amdgcn_s_sleep(1);
             }
             p -= upto;

@@ -77,7 +77,8 @@ __device__ __forceinline__ uint32_t hash64(uint64_t k) {
     return (uint32_t)k;
 }
 
-// ---- device-wide exclusive scan (int32), three launches; tmp must hold cdiv(n, SCAN_TILE)+1 ints -------------
+// ---- device-wide exclusive scan (int32), three launches; tmp must hold scan_tmp_ints(n) = cdiv(n, SCAN_TILE) + 2 ints:
+// one sum per tile, then sums[nb] = the total (k_scan_sums writes it), then one spare -------------------------------------
 constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = 8;
 constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;  // 2048 elements per block
@@ -86,7 +87,11 @@ static inline size_t scan_tmp_ints(long long n) { return (size_t)cdiv(n, SCAN_TI
 
 // out[i] = sum_{j<i} in[j] for i in [0,n); if total != nullptr, *total = sum of all.  in may alias out.
 int scan_exclusive_i32(const int* in, int* out, int n, int* tmp, int* total, hipStream_t stream);
-// the same in ONE launch (chained scan over the workgroups); state: scan_chained_state_words(n) 64-bit words zeroed by the caller
+// the same in ONE launch (chained scan over the workgroups); state: scan_chained_state_words(n) 64-bit words zeroed by the caller.
+// A workgroup that gives up waiting for its predecessors ORs SCAN_CHAIN_SPIN into *status (status may be null).  The callers
+// are grouping's scans (cluster.hip), so the bit lives in grouping's status word next to its own bits 1, 2 and 4; it is not
+// sort_dev.h's SCAN_WALK_CAP, which has the same value in the scan-decode stages' word.
+constexpr int SCAN_CHAIN_SPIN = 16;
 size_t scan_chained_state_words(long long n);
 int scan_exclusive_i32_chained(const int* in, int* out, int n, unsigned long long* state_zeroed, int* total, int* status,
                                hipStream_t stream);
@@ -138,6 +143,7 @@ int coords_prepare_sorted(const int32_t* coords, const int32_t* n_dev, int n, in
 // *status.  sort_dev.h holds that name and what the callers share: histogram helpers, SortBufs, sort_run.
 constexpr int RADIX_U32_DIGIT_BITS = 11, RADIX_U32_PASSES = 3;
 size_t radix_sort_u32_scratch_bytes(int n);
+int radix_sort_u32_tile();                         // keys per workgroup of a digit pass (SORT_TILE of this build)
 int radix_sort_u32(unsigned long long* keys_a, unsigned long long* keys_b, int32_t* vals_a, int32_t* vals_b, int n,
                    const unsigned* ghist, int32_t* status, void* scratch, size_t scratch_bytes, hipStream_t stream);
 // cloud.hip: k_cloud_box for thin.hip -- box[0..2] / box[3..5] = minimum / maximum per axis as order-preserving u32 keys

@@ -795,6 +795,8 @@ int coords_prepare_sorted(const int32_t* coords, const int32_t* n_dev, int n, in
 
 static_assert(RADIX_U32_DIGIT_BITS == RADIX_BITS, "radix_sort_u32 runs sort_pass_body<8>: 11-bit digits");
 
+int radix_sort_u32_tile() { return SORT_TILE; }
+
 size_t radix_sort_u32_scratch_bytes(int n) {
     const size_t sort_blocks = (size_t)cdiv(n > 0 ? n : 1, SORT_TILE);
     return align_up(PL_WORDS * sizeof(int), 256) + align_up((size_t)RADIX_U32_PASSES * sort_blocks * (RADIX / 2) * sizeof(u64), 256);
