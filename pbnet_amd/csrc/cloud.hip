@@ -58,7 +58,7 @@
 // Neither has LDS, a per-lane array or an atomic.
 #include <cmath>
 
-#include "sort_dev.h"
+#include "scan_dev.h"
 
 namespace pbn {
 namespace {
@@ -158,7 +158,7 @@ __global__ void k_cloud_grid(const unsigned* __restrict__ box, const int* __rest
 __global__ __launch_bounds__(TPB) void k_cloud_keys(const float* __restrict__ xyz, int n, const CloudGrid* __restrict__ g,
                                                     u64* __restrict__ keys, int* __restrict__ vals,
                                                     unsigned* __restrict__ ghist) {
-    __shared__ unsigned s_hist[RADIX_U32_PASSES][RADIX_U32];
+    __shared__ unsigned s_hist[RADIX_U32_PASSES][RADIX];
     hist_clear(s_hist);
     __syncthreads();
     const double m0 = g->mn[0], m1 = g->mn[1], m2 = g->mn[2], inv = g->inv;

@@ -1,5 +1,5 @@
 // coords_dev.h -- device helpers shared by the coordinate kernels (coords.hip: hash-table pipeline in any row order;
-// pyramid.hip: the sorted, hash-free pyramid of pbn_coords_prepare).
+// pyramid.hip: the sorted, hash-free pyramid of pbn_coords_prepare; sort.hip: its radix sort).
 #pragma once
 #include "pbn_common.h"
 
@@ -71,6 +71,23 @@ __device__ __forceinline__ unsigned long long spread3(unsigned v) {  // 16 bits 
     x = (x | (x << 4)) & 0x30c30c30c30c30c3ULL;
     x = (x | (x << 2)) & 0x9249249249249249ULL;
     return x;
+}
+
+// plan words of the sorted pyramid (int32, device; pyramid.hip, and sort.hip's k_sort_pass reads its digits from them):
+// bounding box, then from PL_SORT the sort's words (sort_dev.h: SW_*) with the pyramid's own ticket and error flag in their gap
+enum { PL_BMIN = 0, PL_XMIN, PL_YMIN, PL_ZMIN, PL_BMAX, PL_XMAX, PL_YMAX, PL_ZMAX, PL_SORT = 8, PL_TICKET_PYR = 12, PL_ERROR = 13,
+       PL_WORDS = 64 };
+
+struct KeyPlan { int b0, x0, y0, z0, e, nbits; };
+__device__ __forceinline__ KeyPlan key_plan(const int* __restrict__ plan) {
+    KeyPlan k;
+    k.b0 = plan[PL_BMIN];
+    k.x0 = plan[PL_XMIN] & ~15; k.y0 = plan[PL_YMIN] & ~15; k.z0 = plan[PL_ZMIN] & ~15;
+    const int ext = max(max(plan[PL_XMAX] - k.x0, plan[PL_YMAX] - k.y0), plan[PL_ZMAX] - k.z0);
+    k.e = ext > 0 ? 32 - __clz(ext) : 1;
+    const int bext = plan[PL_BMAX] - k.b0;
+    k.nbits = 3 * k.e + (bext > 0 ? 32 - __clz(bext) : 0);
+    return k;
 }
 
 __device__ __forceinline__ int wave_incl_scan_i(int v) {

@@ -9,7 +9,7 @@
 //              face), normalised, and (b) segmentator.cpp:195-198's running lerp, once per occurrence;
 //   weights    3F edges (i1,i2), (i1,i3), (i3,i2) per face (segmentator.cpp:186-192), or the caller's edges
 //              (segment_point), w as segmentator.cpp:204-229 computes it, NaN kept;
-//   sort       pyramid.hip's LSD radix sort on (order-preserving u32 of w, edge index): a total, stable order, NaN last;
+//   sort       sort.hip's LSD radix sort on (order-preserving u32 of w, edge index): a total, stable order, NaN last;
 //   sweep      segment_graph + the small-segment join in host C++ over ONE read-back of the sorted (a, b, w), with the
 //              reference's universe (union by rank, sizes, one-step path compression), so roots -- not only partitions --
 //              come out as the reference's for the same edge order;
@@ -25,7 +25,7 @@
 #include <cmath>
 #include <vector>
 
-#include "sort_dev.h"
+#include "scan_dev.h"
 
 namespace pbn {
 namespace {
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(TPB) void k_edge_weights(const float* __restrict__ 
                                                       const int* __restrict__ idx32, int mode, int n_edges,
                                                       float* __restrict__ w_out, u64* __restrict__ keys,
                                                       int* __restrict__ vals, unsigned* __restrict__ ghist) {
-    __shared__ unsigned s_hist[RADIX_U32_PASSES][RADIX_U32];
+    __shared__ unsigned s_hist[RADIX_U32_PASSES][RADIX];
     hist_clear(s_hist);
     __syncthreads();
     for (int e = blockIdx.x * TPB + threadIdx.x; e < n_edges; e += gridDim.x * TPB) {

@@ -30,7 +30,7 @@
 // is read back inside the loop.
 #include <cmath>
 
-#include "sort_dev.h"
+#include "scan_dev.h"
 
 namespace pbn {
 namespace {

@@ -90,7 +90,7 @@ int scan_exclusive_i32(const int* in, int* out, int n, int* tmp, int* total, hip
 // the same in ONE launch (chained scan over the workgroups); state: scan_chained_state_words(n) 64-bit words zeroed by the caller.
 // A workgroup that gives up waiting for its predecessors ORs SCAN_CHAIN_SPIN into *status (status may be null).  The callers
 // are grouping's scans (cluster.hip), so the bit lives in grouping's status word next to its own bits 1, 2 and 4; it is not
-// sort_dev.h's SCAN_WALK_CAP, which has the same value in the scan-decode stages' word.
+// scan_dev.h's SCAN_WALK_CAP, which has the same value in the scan-decode stages' word.
 constexpr int SCAN_CHAIN_SPIN = 16;
 size_t scan_chained_state_words(long long n);
 int scan_exclusive_i32_chained(const int* in, int* out, int n, unsigned long long* state_zeroed, int* total, int* status,
@@ -137,15 +137,6 @@ int coords_number_first(const int32_t* slot_of_row, const int32_t* table_vals, c
 size_t pyramid_scratch_bytes(int n);
 int coords_prepare_sorted(const int32_t* coords, const int32_t* n_dev, int n, int want_k5, int x_fastest, void* arena,
                           const pbn_prepare_layout* P, hipStream_t stream);
-// pyramid.hip: its LSD radix sort (k_sort_pass's digit pass) for 32-bit keys in the low half of u64 keys, values carried;
-// stable, so ties keep the input order.  ghist: RADIX_U32_PASSES x 2048 digit histograms (digit p = key >> 11p & 2047),
-// filled by the caller; the result lands in keys_b / vals_b.  A chained scan that gives up ORs SCAN_SORT_SPIN (8) into
-// *status.  sort_dev.h holds that name and what the callers share: histogram helpers, SortBufs, sort_run.
-constexpr int RADIX_U32_DIGIT_BITS = 11, RADIX_U32_PASSES = 3;
-size_t radix_sort_u32_scratch_bytes(int n);
-int radix_sort_u32_tile();                         // keys per workgroup of a digit pass (SORT_TILE of this build)
-int radix_sort_u32(unsigned long long* keys_a, unsigned long long* keys_b, int32_t* vals_a, int32_t* vals_b, int n,
-                   const unsigned* ghist, int32_t* status, void* scratch, size_t scratch_bytes, hipStream_t stream);
 // cloud.hip: k_cloud_box for thin.hip -- box[0..2] / box[3..5] = minimum / maximum per axis as order-preserving u32 keys
 // (the caller fills them with 0xff / 0 first), status |= SCAN_NONFINITE when a coordinate is NaN or infinite; n > 0
 int cloud_box(const float* xyz, int n, unsigned* box, int32_t* status, hipStream_t stream);

@@ -6,8 +6,9 @@
 //      input order = the external row order); the same launches reduce the bounding box and write each survivor's Z-order
 //      key  (batch - b_min) << 3e | interleave(x - x0, y - y0, z - z0)  (x0.. = box minimum rounded down to a multiple of 16,
 //      e = bits of the largest extent) together with the digit histograms of the sort;
-//   2. stable LSD radix sort of (key, row) -- own kernels: 11-bit digits, one launch per digit with a chained (decoupled
-//      look-back) scan over the workgroups, only the digits the box needs (24..33 bits for a room at 2 cm -> 3 launches);
+//   2. stable LSD radix sort of (key, row) -- own kernels (sort.hip: k_sort_pass behind radix_sort_planned): digits of at
+//      most 11 bits, one launch per digit with a chained (decoupled look-back) scan over the workgroups, only the digits
+//      the box needs (24..33 bits for a room at 2 cm -> 3 launches);
 //   3. ONE pass over the sorted rows builds all four coarser levels: in Z-order the children of a voxel are contiguous, so
 //      "first row of a level-l voxel" is a comparison with the previous row, the level's numbering is a 4-wide scan
 //      (chained like the sort), and coordinates, parent / child tables and the transposed-convolution tables follow -- no
@@ -17,51 +18,18 @@
 //      its parent is child (p + d) & 1 of the parent's neighbour at (p + d) >> 1: two reads of small, local tables instead
 //      of a probe sequence through a table of random 64-byte lines per (row, offset).
 // Every output equals the one the hash-table pipeline of coords.hip produces for the same rows (tests/test_pyramid_gpu.py).
-#include "coords_dev.h"
+#include "sort_dev.h"
 
 namespace pbn {
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int RADIX_BITS = 11, RADIX = 1 << RADIX_BITS, MAX_PASSES = 4;
-#ifndef PBN_SORT_ITEMS
-#define PBN_SORT_ITEMS 8
-#endif
-constexpr int SORT_ITEMS = PBN_SORT_ITEMS, SORT_TILE = TPB * SORT_ITEMS;   // keys per workgroup; a wave's are contiguous
 constexpr int PYR_ITEMS = 4, PYR_TILE = TPB * PYR_ITEMS;           // 1024 rows per workgroup, striped over the threads
-constexpr unsigned SPIN_LIMIT = 1u << 24;                          // every chained-scan poll is bounded
-constexpr size_t SORT_LDS_BYTES = (size_t)SORT_TILE * 12 + (size_t)(TPB / 64 + 2) * RADIX * 4;
-
-// plan words (int32, device): bounding box, tickets, error flag
-enum { PL_BMIN = 0, PL_XMIN, PL_YMIN, PL_ZMIN, PL_BMAX, PL_XMAX, PL_YMAX, PL_ZMAX, PL_TICKET0 = 8, PL_TICKET_PYR = 12,
-       PL_ERROR = 13, PL_STAMPS = 16, PL_WORDS = 64 };
 constexpr int PBN_STATUS_KEY_BITS = 4;     // the box needs more key bits than MAX_PASSES digits hold
-constexpr int PBN_STATUS_SPIN = 8;         // a chained scan gave up waiting for a predecessor
+constexpr int PBN_STATUS_SPIN = SORT_SPIN; // a chained scan gave up waiting for a predecessor
 
-struct KeyPlan { int b0, x0, y0, z0, e, nbits; };
-__device__ __forceinline__ KeyPlan key_plan(const int* __restrict__ plan) {
-    KeyPlan k;
-    k.b0 = plan[PL_BMIN];
-    k.x0 = plan[PL_XMIN] & ~15; k.y0 = plan[PL_YMIN] & ~15; k.z0 = plan[PL_ZMIN] & ~15;
-    const int ext = max(max(plan[PL_XMAX] - k.x0, plan[PL_YMAX] - k.y0), plan[PL_ZMAX] - k.z0);
-    k.e = ext > 0 ? 32 - __clz(ext) : 1;
-    const int bext = plan[PL_BMAX] - k.b0;
-    k.nbits = 3 * k.e + (bext > 0 ? 32 - __clz(bext) : 0);
-    return k;
-}
 __device__ __forceinline__ u64 key_of(const KeyPlan& k, int b, int x, int y, int z) {
     return ((u64)(unsigned)(b - k.b0) << (3 * k.e)) | spread3((unsigned)(x - k.x0)) | (spread3((unsigned)(y - k.y0)) << 1) |
            (spread3((unsigned)(z - k.z0)) << 2);
-}
-
-// digits of the sort: see "2. radix sort"
-struct SortPlan { int passes, dbits; };
-__device__ __forceinline__ SortPlan sort_plan(int nbits) {
-    SortPlan sp;
-    sp.passes = nbits <= 3 * RADIX_BITS ? min(3, (nbits + 7) / 8) : MAX_PASSES;
-    sp.dbits = max(8, (nbits + sp.passes - 1) / sp.passes);
-    return sp;
 }
 
 // ---- 1. de-duplication -------------------------------------------------------------------------------------------------
@@ -108,15 +76,13 @@ __global__ __launch_bounds__(TPB) void k_unique_keys(const int* __restrict__ coo
                                                     u64* __restrict__ sort_keys, int* __restrict__ sort_vals,
                                                     unsigned* __restrict__ ghist) {
     __shared__ unsigned s_hist[MAX_PASSES][RADIX];
-    for (int e = threadIdx.x; e < MAX_PASSES * RADIX; e += TPB) (&s_hist[0][0])[e] = 0u;
+    hist_clear(s_hist, MAX_PASSES);
     __syncthreads();
     const int n = real_n(n_dev, n_max);
     const KeyPlan kp = key_plan(plan);
     // (no rows -- a device-side count of 0 --: the box is still the fill pattern, not a box too wide)
     if (blockIdx.x == 0 && threadIdx.x == 0 && n > 0 && kp.nbits > MAX_PASSES * RADIX_BITS) atomicOr(status, PBN_STATUS_KEY_BITS);
     const SortPlan sp = sort_plan(min(kp.nbits, MAX_PASSES * RADIX_BITS));
-    const int passes = sp.passes;
-    const unsigned dmask = (1u << sp.dbits) - 1u;
     for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) {
         const int first = first_row[i];
         const int id_first = newid[first];
@@ -130,279 +96,11 @@ __global__ __launch_bounds__(TPB) void k_unique_keys(const int* __restrict__ coo
             const u64 key = key_of(kp, c.x, c.y, c.z, c.w);
             sort_keys[id_first] = key;
             sort_vals[id_first] = id_first;
-            for (int p = 0; p < passes; ++p) atomicAdd(&s_hist[p][(unsigned)(key >> (p * sp.dbits)) & dmask], 1u);
+            hist_add(s_hist, key, sp.passes, sp.dbits);
         }
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < passes * RADIX; e += TPB) {
-        const unsigned v = (&s_hist[0][0])[e];
-        if (v) atomicAdd(&ghist[e], v);
-    }
-}
-
-// ---- 2. radix sort: one digit per launch, chained scan over the workgroups ---------------------------------------------------
-// Digit width: the box needs nbits key bits; they are cut into the fewest digits of at most 11 bits (3 up to 33 bits, 4
-// up to 44), each as NARROW as that allows (>= 8 bits): a workgroup's 4096 keys then fall into few enough bins that, after
-// a local reorder through LDS, runs of keys leave for consecutive addresses (a 24-bit room: 256 bins, runs of 16 keys =
-// whole cache lines; the scattered 8- and 4-byte stores of a direct scatter were 2/3 of a pass).
-// state[blk][bins / 2]: two bins per 64-bit word, each  flag << 30 | count  (flag 1: the workgroup's own count, 2: the
-// inclusive prefix over workgroups 0..blk); a word is written by ONE agent-scope atomic store and read by agent-scope
-// atomic loads (the payload and its flag share the 8-byte granule: no fences).  Workgroup numbers are drawn from a ticket
-// so that every predecessor of a running workgroup has started.
-__device__ __forceinline__ u64 ld_state(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// the same load without the compiler's wait behind it: a batch of them is issued back to back and waited for once
-// (ld_state_wait); the agent-scope atomic form above costs one memory round trip PER load (measured: 8 of them 3.4 us)
-__device__ __forceinline__ void ld_state_issue(u64& dst, const u64* p) {
-    asm volatile("global_load_dwordx2 %0, %1, off sc1" : "=v"(dst) : "v"(p) : "memory");
-}
-__device__ __forceinline__ void ld_state_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void st_state(u64* p, u64 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-#ifdef PBN_SORT_STAMPS
-#define SORT_STAMP(I) if (threadIdx.x == 0 && pass == 0 && (blk == 0 || blk == 20)) plan[PL_STAMPS + (blk ? 16 : 0) + (I)] = (int)__builtin_readcyclecounter();
-#else
-#define SORT_STAMP(I)
-#endif
-struct SortShared {
-    u64* s_key; int* s_val; unsigned (*s_cnt)[RADIX]; unsigned* s_base; unsigned* s_local;
-};
-
-// One digit of the sort for a workgroup, BPT = bins per thread (digit width 8 + log2(BPT) bits) as a compile-time constant:
-// every register array below is indexed by constants.
-template <int BPT>
-__device__ __forceinline__ void sort_pass_body(const u64* __restrict__ kin, u64* __restrict__ kout, const int* __restrict__ vin,
-                                               int* __restrict__ vout, int n, int pass, int* __restrict__ plan,
-                                               int* __restrict__ status, const unsigned* __restrict__ ghist,
-                                               u64* __restrict__ state, const SortShared& sh, int blk, unsigned (*s_wtot)[TPB / 64]) {
-    constexpr int DBITS = (BPT == 1 ? 8 : BPT == 2 ? 9 : BPT == 4 ? 10 : 11), R = 1 << DBITS;
-    constexpr int W = BPT >= 2 ? BPT / 2 : 1;        // 64-bit state words of one workgroup this thread reads
-    constexpr int LB = 32 / W;                       // predecessors per look-back batch (32 loads in flight per thread)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long base = (long long)blk * SORT_TILE;
-    const int shift = pass * DBITS;
-    constexpr unsigned dmask = (unsigned)R - 1u;
-    SORT_STAMP(0);
-
-    // A. stable rank of every key inside (wave, bin): a wave owns a run of consecutive keys, 64 per round.  Every key and
-    // value of the thread is loaded first (independent loads, all in flight together): a load left inside the ranking
-    // rounds would wait out its latency once per round.
-    u64 key[SORT_ITEMS];
-    int val[SORT_ITEMS];
-    unsigned rank[SORT_ITEMS];
-    unsigned* my_cnt = sh.s_cnt[wave];
-    const u64 lt = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int j = 0; j < SORT_ITEMS; ++j) {
-        const long long i = base + wave * (SORT_ITEMS * 64) + j * 64 + lane;
-        key[j] = i < n ? kin[i] : ~0ull;
-        val[j] = i < n ? vin[i] : 0;
-    }
-#pragma unroll
-    for (int j = 0; j < SORT_ITEMS; ++j) {
-        const long long i = base + wave * (SORT_ITEMS * 64) + j * 64 + lane;
-        const bool ok = i < n;
-        const unsigned d = (unsigned)(key[j] >> shift) & dmask;
-        u64 peers = __ballot(ok);
-#pragma unroll
-        for (int b = 0; b < DBITS; ++b) {
-            const u64 m = __ballot((d >> b) & 1u);
-            peers &= ((d >> b) & 1u) ? m : ~m;
-        }
-        unsigned old = 0;
-        const int leader = ok ? __ffsll((long long)peers) - 1 : lane;
-        if (ok && lane == leader) old = atomicAdd(&my_cnt[d], (unsigned)__popcll(peers));     // own row of s_cnt: wave-private
-        old = (unsigned)__shfl((int)old, leader, 64);
-        rank[j] = old + (unsigned)__popcll(peers & lt);
-    }
-    SORT_STAMP(1);
-    __syncthreads();
-    SORT_STAMP(2);
-
-    // B. per bin: wave bases, the workgroup's count, the chained scan over the workgroups, the bin's global and local start
-    const int b0 = tid * BPT;                        // BPT consecutive bins per thread (threads past the last bin idle: BPT >= 1)
-    unsigned tot[BPT], gh[BPT], gsum = 0, lsum = 0;
-#pragma unroll
-    for (int q = 0; q < BPT; ++q) {
-        unsigned run = 0;
-#pragma unroll
-        for (int w = 0; w < TPB / 64; ++w) {
-            const unsigned c = sh.s_cnt[w][b0 + q];
-            sh.s_cnt[w][b0 + q] = run;
-            run += c;
-        }
-        tot[q] = run;
-        gh[q] = ghist[pass * RADIX + b0 + q];
-        gsum += gh[q];
-        lsum += run;
-    }
-    // publish this workgroup's counts (or, for the first one, its prefixes); BPT == 1: lanes 2i, 2i+1 share a word
-    u64* mine = state + (size_t)blk * (RADIX / 2);
-    auto publish = [&](const unsigned* v, u64 flag) {
-        if constexpr (BPT == 1) {
-            const unsigned other = (unsigned)__shfl_xor((int)v[0], 1, 64);
-            if (!(tid & 1)) st_state(mine + tid / 2, (flag << 30 | v[0]) | ((flag << 30 | other) << 32));
-        } else {
-#pragma unroll
-            for (int q = 0; q < BPT; q += 2) st_state(mine + (b0 + q) / 2, (flag << 30 | v[q]) | ((flag << 30 | v[q + 1]) << 32));
-        }
-    };
-    publish(tot, blk == 0 ? 2ull : 1ull);
-    SORT_STAMP(3);
-    // exclusive prefix over the workgroups in front of this one, in batches of LB predecessors: their words are loaded
-    // together (32 independent loads, one round trip: the workgroups of a small sort all start at once, so a walk that
-    // waited for one predecessor at a time would be as long as the grid), then consumed nearest first until a prefix flag
-    // ends the bin's walk
-    unsigned excl[BPT];
-#pragma unroll
-    for (int q = 0; q < BPT; ++q) excl[q] = 0;
-    unsigned open = blk > 0 ? (1u << BPT) - 1u : 0u;                 // bins still looking back
-    unsigned spins = 0;
-    int p = blk - 1;
-    while (p >= 0 && open) {
-        u64 wq[LB][W];
-#pragma unroll
-        for (int d = 0; d < LB; ++d) {
-            const int pp = p - d;
-#pragma unroll
-            for (int q2 = 0; q2 < W; ++q2) {
-                wq[d][q2] = 0ull;
-                ld_state_issue(wq[d][q2], state + (size_t)(pp >= 0 ? pp : 0) * (RADIX / 2) + b0 / 2 + q2);   // block 0 stands in for pp < 0
-            }
-        }
-        ld_state_wait();
-        int used = 0;                                                // predecessors of this batch consumed
-#pragma unroll
-        for (int d = 0; d < LB; ++d) {
-#pragma unroll
-            for (int q2 = 0; q2 < W; ++q2) asm volatile("" : "+v"(wq[d][q2]));
-            if (p - d < 0 || !open || used != d) continue;
-            unsigned v[BPT];
-            if constexpr (BPT == 1) v[0] = (unsigned)(wq[d][0] >> ((tid & 1) * 32));
-            else {
-#pragma unroll
-                for (int q = 0; q < BPT; q += 2) { v[q] = (unsigned)wq[d][q / 2]; v[q + 1] = (unsigned)(wq[d][q / 2] >> 32); }
-            }
-            bool ready = true;
-#pragma unroll
-            for (int q = 0; q < BPT; ++q)
-                if ((open >> q) & 1u) ready &= ((v[q] >> 30) != 0u);
-            if (!ready) continue;
-#pragma unroll
-            for (int q = 0; q < BPT; ++q) {
-                if (!((open >> q) & 1u)) continue;
-                excl[q] += v[q] & 0x3fffffffu;
-                if ((v[q] >> 30) == 2u) open &= ~(1u << q);
-            }
-            used = d + 1;
-        }
-        p -= used;
-        if (used == 0) {
-            if (++spins > SPIN_LIMIT) { atomicOr(status, PBN_STATUS_SPIN); break; }
-            __builtin_amdgcn_s_sleep(1);
-        }
-    }
-    SORT_STAMP(4);
-    if (blk > 0) {
-        unsigned incl[BPT];
-#pragma unroll
-        for (int q = 0; q < BPT; ++q) incl[q] = excl[q] + tot[q];
-        publish(incl, 2ull);
-    }
-    // bucket starts (exclusive scan of the global histogram over the bins) and the bins' starts inside this workgroup
-    const unsigned g_incl = (unsigned)wave_incl_scan_i((int)gsum), l_incl = (unsigned)wave_incl_scan_i((int)lsum);
-    if (lane == 63) { s_wtot[0][wave] = g_incl; s_wtot[1][wave] = l_incl; }
-    __syncthreads();
-    unsigned gstart = g_incl - gsum, lstart = l_incl - lsum;
-    for (int w = 0; w < wave; ++w) { gstart += s_wtot[0][w]; lstart += s_wtot[1][w]; }
-#pragma unroll
-    for (int q = 0; q < BPT; ++q) {
-        sh.s_base[b0 + q] = gstart + excl[q];
-        sh.s_local[b0 + q] = lstart;
-        gstart += gh[q];
-        lstart += tot[q];
-    }
-    __syncthreads();
-    SORT_STAMP(5);
-
-    // C. the workgroup's keys in sorted order through LDS, then out: consecutive threads write consecutive addresses of a bin
-#pragma unroll
-    for (int j = 0; j < SORT_ITEMS; ++j) {
-        const long long i = base + wave * (SORT_ITEMS * 64) + j * 64 + lane;
-        if (i < n) {
-            const unsigned d = (unsigned)(key[j] >> shift) & dmask;
-            const unsigned lp = sh.s_local[d] + sh.s_cnt[wave][d] + rank[j];
-            sh.s_key[lp] = key[j];
-            sh.s_val[lp] = val[j];
-        }
-    }
-    __syncthreads();
-    SORT_STAMP(6);
-    const int here = (int)min((long long)SORT_TILE, (long long)n - base);
-    for (int e = tid; e < here; e += TPB) {
-        const u64 k = sh.s_key[e];
-        const unsigned d = (unsigned)(k >> shift) & dmask;
-        const unsigned pos = sh.s_base[d] + ((unsigned)e - sh.s_local[d]);
-        kout[pos] = k;
-        vout[pos] = sh.s_val[e];
-    }
-    SORT_STAMP(7);
-}
-
-__global__ __launch_bounds__(TPB) void k_sort_pass(const u64* __restrict__ kin, u64* __restrict__ kout,
-                                                  const int* __restrict__ vin, int* __restrict__ vout, const int* n_dev,
-                                                  int n_max, int pass, int* __restrict__ plan, int* __restrict__ status,
-                                                  const unsigned* __restrict__ ghist, u64* __restrict__ state) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char sort_smem[];      // SORT_LDS_BYTES
-    __shared__ unsigned s_wtot[2][TPB / 64];
-    __shared__ int s_blk;
-    SortShared sh;
-    sh.s_key = reinterpret_cast<u64*>(sort_smem);                                   // SORT_TILE keys in the workgroup's sorted order
-    sh.s_val = reinterpret_cast<int*>(sh.s_key + SORT_TILE);
-    sh.s_cnt = reinterpret_cast<unsigned (*)[RADIX]>(sh.s_val + SORT_TILE);         // per wave and bin: counts, then wave bases
-    sh.s_base = &sh.s_cnt[TPB / 64][0];          // where the bin's keys of this workgroup start in the output
-    sh.s_local = sh.s_base + RADIX;              // ... and in the workgroup's own sorted order
-    const KeyPlan kp = key_plan(plan);
-    if (kp.nbits > MAX_PASSES * RADIX_BITS) return;
-    const SortPlan sp = sort_plan(kp.nbits);
-    if (pass >= sp.passes) return;                    // this digit does not exist
-    const int n = real_n(n_dev, n_max);
-    if (n <= 0) return;
-    const int tid = threadIdx.x;
-    if (tid == 0) s_blk = atomicAdd(&plan[PL_TICKET0 + pass], 1);
-    for (int e = tid; e < (TPB / 64) * RADIX; e += TPB) (&sh.s_cnt[0][0])[e] = 0u;
-    __syncthreads();
-    const int blk = s_blk;
-    if ((long long)blk * SORT_TILE >= n) return;
-    switch (sp.dbits) {
-        case 8: sort_pass_body<1>(kin, kout, vin, vout, n, pass, plan, status, ghist, state, sh, blk, s_wtot); break;
-        case 9: sort_pass_body<2>(kin, kout, vin, vout, n, pass, plan, status, ghist, state, sh, blk, s_wtot); break;
-        case 10: sort_pass_body<4>(kin, kout, vin, vout, n, pass, plan, status, ghist, state, sh, blk, s_wtot); break;
-        default: sort_pass_body<8>(kin, kout, vin, vout, n, pass, plan, status, ghist, state, sh, blk, s_wtot); break;
-    }
-}
-
-// The same digit pass for a caller's 32-bit keys (radix_sort_u32 below): three 11-bit digits, tickets in words of its own
-__global__ __launch_bounds__(TPB) void k_sort_pass_u32(const u64* __restrict__ kin, u64* __restrict__ kout,
-                                                      const int* __restrict__ vin, int* __restrict__ vout, int n, int pass,
-                                                      int* __restrict__ words, int* __restrict__ status,
-                                                      const unsigned* __restrict__ ghist, u64* __restrict__ state) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char sort_smem[];      // SORT_LDS_BYTES
-    __shared__ unsigned s_wtot[2][TPB / 64];
-    __shared__ int s_blk;
-    SortShared sh;
-    sh.s_key = reinterpret_cast<u64*>(sort_smem);
-    sh.s_val = reinterpret_cast<int*>(sh.s_key + SORT_TILE);
-    sh.s_cnt = reinterpret_cast<unsigned (*)[RADIX]>(sh.s_val + SORT_TILE);
-    sh.s_base = &sh.s_cnt[TPB / 64][0];
-    sh.s_local = sh.s_base + RADIX;
-    if (n <= 0) return;
-    const int tid = threadIdx.x;
-    if (tid == 0) s_blk = atomicAdd(&words[PL_TICKET0 + pass], 1);
-    for (int e = tid; e < (TPB / 64) * RADIX; e += TPB) (&sh.s_cnt[0][0])[e] = 0u;
-    __syncthreads();
-    const int blk = s_blk;
-    if ((long long)blk * SORT_TILE >= n) return;
-    sort_pass_body<8>(kin, kout, vin, vout, n, pass, words, status, ghist, state, sh, blk, s_wtot);
+    hist_flush(s_hist, ghist, sp.passes);
 }
 
 // ---- 3. all levels from the sorted rows ------------------------------------------------------------------------------------
@@ -681,11 +379,11 @@ __global__ __launch_bounds__(TPB) void k_maps_down(const DownJob jb) {
 // scratch of the sorted pipeline inside the prepare arena's `sort_temp` block
 size_t pyramid_scratch_bytes(int n) {
     const size_t N = (size_t)(n > 0 ? n : 1);
-    const size_t sort_blocks = (size_t)cdiv((long long)N, SORT_TILE), pyr_blocks = (size_t)cdiv((long long)N, PYR_TILE);
+    const size_t pyr_blocks = (size_t)cdiv((long long)N, PYR_TILE);
     size_t b = 0;
     b += align_up(PL_WORDS * sizeof(int), 256);                               // plan
     b += align_up((size_t)MAX_PASSES * RADIX * sizeof(unsigned), 256);       // digit histograms
-    b += align_up((size_t)MAX_PASSES * sort_blocks * (RADIX / 2) * sizeof(u64), 256);   // sort scan state
+    b += align_up(sort_state_bytes(n, MAX_PASSES), 256);                      // sort scan state
     b += align_up(pyr_blocks * 2 * sizeof(u64), 256);                         // pyramid scan state
     b += 3 * align_up(N * sizeof(u64), 256);                                  // level keys 2..4
     return b + 256;
@@ -697,14 +395,14 @@ int coords_prepare_sorted(const int32_t* coords, const int32_t* n_dev, int n, in
     const pbn_coords_layout* L = &P->pyramid;
     auto I = [&](int64_t o) { return (int32_t*)(A + o); };
     const size_t N = (size_t)(n > 0 ? n : 1);
-    const size_t sort_blocks = (size_t)cdiv((long long)N, SORT_TILE), pyr_blocks = (size_t)cdiv((long long)N, PYR_TILE);
+    const size_t pyr_blocks = (size_t)cdiv((long long)N, PYR_TILE);
     // carve the scratch block
     char* S = A + P->sort_temp;
     size_t off = 0;
     auto take = [&](size_t bytes) { char* p = S + off; off += align_up(bytes, 256); return p; };
     int* plan = (int*)take(PL_WORDS * sizeof(int));
     unsigned* ghist = (unsigned*)take((size_t)MAX_PASSES * RADIX * sizeof(unsigned));
-    u64* sort_state = (u64*)take((size_t)MAX_PASSES * sort_blocks * (RADIX / 2) * sizeof(u64));
+    u64* sort_state = (u64*)take(sort_state_bytes(n, MAX_PASSES));
     u64* pyr_state = (u64*)take(pyr_blocks * 2 * sizeof(u64));
     u64* lkeys[3];
     for (int j = 0; j < 3; ++j) lkeys[j] = (u64*)take(N * sizeof(u64));
@@ -722,7 +420,7 @@ int coords_prepare_sorted(const int32_t* coords, const int32_t* n_dev, int n, in
                                 {A + L->nbr_down[0], (size_t)(L->vals[0] - L->nbr_down[0]), 0xff},
                                 {plan + PL_BMIN, 4 * sizeof(int), 0x7f},
                                 {plan + PL_BMAX, 4 * sizeof(int), 0x80},
-                                {plan + PL_TICKET0, (PL_WORDS - PL_TICKET0) * sizeof(int), 0},
+                                {plan + PL_SORT, (PL_WORDS - PL_SORT) * sizeof(int), 0},
                                 {ghist, (size_t)((char*)lkeys[0] - (char*)ghist), 0}};
         const int frc = fill_ranges(fr, 9, st);
         if (frc != PBN_OK) return frc;
@@ -750,14 +448,9 @@ int coords_prepare_sorted(const int32_t* coords, const int32_t* n_dev, int n, in
     hipLaunchKernelGGL(k_unique_keys, dim3(gb), dim3(TPB), 0, st, coords, slot_of_row, first_row, newid, n_dev, n, I(P->uidx32),
                        I(P->inv32), (long long*)(A + P->unique_index), (long long*)(A + P->inverse), I(P->ucoords), plan, status,
                        keys_a, vals_a, ghist);
-    // 2. sort: pass p reads buffer p & 1
-    static const bool lds_attr = (hipFuncSetAttribute((const void*)k_sort_pass, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                      (int)SORT_LDS_BYTES) == hipSuccess);
-    if (!lds_attr) return PBN_ERR_HIP;
-    for (int p = 0; p < MAX_PASSES; ++p)
-        hipLaunchKernelGGL(k_sort_pass, dim3((unsigned)sort_blocks), dim3(TPB), SORT_LDS_BYTES, st, (p & 1) ? keys_b : keys_a,
-                           (p & 1) ? keys_a : keys_b, (p & 1) ? vals_b : vals_a, (p & 1) ? vals_a : vals_b, n_unique, n, p, plan,
-                           status, ghist, sort_state + (size_t)p * sort_blocks * (RADIX / 2));
+    // 2. sort (sort.hip): pass p reads buffer p & 1; the sort's words are the plan's from PL_SORT
+    rc = radix_sort_planned(keys_a, keys_b, vals_a, vals_b, n_unique, n, plan, status, ghist, sort_state, st);
+    if (rc != PBN_OK) return rc;
     // 3. every level
     PyrOut o;
     for (int l = 0; l < 5; ++l) o.coords[l] = I(L->coords[l]);
@@ -789,35 +482,6 @@ int coords_prepare_sorted(const int32_t* coords, const int32_t* n_dev, int n, in
             hipLaunchKernelGGL(k_maps_down, dim3((unsigned)bl), dim3(TPB), 0, st, dj);
         }
     }
-    PBN_LAUNCH_CHECK();
-    return PBN_OK;
-}
-
-static_assert(RADIX_U32_DIGIT_BITS == RADIX_BITS, "radix_sort_u32 runs sort_pass_body<8>: 11-bit digits");
-
-int radix_sort_u32_tile() { return SORT_TILE; }
-
-size_t radix_sort_u32_scratch_bytes(int n) {
-    const size_t sort_blocks = (size_t)cdiv(n > 0 ? n : 1, SORT_TILE);
-    return align_up(PL_WORDS * sizeof(int), 256) + align_up((size_t)RADIX_U32_PASSES * sort_blocks * (RADIX / 2) * sizeof(u64), 256);
-}
-
-int radix_sort_u32(unsigned long long* keys_a, unsigned long long* keys_b, int32_t* vals_a, int32_t* vals_b, int n,
-                   const unsigned* ghist, int32_t* status, void* scratch, size_t scratch_bytes, hipStream_t st) {
-    if (n <= 0) return PBN_OK;
-    if (scratch_bytes < radix_sort_u32_scratch_bytes(n)) return PBN_ERR_WORKSPACE;
-    const size_t sort_blocks = (size_t)cdiv(n, SORT_TILE);
-    int* words = (int*)scratch;
-    u64* state = (u64*)((char*)scratch + align_up(PL_WORDS * sizeof(int), 256));
-    const int frc = fill_bytes(scratch, 0, radix_sort_u32_scratch_bytes(n), st);
-    if (frc != PBN_OK) return frc;
-    static const bool lds_attr = (hipFuncSetAttribute((const void*)k_sort_pass_u32, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                      (int)SORT_LDS_BYTES) == hipSuccess);
-    if (!lds_attr) return PBN_ERR_HIP;
-    for (int p = 0; p < RADIX_U32_PASSES; ++p)
-        hipLaunchKernelGGL(k_sort_pass_u32, dim3((unsigned)sort_blocks), dim3(TPB), SORT_LDS_BYTES, st, (p & 1) ? keys_b : keys_a,
-                           (p & 1) ? keys_a : keys_b, (p & 1) ? vals_b : vals_a, (p & 1) ? vals_a : vals_b, n, p, words, status,
-                           ghist, state + (size_t)p * sort_blocks * (RADIX / 2));
     PBN_LAUNCH_CHECK();
     return PBN_OK;
 }

@@ -1,9 +1,9 @@
 // selftest.hip -- entry points that put the shared device primitives under a test of their own: fill_ranges and the two
-// exclusive scans (common.hip), radix_sort_u32 behind sort_dev.h's SortBufs / sort_run and histogram helpers (pyramid.hip).
+// exclusive scans (common.hip), radix_sort_u32 behind sort_dev.h's SortBufs / sort_run and histogram helpers (sort.hip).
 // Every entry is a shim: it checks its arguments on the host, carves its workspace with Carver and calls the primitive the
 // way the stages do (thin.hip's carve / args / run split).  Nothing here computes, repairs or re-orders a result:
 // tests/test_prims_gpu.py compares what comes back with tests/prims_ref.py byte for byte.
-#include "sort_dev.h"
+#include "scan_dev.h"
 
 namespace pbn {
 namespace {
@@ -36,7 +36,7 @@ size_t scan_ws_bytes(int n, int chained) {
 __global__ __launch_bounds__(TPB) void k_selftest_keys(const unsigned* __restrict__ key_in, const int* __restrict__ val_in, int n,
                                                        u64* __restrict__ keys, int* __restrict__ vals,
                                                        unsigned* __restrict__ ghist) {
-    __shared__ unsigned s_hist[RADIX_U32_PASSES][RADIX_U32];
+    __shared__ unsigned s_hist[RADIX_U32_PASSES][RADIX];
     hist_clear(s_hist);
     __syncthreads();
     for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) {

@@ -1,52 +1,76 @@
-// sort_dev.h -- what the stages of the scan-decode chain (mesh.hip, cloud.hip, thin.hip, vote.hip, orient.hip) share around
-// radix_sort_u32: the digit histograms its caller fills, the buffers of a sort, the launch grid, the chain's limits and
-// status bits, and the stage timing of the *_timed entry points.  Integer helpers and host code only: nothing here depends
-// on a translation unit's -ffp-contract setting.
+// sort_dev.h -- the interface of sort.hip's LSD radix sort, for the coordinate pyramid (pyramid.hip) and for the callers of
+// radix_sort_u32 (scan_dev.h's stages, selftest.hip): the digit constants, the spin status bit, the digit histograms a
+// caller fills, the sort's own words, the host entry points and the buffers of a sort.  Integer helpers and host code
+// only: nothing here depends on a translation unit's -ffp-contract setting.
 #pragma once
 #include "coords_dev.h"
 
 namespace pbn {
+
+// ---- host entry points (sort.hip) ------------------------------------------------------------------------------------------
+size_t sort_state_bytes(int n, int passes);        // chained-scan state of `passes` digit passes over n keys (n <= 0: as 1 key)
+// The pyramid's sort of (64-bit key, row): MAX_PASSES launches of k_sort_pass, which reads its digits from the plan
+// (coords_dev.h) and returns at once in a pass the box does not need; the result lands in buffer (passes & 1).  The sort's
+// words are the plan's SW_WORDS ints from PL_SORT (one pointer: a second one cost the ticket draw a scalar load, 0.2 us a
+// pass); the caller zeroes them, state (sort_state_bytes(n_max, MAX_PASSES)) and ghist (MAX_PASSES x RADIX, then filled).
+int radix_sort_planned(unsigned long long* keys_a, unsigned long long* keys_b, int32_t* vals_a, int32_t* vals_b,
+                       const int32_t* n_dev, int n_max, int32_t* plan, int32_t* status, const unsigned* ghist,
+                       unsigned long long* state, hipStream_t stream);
+// The same digit pass for 32-bit keys in the low half of u64 keys, values carried; stable, so ties keep the input order.
+// ghist: RADIX_U32_PASSES x RADIX digit histograms (digit p = key >> p * RADIX_BITS & RADIX - 1), filled by the caller; the
+// result lands in keys_b / vals_b.  A chained scan that gives up ORs SORT_SPIN into *status.
+size_t radix_sort_u32_scratch_bytes(int n);
+int radix_sort_u32_tile();                         // keys per workgroup of a digit pass (SORT_TILE of this build)
+int radix_sort_u32(unsigned long long* keys_a, unsigned long long* keys_b, int32_t* vals_a, int32_t* vals_b, int n,
+                   const unsigned* ghist, int32_t* status, void* scratch, size_t scratch_bytes, hipStream_t stream);
+
 namespace {
 
 typedef unsigned long long u64;
 
-// ---- limits and status bits ----------------------------------------------------------------------------------------------
-constexpr int SCAN_MAX_POINTS = 1 << 28;          // points of a cloud, raw or kept
-constexpr int SCAN_MAX_K = 32;                    // neighbours per point
-// Bits of a stage's status word that mean the same in every stage (pbnet_amd/mesh.py mirrors them as CLOUD_*).
-enum : int {
-    SCAN_NONFINITE = 1,                           // k_cloud_box: a coordinate is NaN or infinite
-    SCAN_EXTENT = 2,                              // k_thin_keys: an axis spans 2^21 cells or more
-    SCAN_SORT_SPIN = 8,                           // radix_sort_u32: a chained scan gave up
-    SCAN_WALK_CAP = 16,                           // k_orient_jump: a link chain did not end within n hops
-};
+// ---- digits ------------------------------------------------------------------------------------------------------------------
+constexpr int RADIX_BITS = 11, RADIX = 1 << RADIX_BITS;   // the widest digit and its bins (sort.hip: why a digit may be narrower)
+constexpr int MAX_PASSES = 4;                             // digits of the widest key the sort takes
+constexpr int RADIX_U32_PASSES = 3;                       // digits of radix_sort_u32, each RADIX_BITS wide
+constexpr int SORT_SPIN = 8;                              // status bit: a chained scan gave up waiting for a predecessor
 
-// blocks of a striding grid over n items: at least one, at most cap
-inline int grid_for(long long n, int cap = 1024) {
-    const long long b = (n + TPB - 1) / TPB;
-    return (int)(b < 1 ? 1 : b > cap ? cap : b);
+// nbits key bits are cut into the fewest digits of at most RADIX_BITS bits, each as narrow as that allows (>= 8 bits)
+struct SortPlan { int passes, dbits; };
+__device__ __forceinline__ SortPlan sort_plan(int nbits) {
+    SortPlan sp;
+    sp.passes = nbits <= 3 * RADIX_BITS ? min(3, (nbits + 7) / 8) : MAX_PASSES;
+    sp.dbits = max(8, (nbits + sp.passes - 1) / sp.passes);
+    return sp;
 }
 
-// ---- digit histograms of radix_sort_u32 ----------------------------------------------------------------------------------
-// A keys kernel declares `__shared__ unsigned s_hist[RADIX_U32_PASSES][RADIX_U32]`, clears it, adds the low 32 bits of every
-// key it writes and flushes the bins it touched to the sort's ghist; it puts a barrier after the clear and before the flush.
-constexpr int RADIX_U32 = 1 << RADIX_U32_DIGIT_BITS;
+// A word of chained-scan state (sort.hip's digit pass, k_pyramid's level scan): payload and flag in one 8-byte granule,
+// written by ONE agent-scope atomic store and read by agent-scope atomic loads, so no fences; every poll is bounded
+__device__ __forceinline__ u64 ld_state(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st_state(u64* p, u64 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+constexpr unsigned SPIN_LIMIT = 1u << 24;
 
-__device__ __forceinline__ void hist_clear(unsigned (*s_hist)[RADIX_U32]) {
-    for (int e = threadIdx.x; e < RADIX_U32_PASSES * RADIX_U32; e += TPB) (&s_hist[0][0])[e] = 0u;
+// The sort's own words (int32, zeroed by the caller): one ticket per pass and, in a PBN_SORT_STAMPS build, the cycle
+// stamps of two workgroups.  Words 4..7 are not the sort's: a caller that embeds the block may keep words of its own there.
+enum { SW_TICKET0 = 0, SW_STAMPS = 8, SW_WORDS = SW_STAMPS + 32 };
+
+// ---- digit histograms ----------------------------------------------------------------------------------------------------
+// A keys kernel declares `__shared__ unsigned s_hist[passes][RADIX]`, clears it, adds every key it writes (`passes` digits
+// of `dbits` bits) and flushes the bins it touched to the sort's ghist; it puts a barrier after the clear and before the
+// flush.  The defaults are radix_sort_u32's digits.
+__device__ __forceinline__ void hist_clear(unsigned (*s_hist)[RADIX], int passes = RADIX_U32_PASSES) {
+    for (int e = threadIdx.x; e < passes * RADIX; e += TPB) (&s_hist[0][0])[e] = 0u;
 }
-__device__ __forceinline__ void hist_add(unsigned (*s_hist)[RADIX_U32], unsigned key) {
-#pragma unroll
-    for (int p = 0; p < RADIX_U32_PASSES; ++p) atomicAdd(&s_hist[p][(key >> (p * RADIX_U32_DIGIT_BITS)) & (RADIX_U32 - 1)], 1u);
+__device__ __forceinline__ void hist_add(unsigned (*s_hist)[RADIX], u64 key, int passes = RADIX_U32_PASSES, int dbits = RADIX_BITS) {
+    for (int p = 0; p < passes; ++p) atomicAdd(&s_hist[p][(unsigned)(key >> (p * dbits)) & ((1u << dbits) - 1u)], 1u);
 }
-__device__ __forceinline__ void hist_flush(unsigned (*s_hist)[RADIX_U32], unsigned* __restrict__ ghist) {
-    for (int e = threadIdx.x; e < RADIX_U32_PASSES * RADIX_U32; e += TPB) {
+__device__ __forceinline__ void hist_flush(unsigned (*s_hist)[RADIX], unsigned* __restrict__ ghist, int passes = RADIX_U32_PASSES) {
+    for (int e = threadIdx.x; e < passes * RADIX; e += TPB) {
         const unsigned v = (&s_hist[0][0])[e];
         if (v) atomicAdd(&ghist[e], v);
     }
 }
 
-// ---- the buffers of a sort ---------------------------------------------------------------------------------------------
+// ---- the buffers of a radix_sort_u32 -------------------------------------------------------------------------------------
 // Pairs go in through keys_a / vals_a and come out in keys_b / vals_b.  A stage that orders by a two-word key sorts twice
 // over the same buffers (least significant word first) and keeps one histogram per sort, both zeroed up front.
 struct SortBufs {
@@ -57,7 +81,7 @@ inline SortBufs sort_carve(Carver& cv, size_t n, int n_sorts) {             // n
     SortBufs s{};
     s.keys_a = cv.take<u64>(n); s.keys_b = cv.take<u64>(n);
     s.vals_a = cv.take<int>(n); s.vals_b = cv.take<int>(n);
-    for (int i = 0; i < n_sorts; ++i) s.ghist[i] = cv.take<unsigned>((size_t)RADIX_U32_PASSES * RADIX_U32);
+    for (int i = 0; i < n_sorts; ++i) s.ghist[i] = cv.take<unsigned>((size_t)RADIX_U32_PASSES * RADIX);
     s.scratch_bytes = radix_sort_u32_scratch_bytes((int)n);
     s.scratch = cv.take<char>(s.scratch_bytes);
     return s;
@@ -65,40 +89,11 @@ inline SortBufs sort_carve(Carver& cv, size_t n, int n_sorts) {             // n
 
 // the zeroing of one histogram, for the stage's fill_ranges call
 inline FillRange sort_hist_fill(const SortBufs& s, int which) {
-    return FillRange{s.ghist[which], (size_t)RADIX_U32_PASSES * RADIX_U32 * sizeof(unsigned), 0};
+    return FillRange{s.ghist[which], (size_t)RADIX_U32_PASSES * RADIX * sizeof(unsigned), 0};
 }
 
 inline int sort_run(const SortBufs& s, int which, int n, int32_t* status, hipStream_t st) {
     return radix_sort_u32(s.keys_a, s.keys_b, s.vals_a, s.vals_b, n, s.ghist[which], status, s.scratch, s.scratch_bytes, st);
-}
-
-// ---- stage timing ------------------------------------------------------------------------------------------------------
-// N events, destroyed on every path out of the scope that holds them
-template <int N>
-struct StageEvents {
-    hipEvent_t ev[N];
-    int n = 0;
-    StageEvents() = default;
-    StageEvents(const StageEvents&) = delete;
-    StageEvents& operator=(const StageEvents&) = delete;
-    ~StageEvents() { for (int i = 0; i < n; ++i) (void)hipEventDestroy(ev[i]); }
-    hipError_t make() {
-        for (; n < N; ++n) { const hipError_t e = hipEventCreate(&ev[n]); if (e != hipSuccess) return e; }
-        return hipSuccess;
-    }
-};
-
-// A *_timed entry point: body(ev) runs the stage and records ev[0..N-1] around its N - 1 steps; times_ms takes their
-// elapsed times after a synchronisation of the stream.
-template <int N, typename Body>
-int timed_stages(hipStream_t st, float* times_ms, Body body) {
-    StageEvents<N> evs;
-    PBN_HIP_CHECK(evs.make());
-    const int rc = body(evs.ev);
-    if (rc != PBN_OK) return rc;
-    PBN_HIP_CHECK(hipStreamSynchronize(st));
-    for (int i = 0; i + 1 < N; ++i) PBN_HIP_CHECK(hipEventElapsedTime(&times_ms[i], evs.ev[i], evs.ev[i + 1]));
-    return PBN_OK;
 }
 
 }  // namespace

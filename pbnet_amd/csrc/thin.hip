@@ -24,7 +24,7 @@
 // mu = sum m_i / n_valid; sigma = sqrt(sum (m_i - mu)^2 / n_valid), a second pass; keep_i = m_i <= mu + ratio * sigma.
 #include <cmath>
 
-#include "sort_dev.h"
+#include "scan_dev.h"
 
 namespace pbn {
 namespace {
@@ -40,7 +40,7 @@ __device__ __forceinline__ int in_rows(int j, int n) { return (unsigned)j < (uns
 __global__ __launch_bounds__(TPB) void k_thin_keys(const float* __restrict__ xyz, int n, const unsigned* __restrict__ box,
                                                    int* __restrict__ status, double pitch, u64* __restrict__ cellkey,
                                                    u64* __restrict__ keys, int* __restrict__ vals, unsigned* __restrict__ ghist) {
-    __shared__ unsigned s_hist[RADIX_U32_PASSES][RADIX_U32];
+    __shared__ unsigned s_hist[RADIX_U32_PASSES][RADIX];
     hist_clear(s_hist);
     __syncthreads();
     const bool bad = (*status & SCAN_NONFINITE) != 0;                        // the box kernel's word: final before this launch
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(TPB) void k_thin_keys(const float* __restrict__ xyz
 // the high words in the order of the first sort, that order as their values
 __global__ __launch_bounds__(TPB) void k_thin_high(const u64* __restrict__ cellkey, const int* __restrict__ order, int n,
                                                    u64* __restrict__ keys, int* __restrict__ vals, unsigned* __restrict__ ghist) {
-    __shared__ unsigned s_hist[RADIX_U32_PASSES][RADIX_U32];
+    __shared__ unsigned s_hist[RADIX_U32_PASSES][RADIX];
     hist_clear(s_hist);
     __syncthreads();
     for (int s = blockIdx.x * TPB + threadIdx.x; s < n; s += gridDim.x * TPB) {

@@ -20,7 +20,7 @@
 // Compaction.  The winners' instance ids are marked in a table over the id range by plain stores of 1, the table is
 // scanned, out_ins is renumbered in place and old_id[new] = old is written: ascending old-id order.  result[0] = status,
 // result[1] = I', one read-back.
-#include "sort_dev.h"
+#include "scan_dev.h"
 
 namespace pbn {
 namespace {
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(TPB) void k_vote_keys(const int* __restrict__ rows,
                                                    const int* __restrict__ ins, int n, int m, int n_classes,
                                                    int* __restrict__ status, u64* __restrict__ keys, int* __restrict__ vals,
                                                    unsigned* __restrict__ ghist) {
-    __shared__ unsigned s_hist[RADIX_U32_PASSES][RADIX_U32];
+    __shared__ unsigned s_hist[RADIX_U32_PASSES][RADIX];
     hist_clear(s_hist);
     __syncthreads();
     int bad = 0;
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(TPB) void k_vote_keys(const int* __restrict__ rows,
 // The second sort's pairs: (row + 1, vote key) in the order of the first sort, with the rows' digit histograms.
 __global__ __launch_bounds__(TPB) void k_vote_rows(const u64* __restrict__ skey, const int* __restrict__ srow, int n,
                                                    u64* __restrict__ keys, int* __restrict__ vals, unsigned* __restrict__ ghist) {
-    __shared__ unsigned s_hist[RADIX_U32_PASSES][RADIX_U32];
+    __shared__ unsigned s_hist[RADIX_U32_PASSES][RADIX];
     hist_clear(s_hist);
     __syncthreads();
     for (int s = blockIdx.x * TPB + threadIdx.x; s < n; s += gridDim.x * TPB) {

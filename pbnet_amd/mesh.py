@@ -50,7 +50,7 @@ from . import scene_io
 
 MESH_NORMALS, MESH_SEGMENT, MESH_SEGMENT_POINT = 0, 1, 2
 STAGES = ("incidence", "normals", "weights", "sort", "read-back", "host sweep", "relabel")
-# The status bits that every stage of the scan chain shares (csrc/sort_dev.h: SCAN_NONFINITE, SCAN_EXTENT, SCAN_SORT_SPIN):
+# The status bits that every stage of the scan chain shares (csrc/scan_dev.h: SCAN_NONFINITE, SCAN_EXTENT, SCAN_SORT_SPIN):
 # a coordinate is NaN or infinite; an axis spans 2^21 cells or more of thin_points' pitch; the device sort gave up.
 CLOUD_NONFINITE, CLOUD_EXTENT, CLOUD_SORT_SPIN = 1, 2, 8
 
@@ -219,8 +219,8 @@ def knn_edges(idx):
 
 
 ORIENT_STAGES = ("edge codes", "rounds", "tail")
-CLOUD_WALK_CAP = 16                                          # csrc/sort_dev.h: SCAN_WALK_CAP
-CLOUD_MAX_K = 32                                             # csrc/sort_dev.h: SCAN_MAX_K = pbn_cloud_max_k(), known without the library
+CLOUD_WALK_CAP = 16                                          # csrc/scan_dev.h: SCAN_WALK_CAP
+CLOUD_MAX_K = 32                                             # csrc/scan_dev.h: SCAN_MAX_K = pbn_cloud_max_k(), known without the library
 
 
 def orient_normals(nl, idx, times=None):

@@ -1,5 +1,5 @@
 """Plain numpy statements of the shared device primitives (csrc/common.hip fill_ranges, scan_exclusive_i32 and its chained
-form; csrc/pyramid.hip radix_sort_u32), all on the host in int64 / uint64.  Nothing here knows about tiles, windows or digits:
+form; csrc/sort.hip radix_sort_u32), all on the host in int64 / uint64.  Nothing here knows about tiles, windows or digits:
 that is tests/prims_mutants.py, which must agree with these on every designed case."""
 import numpy as np
 

@@ -7,7 +7,7 @@ form: rows beyond it are garbage), x_fastest, want_k5, design (what the builder 
 that raises AssertionError when the input no longer exercises what it was built for).  Rows are clustered: blobs of about 50 %
 occupancy, some pinned to the box corners so that the extent (and with it the digit plan of the sort) is designed.
 
-The tile constants of pyramid.hip the designs depend on are restated here; a precondition evaluated under other constants fails."""
+The tile constants of pyramid.hip and sort.hip the designs depend on are restated here; a precondition evaluated under other constants fails."""
 import functools
 
 import numpy as np
