@@ -1181,6 +1181,72 @@ int pbn_cloud_orient_timed(const float* nl, int n_points, const int32_t* idx, in
                            pbn_stream_t stream, float* times_ms);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Floor plane and upright frame (csrc/upright.hip): PCL / Open3D's segment_plane -- a RANSAC plane fit and a least-squares
+ * refit over the inliers -- and the minimal rotation that takes the plane's normal to +z.  tests/upright_ref.py restates
+ * this contract in numpy, stage by stage.  Every expression is one rounded IEEE operation per operator, in the order the
+ * brackets give, float32 or float64 as stated; nothing is fused.
+ *   Inputs   xyz float32[n,3] (device), 0 <= n <= 2^28; threshold t float32, finite, > 0; n_hyp H in
+ *            1..pbn_cloud_upright_max_hyp() (4096); seed uint64; up_hint double[3] on the HOST, a unit vector, or NULL;
+ *            cos_tilt double (read only with a hint); max_below int >= -1 (-1 = no floor rule).  Else PBN_ERR_ARG.
+ *   Draws    mix(z): z ^= z >> 30; z *= 0xbf58476d1ce4e5b9; z ^= z >> 27; z *= 0x94d049bb133111eb; z ^= z >> 31, all
+ *            modulo 2^64 (the splitmix64 finalizer).  Hypothesis h draws i_j = ((mix(seed + 3h + j) >> 32) * n) >> 32 for
+ *            j = 0, 1, 2 (the sum modulo 2^64, the product in 64 bits), and p_j = xyz[i_j] as float64.
+ *   Plane    float64: e1 = p1 - p0, e2 = p2 - p0; nx = e1y*e2z - e1z*e2y, ny = e1z*e2x - e1x*e2z, nz = e1x*e2y - e1y*e2x;
+ *            q = (nx*nx + ny*ny) + nz*nz.  The hypothesis is DEAD when n < 3, when two of its indices coincide, or when
+ *            q > 0 is false or q is not finite.  Otherwise r = sqrt(q), u = (nx/r, ny/r, nz/r),
+ *            d = -((ux*p0x + uy*p0y) + uz*p0z).  With a hint: g = (ux*hx + uy*hy) + uz*hz; when g < 0, u and d are
+ *            negated; when |g| < cos_tilt the hypothesis is dead.  (a, b, c, d) = float32(ux, uy, uz, d).
+ *   Score    for every live hypothesis and every point, float32: s = ((a*x + b*y) + c*z) + d; in[h] counts |s| <= t,
+ *            above[h] counts s > t, below[h] = n - in[h] - above[h].  A NaN or infinite coordinate anywhere in xyz sets
+ *            bit 1 of status (pbn_cloud_knn's bit); no output is to be trusted then.
+ *   Select   without a hint a hypothesis with below > above is negated: the two counts swap and (a, b, c, d) change
+ *            sign.  With max_below >= 0 a hypothesis with below > max_below is dead (nothing lies under a floor).  The
+ *            winner is the live hypothesis with the most inliers, ties to the lowest h; plane0 float32[4] is its plane.
+ *            Without a live hypothesis found = 0: xyz_out = xyz, floor = 0, height = 0, R = I, every other output 0.
+ *   Refit    over the points with |s| <= t under plane0: the count, the float64 centroid (three sums of the float64
+ *            coordinates, each divided by the count), then with dx = x - cx, ... the six sums of dx*dx, dx*dy, dx*dz,
+ *            dy*dy, dy*dz, dz*dz.  Every sum has pbn_cloud_outlier_mask's fixed shape over ALL n indices: blocks of 256
+ *            consecutive indices, the tree v[j] += v[j + s] for s = 128 .. 1, absent entries (no inlier, or past n) 0.0,
+ *            the block partials added in block order from 0.0.  The normal is pbn_cloud_normals' Jacobi eigenvector of the
+ *            symmetric matrix of the six sums: 10 fixed sweeps (01, 02, 12) from V = I, the column of the smallest
+ *            diagonal entry (ties to the lowest axis) divided by its length.  It is negated when
+ *            (nx*a0 + ny*b0) + nz*c0 < 0 with (a0, b0, c0) = float64(plane0); d = -((nx*cx + ny*cy) + nz*cz).
+ *            With fewer than 3 inliers plane = float64(plane0).  plane double[4]; moments double[10] = count, centroid,
+ *            the six sums.
+ *   R        with (a, b, c) = plane[0..2] and k = 1 + c: when k > 0,
+ *            R = [[1 - (a*a)/k, -((a*b)/k), -a], [-((a*b)/k), 1 - (b*b)/k, -b], [a, b, c]]; otherwise diag(1, -1, -1).
+ *            R double[9] row-major; a pure rotation, no shift.  R32 = float32(R), (a32, b32, c32, d32) = float32(plane).
+ *   Apply    per point, float32: xyz_out row r = (R32[r][0]*x + R32[r][1]*y) + R32[r][2]*z;
+ *            height = ((a32*x + b32*y) + c32*z) + d32; floor = |height| <= t.  xyz_out may be NULL (the fit alone).
+ *   info     int32[8]: found, winner h, its in, above, below (after the select stage), the refit's inliers, the
+ *            hypotheses alive at the arg-max, 0.
+ * Integer atomics only: two runs give the same bytes.  Argument checks run on the host before any launch; n_points == 0 is
+ * valid (found = 0) and launches nothing that indexes; only the _timed entry synchronises.
+ * ------------------------------------------------------------------------------------------------------------ */
+/* bytes of workspace for pbn_cloud_upright; 0 = sizes out of range */
+size_t pbn_cloud_upright_workspace_bytes(int n_points, int n_hyp);
+int pbn_cloud_upright_max_hyp(void);
+int pbn_cloud_upright(const float* xyz, int n_points, float threshold, int n_hyp, uint64_t seed, const double* up_hint,
+                      double cos_tilt, int max_below, float* xyz_out, uint8_t* floor, float* height, double* plane, float* plane0,
+                      double* R, double* moments, int32_t* info, int32_t* status, void* workspace, size_t workspace_bytes,
+                      pbn_stream_t stream);
+/* Measurement variant: HIP events around the stages, SYNCHRONISES; times_ms (host float[4]): hypotheses, score,
+ * select + refit, apply. */
+int pbn_cloud_upright_timed(const float* xyz, int n_points, float threshold, int n_hyp, uint64_t seed, const double* up_hint,
+                            double cos_tilt, int max_below, float* xyz_out, uint8_t* floor, float* height, double* plane,
+                            float* plane0, double* R, double* moments, int32_t* info, int32_t* status, void* workspace,
+                            size_t workspace_bytes, pbn_stream_t stream, float* times_ms);
+/* The launch geometry of the score kernel, for tests: points per workgroup (pbn_cloud_upright uses
+ * pbn_cloud_upright_chunk()), hypotheses per workgroup, and the entry with `chunk` in 1..2048 given.  The geometry changes
+ * the speed, never a byte of the result. */
+int pbn_cloud_upright_chunk(void);
+int pbn_cloud_upright_hyp_block(void);
+int pbn_cloud_upright_chunked(const float* xyz, int n_points, float threshold, int n_hyp, uint64_t seed, const double* up_hint,
+                              double cos_tilt, int max_below, int chunk, float* xyz_out, uint8_t* floor, float* height,
+                              double* plane, float* plane0, double* R, double* moments, int32_t* info, int32_t* status,
+                              void* workspace, size_t workspace_bytes, pbn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Annotated raw scans (csrc/vote.hip): the raw points' labels voted down to the kept points.  Integers only: two runs
  * give the same bytes, and tests/vote_ref.py restates the contract in numpy.  Argument checks run on the host before any
  * launch (n_classes in 1..1023, n_raw and m in 0..2^28, else PBN_ERR_ARG); nothing synchronises.

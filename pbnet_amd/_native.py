@@ -317,6 +317,19 @@ SIGNATURES = {
     "pbn_cloud_orient": (c_int, [c_f32p, c_int, c_i32p, c_int, c_f32p, c_vp, c_i32p, c_i32p, c_i32p, c_vp, c_size, c_vp]),
     "pbn_cloud_orient_timed": (c_int, [c_f32p, c_int, c_i32p, c_int, c_f32p, c_vp, c_i32p, c_i32p, c_i32p, c_vp, c_size, c_vp,
                                        ctypes.POINTER(ctypes.c_float)]),
+    "pbn_cloud_upright_workspace_bytes": (c_size, [c_int, c_int]),
+    "pbn_cloud_upright_max_hyp": (c_int, []),
+    "pbn_cloud_upright_chunk": (c_int, []),
+    "pbn_cloud_upright_hyp_block": (c_int, []),
+    "pbn_cloud_upright": (c_int, [c_f32p, c_int, c_float, c_int, ctypes.c_uint64, ctypes.POINTER(ctypes.c_double),
+                                  ctypes.c_double, c_int, c_f32p, c_vp, c_f32p, c_vp, c_f32p, c_vp, c_vp, c_i32p, c_i32p, c_vp,
+                                  c_size, c_vp]),
+    "pbn_cloud_upright_timed": (c_int, [c_f32p, c_int, c_float, c_int, ctypes.c_uint64, ctypes.POINTER(ctypes.c_double),
+                                        ctypes.c_double, c_int, c_f32p, c_vp, c_f32p, c_vp, c_f32p, c_vp, c_vp, c_i32p, c_i32p,
+                                        c_vp, c_size, c_vp, ctypes.POINTER(ctypes.c_float)]),
+    "pbn_cloud_upright_chunked": (c_int, [c_f32p, c_int, c_float, c_int, ctypes.c_uint64, ctypes.POINTER(ctypes.c_double),
+                                          ctypes.c_double, c_int, c_int, c_f32p, c_vp, c_f32p, c_vp, c_f32p, c_vp, c_vp, c_i32p,
+                                          c_i32p, c_vp, c_size, c_vp]),
     "pbn_cloud_vote_workspace_bytes": (c_size, [c_int, c_int]),
     "pbn_cloud_vote_labels": (c_int, [c_i32p, c_i32p, c_i32p, c_int, c_int, c_int, c_vp, c_vp, c_i32p, c_i32p, c_i32p, c_vp, c_vp,
                                       c_size, c_vp]),

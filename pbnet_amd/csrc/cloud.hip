@@ -66,7 +66,6 @@ namespace {
 constexpr int CLOUD_AXIS_CELLS = 1024;
 constexpr int CLOUD_EVENTS = 5;                   // around: box + grid | keys + sort | table | search
 constexpr u64 CLOUD_PAD_KEY = ((u64)0x7f800000u << 32) | 0xffffffffu;   // d2 = +inf, idx = -1: after every real candidate
-constexpr int JACOBI_SWEEPS = 10;
 constexpr double BOUND_SLACK = 1.0 / 274877906944.0;          // 2^-38 (see the header)
 constexpr double BOUND_SCALE = 1.0 - 1.0 / 1099511627776.0;   // 1 - 2^-40
 
@@ -398,25 +397,6 @@ __global__ __launch_bounds__(TPB) void k_radius_gather(const int* __restrict__ i
 }
 
 // ---- normals -----------------------------------------------------------------------------------------------------------
-// one Jacobi rotation of the symmetric 3x3 (app, aqq, apq; apr, aqr the couplings to the third axis) and of the columns
-// vp, vq of the eigenvector matrix (Numerical Recipes' jacobi, t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)))
-__device__ __forceinline__ void jacobi_rot(double& app, double& aqq, double& apq, double& apr, double& aqr, double& vp0,
-                                           double& vp1, double& vp2, double& vq0, double& vq1, double& vq2) {
-    if (apq == 0.0) return;
-    const double theta = (aqq - app) / (2.0 * apq);
-    const double tt = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));   // an infinite theta gives 0
-    const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-    app = app - tt * apq;
-    aqq = aqq + tt * apq;
-    apq = 0.0;
-    const double pr = c * apr - s * aqr, qr = s * apr + c * aqr;
-    apr = pr; aqr = qr;
-    double a, b;
-    a = c * vp0 - s * vq0; b = s * vp0 + c * vq0; vp0 = a; vq0 = b;
-    a = c * vp1 - s * vq1; b = s * vp1 + c * vq1; vp1 = a; vq1 = b;
-    a = c * vp2 - s * vq2; b = s * vp2 + c * vq2; vp2 = a; vq2 = b;
-}
-
 // float64 throughout: 4 waves per SIMD leave the 128 VGPRs the rotations want (no scratch)
 __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_cloud_normals(const float* __restrict__ xyz, int n, const int* __restrict__ idx,
                                                        int k, const float* __restrict__ viewpoint, float* __restrict__ nl) {
@@ -444,21 +424,8 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 4))) voi
             a00 = a00 + dx * dx; a01 = a01 + dx * dy; a02 = a02 + dx * dz;
             a11 = a11 + dy * dy; a12 = a12 + dy * dz; a22 = a22 + dz * dz;
         }
-        double v00 = 1.0, v10 = 0.0, v20 = 0.0, v01 = 0.0, v11 = 1.0, v21 = 0.0, v02 = 0.0, v12 = 0.0, v22 = 1.0;   // v[row][col]
-        for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
-            jacobi_rot(a00, a11, a01, a02, a12, v00, v10, v20, v01, v11, v21);
-            jacobi_rot(a00, a22, a02, a01, a12, v00, v10, v20, v02, v12, v22);
-            jacobi_rot(a11, a22, a12, a01, a02, v01, v11, v21, v02, v12, v22);
-        }
-        // the column of the smallest eigenvalue (ties keep the lowest axis), blended with exact 0 / 1 weights: a chain of
-        // selects over nine doubles is turned into an indexed table in scratch
-        const int col = a22 < fmin(a00, a11) ? 2 : a11 < a00 ? 1 : 0;
-        const double w0 = col == 0 ? 1.0 : 0.0, w1 = col == 1 ? 1.0 : 0.0, w2 = col == 2 ? 1.0 : 0.0;
-        double nx = (w0 * v00 + w1 * v01) + w2 * v02, ny = (w0 * v10 + w1 * v11) + w2 * v12,
-               nz = (w0 * v20 + w1 * v21) + w2 * v22;
-        const double len = sqrt((nx * nx + ny * ny) + nz * nz);
-        if (len > 0.0 && __builtin_isfinite(len)) { nx = nx / len; ny = ny / len; nz = nz / len; }
-        else { nx = 1.0; ny = 0.0; nz = 0.0; }                               // unreachable for finite input: stay a unit vector
+        double nx, ny, nz;
+        jacobi_smallest(a00, a01, a02, a11, a12, a22, nx, ny, nz);     // scan_dev.h
         const double dot = (nx * ((double)viewpoint[0] - px) + ny * ((double)viewpoint[1] - py)) + nz * ((double)viewpoint[2] - pz);
         if (dot < 0.0) { nx = -nx; ny = -ny; nz = -nz; }
         nl[3 * (size_t)i] = (float)nx; nl[3 * (size_t)i + 1] = (float)ny; nl[3 * (size_t)i + 2] = (float)nz;

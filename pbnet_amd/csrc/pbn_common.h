@@ -67,15 +67,16 @@ __device__ __forceinline__ float okey32_val(unsigned k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
-// 64-bit finalizer (splitmix64) -> table slot
-__device__ __forceinline__ uint32_t hash64(uint64_t k) {
+// 64-bit finalizer (splitmix64): all 64 bits (upright.hip's generator), and its low word -> table slot
+__device__ __forceinline__ uint64_t mix64(uint64_t k) {
     k ^= k >> 30;
     k *= 0xbf58476d1ce4e5b9ULL;
     k ^= k >> 27;
     k *= 0x94d049bb133111ebULL;
     k ^= k >> 31;
-    return (uint32_t)k;
+    return k;
 }
+__device__ __forceinline__ uint32_t hash64(uint64_t k) { return (uint32_t)mix64(k); }
 
 // ---- device-wide exclusive scan (int32), three launches; tmp must hold scan_tmp_ints(n) = cdiv(n, SCAN_TILE) + 2 ints:
 // one sum per tile, then sums[nb] = the total (k_scan_sums writes it), then one spare -------------------------------------

@@ -197,18 +197,7 @@ int thin_args(const float* xyz, const float* rgb, int n, double pitch, const flo
 }
 
 // ---- outliers ----------------------------------------------------------------------------------------------------------
-constexpr int SUM_BLOCK = 256;                     // the contract's block of consecutive indices
-
-// v[0] = the contract's tree over the block's 256 entries; every thread of the block calls it
-__device__ __forceinline__ void tree_sum(double* v) {
-    __syncthreads();
-#pragma unroll
-    for (int s = SUM_BLOCK / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) v[threadIdx.x] = v[threadIdx.x] + v[threadIdx.x + s];
-        __syncthreads();
-    }
-}
-
+// SUM_BLOCK, tree_sum, ordered_total: scan_dev.h
 __global__ __launch_bounds__(SUM_BLOCK) void k_outlier_mean(const float* __restrict__ d2, int n, int k, double* __restrict__ m,
                                                             unsigned char* __restrict__ valid, double* __restrict__ psum,
                                                             int* __restrict__ pcnt) {
@@ -252,19 +241,8 @@ __global__ __launch_bounds__(SUM_BLOCK) void k_outlier_total(const double* __res
                                                              int pass, double* __restrict__ stats) {
     __shared__ double s_v[SUM_BLOCK];
     __shared__ int s_c[SUM_BLOCK];
-    double sum = 0.0;
-    long long cnt = 0;
-    for (int base = 0; base < nb; base += SUM_BLOCK) {
-        const int b = base + (int)threadIdx.x;
-        s_v[threadIdx.x] = b < nb ? psum[b] : 0.0;
-        s_c[threadIdx.x] = (b < nb && pass == 0) ? pcnt[b] : 0;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const int here = min(SUM_BLOCK, nb - base);
-            for (int j = 0; j < here; ++j) { sum = sum + s_v[j]; cnt += s_c[j]; }
-        }
-        __syncthreads();
-    }
+    const double sum = ordered_total(psum, nb, s_v);
+    const long long cnt = pass == 0 ? ordered_count(pcnt, nb, s_c) : 0;
     if (threadIdx.x != 0) return;
     if (pass == 0) {
         stats[0] = sum / (double)cnt;                                        // no valid row: 0 / 0 = NaN, and nothing is kept

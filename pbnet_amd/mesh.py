@@ -15,6 +15,9 @@ knn_edges        the graph as segment_point's E x 2 edges
 orient_normals   point_normals' signs made consistent over the graph (csrc/orient.hip), bit for bit tests/orient_ref.py
 read_ply_points  the vertex-only counterpart of read_ply
 decode_points    decode_mesh without faces: xyz, rgb, nl, sup
+fit_plane        the floor plane of a scan (csrc/upright.hip): RANSAC scored on the device and a float64 refit, bit for bit
+                 tests/upright_ref.py
+upright          fit_plane and the scan rotated so that the plane's normal is +z
 
 Raw sensor scans (csrc/thin.hip): to the network's pitch and back.
 thin_points      one float64 centroid per occupied cell of a grid, bit for bit tests/thin_ref.py
@@ -443,6 +446,134 @@ def radius_raw_index(inverse, keep, xyz, radius, cell=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------ floor plane, upright frame
+UPRIGHT_STAGES = ("hypotheses", "score", "select + refit", "apply")
+UPRIGHT_MAX_HYP = 4096                                       # csrc/upright.hip: UPR_MAX_HYP = pbn_cloud_upright_max_hyp()
+UPRIGHT_KEYS = ("threshold", "hypotheses", "seed", "up_hint", "max_tilt", "below_frac")
+
+
+def _upright_args(what, xyz, threshold, hypotheses, seed, up_hint, max_tilt, below_frac):
+    """fit_plane's checks, values and dtypes before the device or the library: (float32 threshold, H, seed, the float64
+    unit hint as a ctypes double[3] or None, cos(max_tilt), max_below)."""
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)):
+        raise TypeError("%s: threshold must be a number, got %r" % (what, threshold))
+    with np.errstate(over="ignore"):
+        tf = np.float32(threshold)
+    if not (np.isfinite(tf) and tf > 0):
+        raise ValueError("%s: threshold must be positive and finite as a float32, got %r" % (what, threshold))
+    if isinstance(hypotheses, bool) or not isinstance(hypotheses, (int, np.integer)) or not 1 <= int(hypotheses) <= UPRIGHT_MAX_HYP:
+        raise ValueError("%s: hypotheses must be an int in 1..%d, got %r" % (what, UPRIGHT_MAX_HYP, hypotheses))
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < (1 << 64):
+        raise ValueError("%s: seed must be an int in 0..2^64 - 1, got %r" % (what, seed))
+    hint = None
+    if up_hint is not None:
+        try:
+            h = np.asarray(up_hint.detach().cpu().numpy() if torch.is_tensor(up_hint) else up_hint, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            raise TypeError("%s: up_hint must be three numbers, got %r" % (what, up_hint)) from None
+        if h.shape != (3,) or not np.all(np.isfinite(h)):
+            raise ValueError("%s: up_hint must be three finite numbers, got %r" % (what, up_hint))
+        length = np.sqrt((h[0] * h[0] + h[1] * h[1]) + h[2] * h[2])
+        if not (length > 0 and np.isfinite(length)):
+            raise ValueError("%s: up_hint must have a non-zero length, got %r" % (what, up_hint))
+        hint = (ctypes.c_double * 3)(*(float(v) for v in h / length))
+    if isinstance(max_tilt, bool) or not isinstance(max_tilt, (int, float, np.integer, np.floating)):
+        raise TypeError("%s: max_tilt must be a number of degrees, got %r" % (what, max_tilt))
+    if not 0.0 < float(max_tilt) <= 90.0:
+        raise ValueError("%s: max_tilt must lie in (0, 90] degrees, got %r" % (what, max_tilt))
+    if below_frac is not None:
+        if isinstance(below_frac, bool) or not isinstance(below_frac, (int, float, np.integer, np.floating)):
+            raise TypeError("%s: below_frac must be a number or None, got %r" % (what, below_frac))
+        if not 0.0 <= float(below_frac) <= 1.0:
+            raise ValueError("%s: below_frac must lie in [0, 1] or be None, got %r" % (what, below_frac))
+    if not torch.is_tensor(xyz) or xyz.dtype != torch.float32 or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise TypeError("xyz must be a float32 [n, 3] tensor, got %s" % (
+            "%s %s" % (xyz.dtype, tuple(xyz.shape)) if torch.is_tensor(xyz) else type(xyz).__name__))
+    max_below = -1 if below_frac is None else int(float(below_frac) * int(xyz.shape[0]))
+    return float(tf), int(hypotheses), int(seed), hint, float(np.cos(np.deg2rad(np.float64(max_tilt)))), max_below
+
+
+def _upright(what, rotate, xyz, threshold, hypotheses, seed, up_hint, max_tilt, below_frac, times, chunk=None):
+    tf, n_hyp, seed, hint, cos_tilt, max_below = _upright_args(what, xyz, threshold, hypotheses, seed, up_hint, max_tilt,
+                                                               below_frac)
+    xyz = _check_xyz("xyz", xyz)
+    n, dev = int(xyz.shape[0]), xyz.device
+    ws = _scan_workspace(N.lib().pbn_cloud_upright_workspace_bytes(n, n_hyp), dev, "%d points" % n)
+    out = torch.empty(n, 3, dtype=torch.float32, device=dev) if rotate else None
+    floor = torch.empty(n, dtype=torch.bool, device=dev)
+    height = torch.empty(n, dtype=torch.float32, device=dev)
+    f64 = torch.empty(4 + 9 + 10, dtype=torch.float64, device=dev)       # plane, R, moments
+    plane, R, moments = f64[:4], f64[4:13], f64[13:]
+    plane0 = torch.empty(4, dtype=torch.float32, device=dev)
+    res = torch.zeros(9, dtype=torch.int32, device=dev)                  # info[8], status
+    head = (N.ptr(xyz), n, tf, n_hyp, seed, hint, cos_tilt, max_below)
+    tail = (N.ptr(out), N.ptr(floor), N.ptr(height), N.ptr(plane), N.ptr(plane0), N.ptr(R), N.ptr(moments), N.ptr(res),
+            N.ptr(res[8:]), N.ptr(ws), ws.numel(), N.current_stream())
+    if chunk is None:
+        _staged_call("cloud_upright", head + tail, UPRIGHT_STAGES, times)
+    else:                                                    # the score kernel's launch geometry, for the tests
+        N.check(N.lib().pbn_cloud_upright_chunked(*head, int(chunk), *tail), "pbn_cloud_upright_chunked")
+    host = res.tolist()                                      # the one read-back
+    if host[8] & CLOUD_NONFINITE:
+        raise ValueError("%s: a coordinate is NaN or infinite" % what)
+    if host[8]:
+        raise RuntimeError("%s: status %d" % (what, host[8]))
+    r = {"plane": plane, "plane0": plane0, "floor": floor, "height": height, "moments": moments, "info": res[:8],
+         "found": bool(host[0]), "hypothesis": host[1], "inliers": host[2]}
+    if rotate:
+        r.update(R=R.reshape(3, 3), xyz=out)
+    return r
+
+
+def fit_plane(xyz, threshold, hypotheses=1024, seed=0, up_hint=None, max_tilt=30.0, below_frac=0.01, times=None):
+    """The floor plane of a scan (csrc/upright.hip; PCL / Open3D's segment_plane): `hypotheses` planes through three
+    points each, drawn from a splitmix64 stream of `seed`, every one scored against every point in float32 -- inliers within
+    `threshold`, points above, points below -- and the winner refitted by least squares over its inliers in float64.
+    include/pbnet_hip.h ("Floor plane and upright frame") states every operation; tests/upright_ref.py restates it in numpy.
+
+    `up_hint` (three numbers, any length; None = unknown) is roughly where up is in the scan's frame: a hypothesis is turned
+    to agree with it and dropped when it leans more than `max_tilt` degrees away.  Without a hint a plane is turned so
+    that more points lie above it than below.  `below_frac` is the floor rule: a plane with more than
+    int(below_frac * N) points below it is dropped -- nothing lies under a floor -- which rejects the ceiling under a hint
+    and table tops always; None turns it off, which is plain segment_plane: the largest plane, whatever it is.
+
+    Returns a dict on the device: plane f64 [4] (unit normal and offset after the refit), plane0 f32 [4] (the winning
+    hypothesis), floor bool [N] and height f32 [N] (|height| <= threshold, the signed distance from the refit plane),
+    moments f64 [10] (inliers, centroid, six centred second-moment sums), info int32 [8] (found, winner, its in / above /
+    below, refit inliers, hypotheses alive at the end, 0), and the Python values found, hypothesis and inliers.  Without a
+    live hypothesis found is False and everything else is zero.  One read-back; integer atomics only, so two runs give the
+    same bytes.  A non-finite coordinate raises ValueError.  `times` (a dict) takes the stage times of the measurement
+    entry, which synchronises."""
+    return _upright("fit_plane", False, xyz, threshold, hypotheses, seed, up_hint, max_tilt, below_frac, times)
+
+
+def upright(xyz, threshold, hypotheses=1024, seed=0, up_hint=None, max_tilt=30.0, below_frac=0.01, times=None):
+    """fit_plane, and the scan turned upright by the minimal rotation that takes the plane's normal to +z: the same dict
+    plus R f64 [3, 3] and xyz f32 [N, 3] = float32(R) . p, on the device.  R is a pure rotation with no shift, so camera
+    poses can take it as well; the floor ends at z = -plane[3].  Without a plane (found False) R is the identity and xyz
+    the input's bytes."""
+    return _upright("upright", True, xyz, threshold, hypotheses, seed, up_hint, max_tilt, below_frac, times)
+
+
+def _upright_option(upright, pitch):
+    """decode_points' `upright` as fit_plane's keyword arguments, or None; checked before anything is uploaded."""
+    if upright is None or upright is False:
+        return None
+    if upright is True:
+        upright = {}
+    if not isinstance(upright, dict):
+        raise TypeError("decode_points: upright must be None, True or a dict of fit_plane's arguments, got %r" % (upright,))
+    unknown = sorted(set(upright) - set(UPRIGHT_KEYS))
+    if unknown:
+        raise TypeError("decode_points: upright has no argument %s (it takes %s)" % (", ".join(map(repr, unknown)),
+                                                                                    ", ".join(UPRIGHT_KEYS)))
+    kw = dict(threshold=pitch if pitch is not None else 0.02, hypotheses=1024, seed=0, up_hint=None, max_tilt=30.0,
+              below_frac=0.01)
+    kw.update(upright)
+    _upright_args("decode_points: upright", torch.empty(0, 3), **kw)
+    return kw
+
+
 def carry_labels(labels, raw_index, fill=-1):
     """The gather that goes with raw_index: out[i] = labels[raw_index[i]], `fill` where raw_index[i] is -1.  `labels` is
     any integer tensor whose first axis is the kept points; the result has raw_index's length on that axis."""
@@ -678,12 +809,14 @@ def decode_mesh(src, device="cuda", kThresh=0.01, segMinVerts=20):
             "face": face_d, "sup": sup}
 
 
-def _kept_points(xyz, colours, dev, k, pitch, outlier_ratio, outlier_radius=None, outlier_min_pts=None):
+def _kept_points(xyz, colours, dev, k, pitch, outlier_ratio, outlier_radius=None, outlier_min_pts=None, upright_kw=None):
     """decode_points' front for a raw scan: upload, thin_points (pitch), then knn_graph -> outlier_mask -> raw_index
     (outlier_ratio) or radius_outlier_mask -> radius_raw_index (outlier_radius, outlier_min_pts: no graph over the
     unfiltered points), and the compaction.  Returns the kept points' (xyz, colours) as host float32 arrays --
     centre_and_scale is a host numpy expression, so the kept M x 6 floats make one extra round trip -- and raw_index /
-    count on the device."""
+    count on the device, then upright's result or None.  With `upright_kw` (fit_plane's keyword arguments) the kept points
+    are turned upright while they are still on the device: the returned xyz is in the upright frame, and the result's
+    "kept_xyz" holds the kept points in the sensor's frame."""
     xyz_d = torch.from_numpy(np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)).to(dev)
     col_d = torch.from_numpy(np.ascontiguousarray(colours, np.float32).reshape(-1, 3)).to(dev)
     n_raw = int(xyz_d.shape[0])
@@ -702,16 +835,24 @@ def _kept_points(xyz, colours, dev, k, pitch, outlier_ratio, outlier_radius=None
         keep = radius_outlier_mask(xyz_d, outlier_radius, outlier_min_pts)
         inverse = radius_raw_index(inverse, keep, xyz_d, outlier_radius)
         xyz_d, col_d, count = xyz_d[keep], col_d[keep], count[keep]
-    return xyz_d.cpu().numpy(), col_d.cpu().numpy(), inverse, count
+    up = None
+    if upright_kw is not None:
+        up = upright(xyz_d, **upright_kw)
+        if not up["found"]:
+            raise ValueError("decode_points: no floor plane found among %d points (%d hypotheses, %d alive at the end); "
+                             "check threshold, up_hint and below_frac" % (int(xyz_d.shape[0]), upright_kw["hypotheses"],
+                                                                          int(up["info"][6])))
+        up["kept_xyz"], xyz_d = xyz_d, up["xyz"]
+    return xyz_d.cpu().numpy(), col_d.cpu().numpy(), inverse, count, up
 
 
 def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpoint=None, return_graph=False, pitch=None,
                   outlier_ratio=None, return_kept=False, sem_label=None, ins_label=None, n_classes=20, outlier_radius=None,
-                  outlier_min_pts=None, orient=None):
+                  outlier_min_pts=None, orient=None, upright=None):
     """decode_mesh for a scan without faces: `src` is a vertex-only `.ply` path or (xyz [V,3], colours [V,3] 0..255).
     centre_and_scale -> knn_graph -> point_normals -> knn_edges -> segment_point.  Returns xyz (mean-centred), rgb, nl and
     sup on `device` -- what SceneCache and save_decoded take (no `face`) -- plus idx and d2 when return_graph is set.
-    `viewpoint` is given in the centred frame; None is the cloud's mean.
+    `viewpoint` is given in the final frame (upright when `upright` is set, and centred); None is the cloud's mean.
 
     `orient="graph"` makes the normals' signs consistent over the kNN graph before the segmentation (orient_normals between
     point_normals and segment_point): towards one viewpoint, a surface seen edge-on gets its signs from noise, and
@@ -729,6 +870,16 @@ def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpo
     filter, for flying pixels: a point is kept when at least outlier_min_pts other points lie within outlier_radius
     (radius_outlier_mask), and a dropped point is spoken for by its nearest KEPT point within that radius
     (radius_raw_index).  No kNN graph is built over the unfiltered points; everything behind the front is the same.
+
+    `upright` turns a scan that arrives in its sensor's frame (y down and z forward, or anything else) so that its floor is
+    level and z is up, the one "up" the network's weights know: True, or a dict of fit_plane's keyword arguments
+    (threshold defaults to `pitch` when given, else 0.02).  It takes effect on the kept points -- after thin_points and the
+    outlier filter, directly after the upload without them -- and before the centring; everything behind it sees the
+    upright cloud.  The result gains R (f64 [3, 3]), plane (f64 [4]), floor (bool [M]) and height (f32 [M]) of the kept
+    points; kept_xyz (return_kept) stays in the sensor's frame, and R maps it.  Without a hint the largest one-sided plane
+    wins, which in a room with a long wall may be that wall: a caller whose sensor knows roughly where up is should pass
+    up_hint.  No plane at all raises ValueError("decode_points: no floor plane found ...").  None is the decode of
+    before, byte for byte.
 
     An annotated scan: `sem_label` and `ins_label` (both or neither; one per raw point; integer arrays or tensors, or the
     float64 arrays the reference's `.npy` files hold; negative = unannotated) are voted down to the kept points over the
@@ -748,17 +899,21 @@ def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpo
         raise ValueError("decode_points: give both outlier_radius and outlier_min_pts, or neither")
     if outlier_radius is not None and outlier_ratio is not None:
         raise ValueError("decode_points: outlier_radius / outlier_min_pts and outlier_ratio are two filters, give one")
+    upright_kw = _upright_option(upright, pitch)
     dev = torch.device(device)
     labels = None
     if sem_label is not None:
         n_raw = int(np.asarray(xyz).reshape(-1, 3).shape[0])
         labels = [_raw_labels(name, v, n_raw) for name, v in (("sem_label", sem_label), ("ins_label", ins_label))]
         labels = [torch.from_numpy(a).to(dev) for a in labels]
-    raw = None
+    raw, up = None, None
     if pitch is not None or outlier_ratio is not None or outlier_radius is not None:
-        xyz, colours, *raw = _kept_points(xyz, colours, dev, k, pitch, outlier_ratio, outlier_radius, outlier_min_pts)
+        xyz, colours, *raw, up = _kept_points(xyz, colours, dev, k, pitch, outlier_ratio, outlier_radius, outlier_min_pts,
+                                              upright_kw)
     elif return_kept:
         raise ValueError("decode_points: return_kept needs pitch, outlier_ratio or outlier_radius")
+    elif upright_kw is not None:
+        xyz, colours, _, _, up = _kept_points(xyz, colours, dev, k, None, None, upright_kw=upright_kw)
     xyz_c, rgb = centre_and_scale(xyz, colours)
     xyz_d = torch.from_numpy(np.ascontiguousarray(xyz_c, np.float32)).to(dev)
     idx, d2 = knn_graph(xyz_d, k=k)
@@ -770,12 +925,15 @@ def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpo
     out = {"xyz": xyz_d, "rgb": torch.from_numpy(np.ascontiguousarray(rgb, np.float32)).to(dev), "nl": nl, "sup": sup}
     if oriented is not None:
         out.update(flipped=oriented["flipped"], tree=oriented["tree"])
+    if up is not None:
+        out.update(R=up["R"], plane=up["plane"], floor=up["floor"], height=up["height"])
     if return_graph:
         out.update(idx=idx, d2=d2)
     if raw is not None:
         out.update(raw_index=raw[0], count=raw[1])
         if return_kept:
-            out.update(kept_xyz=torch.from_numpy(xyz).to(dev), kept_rgb=torch.from_numpy(colours).to(dev))
+            out.update(kept_xyz=up["kept_xyz"] if up is not None else torch.from_numpy(xyz).to(dev),
+                       kept_rgb=torch.from_numpy(colours).to(dev))
     if labels is not None:
         m = int(xyz_d.shape[0])
         rows = raw[0] if raw is not None else torch.arange(m, dtype=torch.int32, device=dev)
@@ -786,14 +944,16 @@ def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpo
     return out
 
 
-SCENE_BOOKKEEPING = ("votes", "members", "ins_old_id", "raw_index", "count", "flipped", "tree")   # of a decode, not of a scene on disk
+SCENE_BOOKKEEPING = ("votes", "members", "ins_old_id", "raw_index", "count", "flipped", "tree",
+                     "R", "plane", "floor", "height")        # of a decode, not of a scene on disk
 
 
 def save_decoded(npy_dir, scene, decoded, sem_label=None, ins_label=None):
     """Write a decode_mesh result under the reference's names (`<scene>_xyz.npy` ...).  Without labels (a test-split scene
     or a user's own room) only xyz, rgb, nl, face and sup are written, as decode_scannet.py f_test does.  A decode_points
     result that carries its own sem_label / ins_label (an annotated scan) is written with them when none are passed; the
-    bookkeeping arrays of a raw scan (votes, members, ins_old_id, raw_index, count, flipped, tree) are never scene files."""
+    bookkeeping arrays of a raw scan (votes, members, ins_old_id, raw_index, count, flipped, tree, R, plane, floor, height)
+    are never scene files."""
     arrays = {k: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in decoded.items()
               if k not in SCENE_BOOKKEEPING}
     if (sem_label is None) != (ins_label is None):
