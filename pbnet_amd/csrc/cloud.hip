@@ -39,17 +39,19 @@
 // has a COMPUTED d2 >= bound2 = fl(fl(D) * fl(D)), D the smallest over the block's inner faces.  A query stops when its
 // k-th d2 is STRICTLY below bound2 (strictly: an unscanned point at the same d2 with a smaller index would belong in the
 // row; an unfilled row has k-th d2 = +inf and never passes), or when the block covers the grid, which happens at
-// r <= 1023 whatever the data: the loop cannot spin.  Neither condition mentions h beyond the bound's value.
+// r <= 1023 whatever the data: the loop cannot spin.  Neither condition mentions h beyond the bound's value.  The loop is
+// shell_walk below, the only one in this file: the search and both fixed-radius kernels differ in what they do with a
+// point (visit) and in when they have enough (enough, r2), never in which cells they scan or in the bound.
 //
 // Normals: one lane per point, float64, no atomics.  S = the point, then its valid neighbours in rank order; mean, then
 // the six covariance sums, in that order; the eigenvector of the smallest eigenvalue by a FIXED number of cyclic Jacobi
 // sweeps (no data-dependent loop); flipped towards the viewpoint; rounded to float32.  |S| < 3 gives the zero vector.
 //
 // Fixed radius (pbn_cloud_radius_count / pbn_cloud_radius_raw_index): the same grid front (cloud_front below, which
-// pbn_cloud_knn runs too) with a cell a hair above the radius, and the same shell walk without a k-th neighbour.
+// pbn_cloud_knn runs too) with a cell a hair above the radius, and shell_walk with a radius in place of a k-th neighbour.
 // rf = the caller's float32 radius, r2 = fl(rf * rf), j is a neighbour of i when j != i and d2(i, j) <= r2.  By the
-// argument above every unscanned point has a computed d2 >= bound2, so a query stops when bound2 is STRICTLY above r2
-// (an unscanned point exactly at r2 is a neighbour), when the block covers the grid, or when it has what it came for:
+// argument above every unscanned point has a computed d2 >= bound2, so shell_walk stops a query when bound2 is STRICTLY
+// above r2 (an unscanned point exactly at r2 is a neighbour), when the block covers the grid, or when it has what it came for:
 //   count   count[i] = min(neighbours, cap), in a register; the lane stops at cap;
 //   route   for a dropped point the kept point with the smallest (d2 bits, j) within r2, one 64-bit key in registers; it
 //           also stops once its best d2 is strictly below bound2, as a search for k = 1 would.  Kept lanes write their own
@@ -235,75 +237,12 @@ __device__ __forceinline__ bool block_bound2(const CloudQuery& c, int r, float& 
     return inner;
 }
 
-__global__ __launch_bounds__(TPB) void k_cloud_search(const float4* __restrict__ pts, const u64* __restrict__ keys,
-                                                      const int2* __restrict__ table, const CloudGrid* __restrict__ g,
-                                                      const int* __restrict__ status, int n, int k,
-                                                      int* __restrict__ idx, float* __restrict__ d2_out) {
-    extern __shared__ __attribute__((aligned(16))) u64 s_best[];            // [k][TPB], lane-minor
-    if (*status != 0) return;                                                // non-finite input or a failed sort: no row is written
-    const int tid = threadIdx.x;
-    const int t = blockIdx.x * TPB + tid;
-    if (t >= n) return;                                                      // no barrier below: every lane owns its column
-    u64* __restrict__ best = s_best + tid;
-    for (int r = 0; r < k; ++r) best[r * TPB] = CLOUD_PAD_KEY;
-    u64 worst = CLOUD_PAD_KEY;
-
-    const float4 q = pts[t];
-    const int qi = __float_as_int(q.w);
-    const CloudQuery c0 = cloud_query(q, (unsigned)keys[t], g);
-    const int cx = c0.cx, cy = c0.cy, cz = c0.cz, d0 = c0.d0, d1 = c0.d1, d2 = c0.d2;
-
-    for (int r = 0; r < CLOUD_AXIS_CELLS; ++r) {
-        const int xlo = max(cx - r, 0), xhi = min(cx + r, d0 - 1);
-        const int ylo = max(cy - r, 0), yhi = min(cy + r, d1 - 1);
-        const int zlo = max(cz - r, 0), zhi = min(cz + r, d2 - 1);
-        for (int z = zlo; z <= zhi; ++z) {
-            for (int y = ylo; y <= yhi; ++y) {
-                // a row on the shell's y / z faces is scanned whole, an inner row only at its two ends
-                const bool full = (z - cz == r) || (cz - z == r) || (y - cy == r) || (cy - y == r);
-                int x = full ? xlo : (cx - r >= 0 ? cx - r : cx + r);
-                while (x <= xhi) {
-                    const int2 se = table[(size_t)(z * d1 + y) * d0 + x];
-                    for (int i = se.x; i < se.y; ++i) {
-                        const float4 c = pts[i];
-                        const int j = __float_as_int(c.w);
-                        if (j == qi) continue;                               // self goes by index, not by distance
-                        const float dx = c.x - q.x, dy = c.y - q.y, dz = c.z - q.z;
-                        const float dd = (dx * dx + dy * dy) + dz * dz;
-                        const u64 ck = ((u64)__float_as_uint(dd) << 32) | (unsigned)j;
-                        if (ck < worst) {
-                            int p = k - 1;
-                            while (p > 0) {                                  // at most k - 1 steps
-                                const u64 prev = best[(p - 1) * TPB];
-                                if (prev <= ck) break;
-                                best[p * TPB] = prev;
-                                --p;
-                            }
-                            best[p * TPB] = ck;
-                            worst = best[(k - 1) * TPB];
-                        }
-                    }
-                    x = full ? x + 1 : (x < cx + r ? cx + r : xhi + 1);
-                }
-            }
-        }
-        float bound2;
-        if (!block_bound2(c0, r, bound2)) break;                             // the block covers the grid
-        if (__uint_as_float((unsigned)(worst >> 32)) < bound2) break;
-    }
-    for (int r = 0; r < k; ++r) {
-        const u64 b = best[r * TPB];
-        idx[(size_t)qi * k + r] = (int)(unsigned)b;
-        d2_out[(size_t)qi * k + r] = __uint_as_float((unsigned)(b >> 32));
-    }
-}
-
-// ---- fixed radius ------------------------------------------------------------------------------------------------------
-// k_cloud_search's walk for a fixed radius.  visit(i, pts[i]) sees every point of the scanned cells, the query included,
-// and returns false once the lane needs no more; after each shell the walk ends when the block covers the grid, when
-// bound2 > r2, or when enough(bound2) says so.
+// The file's ONE walk over the Chebyshev shells of cells around a query's cell (the header's "Termination and exactness").
+// visit(i, pts[i]) sees every point of the scanned cells, the query included, and returns false once the lane needs no
+// more; after each shell the walk ends when the block covers the grid, when bound2 > r2 (a search passes r2 = +inf:
+// never), or when enough(bound2) says so.
 template <typename Visit, typename Enough>
-__device__ __forceinline__ void radius_walk(const float4* __restrict__ pts, const int2* __restrict__ table,
+__device__ __forceinline__ void shell_walk(const float4* __restrict__ pts, const int2* __restrict__ table,
                                             const CloudQuery& c, float r2, Visit visit, Enough enough) {
     const int cx = c.cx, cy = c.cy, cz = c.cz;
     bool more = true;
@@ -328,6 +267,50 @@ __device__ __forceinline__ void radius_walk(const float4* __restrict__ pts, cons
     }
 }
 
+__global__ __launch_bounds__(TPB) void k_cloud_search(const float4* __restrict__ pts, const u64* __restrict__ keys,
+                                                      const int2* __restrict__ table, const CloudGrid* __restrict__ g,
+                                                      const int* __restrict__ status, int n, int k,
+                                                      int* __restrict__ idx, float* __restrict__ d2_out) {
+    extern __shared__ __attribute__((aligned(16))) u64 s_best[];            // [k][TPB], lane-minor
+    if (*status != 0) return;                                                // non-finite input or a failed sort: no row is written
+    const int tid = threadIdx.x;
+    const int t = blockIdx.x * TPB + tid;
+    if (t >= n) return;                                                      // no barrier below: every lane owns its column
+    u64* __restrict__ best = s_best + tid;
+    for (int r = 0; r < k; ++r) best[r * TPB] = CLOUD_PAD_KEY;
+    u64 worst = CLOUD_PAD_KEY;
+
+    const float4 q = pts[t];
+    const int qi = __float_as_int(q.w);
+    shell_walk(pts, table, cloud_query(q, (unsigned)keys[t], g), __uint_as_float(0x7f800000u),   // r2 = +inf: no radius
+               [&](int, const float4 c) {
+                   const int j = __float_as_int(c.w);
+                   if (j == qi) return true;                                 // self goes by index, not by distance
+                   const float dx = c.x - q.x, dy = c.y - q.y, dz = c.z - q.z;
+                   const float dd = (dx * dx + dy * dy) + dz * dz;
+                   const u64 ck = ((u64)__float_as_uint(dd) << 32) | (unsigned)j;
+                   if (ck < worst) {
+                       int p = k - 1;
+                       while (p > 0) {                                       // at most k - 1 steps
+                           const u64 prev = best[(p - 1) * TPB];
+                           if (prev <= ck) break;
+                           best[p * TPB] = prev;
+                           --p;
+                       }
+                       best[p * TPB] = ck;
+                       worst = best[(k - 1) * TPB];
+                   }
+                   return true;                                              // a search never has enough before a shell ends
+               },
+               [&](float bound2) { return __uint_as_float((unsigned)(worst >> 32)) < bound2; });
+    for (int r = 0; r < k; ++r) {
+        const u64 b = best[r * TPB];
+        idx[(size_t)qi * k + r] = (int)(unsigned)b;
+        d2_out[(size_t)qi * k + r] = __uint_as_float((unsigned)(b >> 32));
+    }
+}
+
+// ---- fixed radius ------------------------------------------------------------------------------------------------------
 // One lane per query in sorted order; count[query] = min(points j != query with d2 <= r2, cap).
 __global__ __launch_bounds__(TPB) void k_radius_count(const float4* __restrict__ pts, const u64* __restrict__ keys,
                                                       const int2* __restrict__ table, const CloudGrid* __restrict__ g,
@@ -339,7 +322,7 @@ __global__ __launch_bounds__(TPB) void k_radius_count(const float4* __restrict__
     const float4 q = pts[t];
     const int qi = __float_as_int(q.w);
     int cnt = 0;
-    radius_walk(pts, table, cloud_query(q, (unsigned)keys[t], g), r2,
+    shell_walk(pts, table, cloud_query(q, (unsigned)keys[t], g), r2,
                 [&](int, const float4 c) {
                     const float dx = c.x - q.x, dy = c.y - q.y, dz = c.z - q.z;
                     const float dd = (dx * dx + dy * dy) + dz * dz;
@@ -375,7 +358,7 @@ __global__ __launch_bounds__(TPB) void k_radius_route(const float4* __restrict__
     const int qi = __float_as_int(q.w);
     if (skeep[t]) { route[qi] = rank[qi]; return; }
     u64 best = CLOUD_PAD_KEY;
-    radius_walk(pts, table, cloud_query(q, (unsigned)keys[t], g), r2,
+    shell_walk(pts, table, cloud_query(q, (unsigned)keys[t], g), r2,
                 [&](int i, const float4 c) {
                     const float dx = c.x - q.x, dy = c.y - q.y, dz = c.z - q.z;
                     const float dd = (dx * dx + dy * dy) + dz * dz;

@@ -70,6 +70,29 @@ def room(seed=1, n=3000):
     return p.astype(F32)
 
 
+def collinear(n=300, seed=0):
+    """Points on one line along x: two axes of zero extent, so two axes of one cell and shells that grow along x only."""
+    p = np.zeros((n, 3))
+    p[:, 0] = np.random.default_rng(60 + seed).uniform(0, 10, n)
+    p[:, 1:] = (0.5, -2.0)
+    return p.astype(F32)
+
+
+FACE_TIE_CELL = 1.0
+
+
+def face_tie():
+    """Cells of 1.0 along x, origin 0.  Query 1 at x = 1.5 (cell 1) has point 2 at x = 1.0 (its own cell) and point 0 at
+    x = 2.0 (cell 2, across the face) both at d2 = 0.25 exactly, and after shell 0 the bound to that face is 0.25 as well
+    (the bound's slack of 2^-38 vanishes in the float32 rounding of 0.5).  For k = 1 the row is point 0, the lower index:
+    the walk has to go on past a k-th d2 that EQUALS the bound.  Points 3 and 4 pin the grid's origin and its length."""
+    x = np.array([2.0, 1.5, 1.0, 0.0, 4.0])
+    return np.stack([x, np.full(5, 0.5), np.full(5, 0.5)], 1).astype(F32)
+
+
+SPARSE_CELL = 0.05
+
+
 def _cases():
     c = {"n0": (np.zeros((0, 3), F32), None), "n1": (gauss(1), None), "n2": (gauss(2), None)}
     for n in (63, 64, 65, 255, 256, 257):
@@ -86,6 +109,13 @@ def _cases():
     c["offset"] = (offset(), None)
     for seed in (1, 2, 3):
         c["room%d" % seed] = (room(seed), None)
+    c["collinear"] = (collinear(), None)
+    c["face_tie"] = (face_tie(), FACE_TIE_CELL)
+    # 300 points of a unit Gaussian under a cell of 0.05 (the table's cap widens it to ~0.4): the k-th neighbour of a point
+    # in the tails lies several cells away, so its walk needs shells r >= 2
+    c["sparse_small_cell"] = (gauss(300), SPARSE_CELL)
+    # one cell for the whole grid: the block has no inner face, and the walk ends because it covers the grid
+    c["n257_one_cell"] = (gauss(257), 1.0e3)
     return c
 
 
