@@ -212,8 +212,10 @@ int pbn_segment_pool(const void* feats, int ld, int channels, int dtype, const i
                      float* out_max, float* out_avg, void* workspace, size_t workspace_bytes, pbn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
- * Stage glue of PBNet.forward (csrc/stages.hip): each call replaces a run of small tensor ops of the reference by one
- * launch with identical integer results and the same fp32 arithmetic.
+ * Stage glue of PBNet.forward (csrc/front.hip, csrc/heads.hip): each call replaces a run of small tensor ops of the
+ * reference by one launch with identical integer results and the same fp32 arithmetic.  Where a size is followed by a
+ * device count (n_dev, n_ent_dev, n_rows_dev: the first int32 word is read on the device) the size is a CAPACITY and the
+ * launch covers min(count, capacity); a NULL count means the size is exact (capacity-planned inference, below).
  *
  * pbn_local_scene_rows -- rows of every local scene (network/PBNet.py:182-247).  Entry e (one grouping cluster taking
  * part in one local scene) owns rows [ent_row_start[e], ent_row_start[e+1]); row j of it is the point
@@ -222,17 +224,18 @@ int pbn_segment_pool(const void* feats, int ld, int channels, int dtype, const i
  * multiplication by the fp32 reciprocal -- and the mask-branch input row
  *   [point_feat[p, 0:channels], sem_score[p, sem_pred[p]], ent_weight[e], 0 ... 0]   (ld_out elements of `dtype`);
  * sem_pred NULL = column 0 (sem_score is then the per-point own-class score of pbn_sem_argmax_table).
+ * n_ent_dev / n_rows_dev: both NULL or both given (PBN_ERR_ARG otherwise).
  *
- * pbn_gather_pad_rows -- out[i, 0:row_bytes] = in[idx[i], 0:row_bytes] (idx NULL = identity), the rest of the output
- * row zero-filled: builds a 16-byte-aligned, zero-padded input slab in one pass.  All byte counts multiples of 4. */
+ * pbn_gather_pad_rows -- out[i, 0:row_bytes] = in[idx2[idx[i]], 0:row_bytes] (either index NULL = identity), the rest of
+ * the output row zero-filled: builds a 16-byte-aligned, zero-padded input slab in one pass.  All byte counts multiples of 4. */
 int pbn_local_scene_rows(const int32_t* ent_row_start, const int32_t* ent_member_start, const int32_t* ent_scene,
-                         const float* ent_weight, int n_ent, int n_rows, const int32_t* member_idx,
-                         const int64_t* ins_ind, const float* xyz, float inv_voxel, const void* point_feat, int ld_feat,
-                         int channels, const void* sem_score, int ld_sem, const int64_t* sem_pred, int dtype,
-                         int64_t* point_idx, int64_t* row_scene, int32_t* coords, void* feat_out, int ld_out,
-                         pbn_stream_t stream);
-int pbn_gather_pad_rows(const void* in, int ld_in_bytes, int row_bytes, const int64_t* idx, int n, void* out,
-                        int ld_out_bytes, pbn_stream_t stream);
+                         const float* ent_weight, int n_ent, int n_rows, const int32_t* n_ent_dev,
+                         const int32_t* n_rows_dev, const int32_t* member_idx, const int64_t* ins_ind, const float* xyz,
+                         float inv_voxel, const void* point_feat, int ld_feat, int channels, const void* sem_score,
+                         int ld_sem, const int64_t* sem_pred, int dtype, int64_t* point_idx, int64_t* row_scene,
+                         int32_t* coords, void* feat_out, int ld_out, pbn_stream_t stream);
+int pbn_gather_pad_rows(const void* in, int ld_in_bytes, int row_bytes, const int64_t* idx, const int64_t* idx2, int n,
+                        const int32_t* n_dev, void* out, int ld_out_bytes, pbn_stream_t stream);
 
 /* pbn_pack_weight -- fp32 master weights [n_offsets, dim_a, dim_b] (the reference's `kernel` layout [K, Cin, Cout]) into
  * the `w_packed` fragment order pbn_spconv_forward reads, in one launch.  flip mirrors the offsets (K-1-k), transpose
@@ -253,12 +256,6 @@ typedef struct pbn_pack_job {
     int32_t reserved[2];
 } pbn_pack_job;
 int pbn_pack_weights_batch(const pbn_pack_job* jobs, int n_jobs, int max_vectors, int dtype, pbn_stream_t stream);
-
-/* pbn_gather_rulebook_rows -- the gathered operand of the weight gradient (training, BASELINE configs[2]):
- * out[v, j, 0:row_bytes] = in[nbr[v, k0 + j], 0:row_bytes] for j < kc, zeros where nbr is -1; out is dense
- * [n, kc, row_bytes].  dW[k0:k0+kc] is then one dense contraction of this slab with the output gradient. */
-int pbn_gather_rulebook_rows(const void* in, int ld_in_bytes, int row_bytes, const int32_t* nbr, int n_offsets, int k0,
-                             int kc, int n, void* out, pbn_stream_t stream);
 
 /* Train-mode batch normalisation of a feature slab x[n, channels] (row stride ld_* elements, rows 16-byte aligned;
  * ME.MinkowskiBatchNorm = torch.nn.BatchNorm1d on .F, /root/reference/network/Mink.py:71-73,224; training, configs[2]).
@@ -370,7 +367,7 @@ int pbn_spconv_wgrad_plan(int dtype, int ld_x, int ld_g, int aligned16, int iden
  * is allocated at a CAPACITY chosen by the caller (pbnet_amd/planned.py takes them from a previous forward of a scene of the
  * same size class); kernels read the true counts from `counts` (int32[PBN_CNT_WORDS]) and raise bits of
  * counts[PBN_CNT_OVERFLOW] instead of writing past a capacity (the caller then falls back to the size-exact path).
- * The `_dev` variants of the stage kernels take (capacity, pointer to the device-side count).
+ * The stage kernels (csrc/front.hip, csrc/heads.hip) take (capacity, pointer to the device-side count).
  *   pbn_class_gate       network/PBNet.py:151-160,172-173: classes with (float)count < thr05[c] are dropped; class_base[c]
  *                        = first output slot of class c (-1 dropped), seg_len[(c-2)*nb + b] = points of (class, batch)
  *                        (0 for dropped classes: the grouping skips empty segments), counts[PBN_CNT_POINTS].
@@ -408,37 +405,20 @@ int pbn_proposal_offsets(const int32_t* per_scene, int s_cap, int64_t* proposals
                          int32_t* dense_of, int32_t* counts, pbn_stream_t stream);
 int pbn_batch_starts(const int32_t* coords, const int32_t* n_dev, int n_cap, int n_segments, int32_t* seg_start,
                      pbn_stream_t stream);
-int pbn_local_scene_rows_dev(const int32_t* ent_row_start, const int32_t* ent_member_start, const int32_t* ent_scene,
-                             const float* ent_weight, int n_ent_cap, int n_rows_cap, const int32_t* n_ent_dev,
-                             const int32_t* n_rows_dev, const int32_t* member_idx, const int64_t* ins_ind, const float* xyz,
-                             float inv_voxel, const void* point_feat, int ld_feat, int channels, const void* sem_score,
-                             int ld_sem, const int64_t* sem_pred, int dtype, int64_t* point_idx, int64_t* row_scene,
-                             int32_t* coords, void* feat_out, int ld_out, pbn_stream_t stream);
-int pbn_gather_pad_rows_dev(const void* in, int ld_in_bytes, int row_bytes, const int64_t* idx, const int64_t* idx2,
-                            int n_cap, const int32_t* n_dev, void* out, int ld_out_bytes, pbn_stream_t stream);
-/* in_rows: the row capacity of `in`; a resolved row index outside [0, in_rows) reads as a row of zeros (an index table of a
- * level that overflowed its capacity names rows that were never computed). */
-int pbn_mlp_rows_dev(const void* in, int ld_in, int in_rows, int channels, const int64_t* idx_a, const int64_t* idx_b, int n_cap,
-                     const int32_t* n_dev, const float* w1, const float* scale, const float* shift, const float* slope,
-                     int hidden, const float* w2, const float* b2, int n_out, int sigmoid, void* out, int ld_out, int dtype,
-                     pbn_stream_t stream);
-int pbn_mask_count_dev(const void* mask_score, int ld, float thd, const int64_t* row_scene, int n_cap, const int32_t* n_dev,
-                       int n_scenes_cap, int dtype, int32_t* per_scene, int32_t* block_cnt, pbn_stream_t stream);
-int pbn_proposal_rows_dev(const void* mask_score, int ld, float thd, const int64_t* row_scene, const int64_t* point_idx,
-                          int n_cap, const int32_t* n_dev, const int32_t* dense_of, const int32_t* block_cnt,
-                          const float* xyz, float scale, float inv_voxel, const void* point_feat, int ld_feat, int channels,
-                          int dtype, int64_t* proposals_idx, void* proposals_ms, int32_t* coords, void* feat_out,
-                          pbn_stream_t stream);
 
-/* pbn_mlp_rows -- the two-layer heads of network/PBNet.py:43-82 in eval mode, one launch per head:
+/* pbn_mlp_rows (csrc/heads.hip) -- the two-layer heads of network/PBNet.py:43-82 in eval mode, one launch per head:
  *   out[i, 0:n_out] = act( W2 . prelu( (W1 . x) * scale + shift ) + b2 ),   x = in[row(i), 0:channels],
  *   row(i) = idx_b[idx_a[i]] (either index level may be NULL), act = sigmoid or identity.
  * W1 f32[hidden, channels], scale/shift = eval-mode BatchNorm folded (f32[hidden]), slope f32[hidden] (PReLU),
  * W2 f32[n_out, hidden], b2 f32[n_out] or NULL.  fp32 arithmetic, one rounding to `dtype` at the end.
+ * in_rows: the row capacity of `in`; a resolved row index outside [0, in_rows) reads as a row of zeros (an index table of a
+ * level that overflowed its capacity names rows that were never computed).  in_rows < 0: the rows are not bounded.
+ * n_dev: device count of the rows (NULL = n is exact).
  * channels must be 32 and hidden 16 or 32 (the shapes PBNet builds); anything else returns PBN_ERR_UNSUPPORTED. */
-int pbn_mlp_rows(const void* in, int ld_in, int channels, const int64_t* idx_a, const int64_t* idx_b, int n,
-                 const float* w1, const float* scale, const float* shift, const float* slope, int hidden, const float* w2,
-                 const float* b2, int n_out, int sigmoid, void* out, int ld_out, int dtype, pbn_stream_t stream);
+int pbn_mlp_rows(const void* in, int ld_in, int in_rows, int channels, const int64_t* idx_a, const int64_t* idx_b, int n,
+                 const int32_t* n_dev, const float* w1, const float* scale, const float* shift, const float* slope, int hidden,
+                 const float* w2, const float* b2, int n_out, int sigmoid, void* out, int ld_out, int dtype,
+                 pbn_stream_t stream);
 
 /* pbn_sem_argmax_table -- network/PBNet.py:134,151-163: per point the arg-max class (first maximum), the softmax score
  * of that class (1 / sum exp(s - max), fp32, rounded to `dtype`; may be NULL) and the [n_cls, nb] population table
@@ -462,12 +442,13 @@ int pbn_select_points(const int64_t* sem_pred, int n, int n_cls, const int32_t* 
  *                       of the surviving scenes ("remove null proposals", :342-345) and the proposal offsets;
  *   pbn_proposal_rows : for every kept row, in row order: proposals_idx = (dense_of[row_scene], point_idx),
  *                       proposals_ms = its mask score and, optionally, the score-branch voxel coordinate
- *                       (dense id, floor(xyz[p] * scale * inv_voxel)) and input feature row point_feat[p, 0:channels]. */
-int pbn_mask_count(const void* mask_score, int ld, float thd, const int64_t* row_scene, int n, int n_scenes, int dtype,
-                   int32_t* per_scene, int32_t* block_cnt, pbn_stream_t stream);
+ *                       (dense id, floor(xyz[p] * scale * inv_voxel)) and input feature row point_feat[p, 0:channels].
+ * n_dev: device count of the input rows (NULL = n is exact); n_scenes may be a capacity either way. */
+int pbn_mask_count(const void* mask_score, int ld, float thd, const int64_t* row_scene, int n, const int32_t* n_dev,
+                   int n_scenes, int dtype, int32_t* per_scene, int32_t* block_cnt, pbn_stream_t stream);
 int pbn_proposal_rows(const void* mask_score, int ld, float thd, const int64_t* row_scene, const int64_t* point_idx, int n,
-                      const int32_t* dense_of, const int32_t* block_cnt, const float* xyz, float scale, float inv_voxel,
-                      const void* point_feat, int ld_feat, int channels, int dtype, int64_t* proposals_idx,
+                      const int32_t* n_dev, const int32_t* dense_of, const int32_t* block_cnt, const float* xyz, float scale,
+                      float inv_voxel, const void* point_feat, int ld_feat, int channels, int dtype, int64_t* proposals_idx,
                       void* proposals_ms, int32_t* coords, void* feat_out, pbn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------

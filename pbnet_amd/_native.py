@@ -160,18 +160,19 @@ SIGNATURES = {
     "pbn_gather_rows": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_int, c_vp]),
     "pbn_segment_pool_workspace_bytes": (c_size, [c_int, c_int]),
     "pbn_segment_pool": (c_int, [c_vp, c_int, c_int, c_int, c_i32p, c_int, c_f32p, c_f32p, c_vp, c_size, c_vp]),
-    "pbn_local_scene_rows": (c_int, [c_i32p, c_i32p, c_i32p, c_f32p, c_int, c_int, c_i32p, c_vp, c_f32p, c_float, c_vp,
-                                     c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_i32p, c_vp, c_int, c_vp]),
-    "pbn_gather_pad_rows": (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp]),
-    "pbn_mlp_rows": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_f32p, c_f32p,
-                             c_int, c_int, c_vp, c_int, c_int, c_vp]),
+    "pbn_local_scene_rows": (c_int, [c_i32p, c_i32p, c_i32p, c_f32p, c_int, c_int, c_i32p, c_i32p, c_i32p, c_vp, c_f32p,
+                                     c_float, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_i32p, c_vp,
+                                     c_int, c_vp]),
+    "pbn_gather_pad_rows": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_i32p, c_vp, c_int, c_vp]),
+    "pbn_mlp_rows": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_int,
+                             c_f32p, c_f32p, c_int, c_int, c_vp, c_int, c_int, c_vp]),
     "pbn_select_blocks": (c_int, [c_int]),
     "pbn_sem_argmax_table": (c_int, [c_vp, c_int, c_int, c_i32p, c_int, c_int, c_int, c_vp, c_vp, c_i32p, c_i32p, c_vp]),
     "pbn_select_points": (c_int, [c_vp, c_int, c_int, c_i32p, c_i32p, c_f32p, c_vp, c_int, c_int, c_vp, c_f32p, c_f32p,
                                   c_i32p, c_vp]),
-    "pbn_mask_count": (c_int, [c_vp, c_int, c_float, c_vp, c_int, c_int, c_int, c_i32p, c_i32p, c_vp]),
-    "pbn_proposal_rows": (c_int, [c_vp, c_int, c_float, c_vp, c_vp, c_int, c_i32p, c_i32p, c_f32p, c_float, c_float, c_vp,
-                                  c_int, c_int, c_int, c_vp, c_vp, c_i32p, c_vp, c_vp]),
+    "pbn_mask_count": (c_int, [c_vp, c_int, c_float, c_vp, c_int, c_i32p, c_int, c_int, c_i32p, c_i32p, c_vp]),
+    "pbn_proposal_rows": (c_int, [c_vp, c_int, c_float, c_vp, c_vp, c_int, c_i32p, c_i32p, c_i32p, c_f32p, c_float,
+                                  c_float, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_i32p, c_vp, c_vp]),
     "pbn_post_words": (c_int, [c_int]),
     "pbn_proposal_bitmask": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_i32p, c_vp]),
     "pbn_mask_iou": (c_int, [c_vp, c_i32p, c_int, c_int, c_i32p, c_f32p, c_vp]),
@@ -224,7 +225,6 @@ SIGNATURES = {
     "pbn_rulebook_pair_counts": (c_int, [c_i32p, c_int, c_int, c_i32p, c_i32p, c_vp]),
     "pbn_rulebook_pair_fill_dev": (c_int, [c_i32p, c_int, c_int, c_i32p, c_i32p, c_int, c_i32p, c_vp, c_vp, c_vp, c_vp]),
     "pbn_rulebook_pair_fill": (c_int, [c_i32p, c_int, c_int, c_i32p, c_i32p, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
-    "pbn_gather_rulebook_rows": (c_int, [c_vp, c_int, c_int, c_i32p, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "pbn_pack_weights_batch": (c_int, [c_vp, c_int, c_int, c_int, c_vp]),
     "pbn_pack_weight": (c_int, [c_f32p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "pbn_kernel_map_cube": (c_int, [c_i32p, c_i32p, c_int, c_int, c_int, c_int, c_vp, c_i32p, c_int, c_i32p, c_vp]),
@@ -244,15 +244,6 @@ SIGNATURES = {
                                c_i32p, c_i32p, c_f32p, c_i32p, c_vp, c_size, c_vp]),
     "pbn_proposal_offsets": (c_int, [c_i32p, c_int, c_vp, c_vp, c_i32p, c_i32p, c_vp]),
     "pbn_batch_starts": (c_int, [c_i32p, c_i32p, c_int, c_int, c_i32p, c_vp]),
-    "pbn_local_scene_rows_dev": (c_int, [c_i32p, c_i32p, c_i32p, c_f32p, c_int, c_int, c_i32p, c_i32p, c_i32p, c_vp, c_f32p,
-                                         c_float, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_i32p, c_vp,
-                                         c_int, c_vp]),
-    "pbn_gather_pad_rows_dev": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_i32p, c_vp, c_int, c_vp]),
-    "pbn_mlp_rows_dev": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_int,
-                                 c_f32p, c_f32p, c_int, c_int, c_vp, c_int, c_int, c_vp]),
-    "pbn_mask_count_dev": (c_int, [c_vp, c_int, c_float, c_vp, c_int, c_i32p, c_int, c_int, c_i32p, c_i32p, c_vp]),
-    "pbn_proposal_rows_dev": (c_int, [c_vp, c_int, c_float, c_vp, c_vp, c_int, c_i32p, c_i32p, c_i32p, c_f32p, c_float,
-                                      c_float, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_i32p, c_vp, c_vp]),
     "pbn_morton_keys": (c_int, [c_i32p, c_i32p, c_int, c_vp, c_vp]),
     "pbn_unet_arena_bytes": (c_size, [ctypes.POINTER(UnetBuf), c_int, ctypes.POINTER(c_i32), c_int,
                                       ctypes.POINTER(c_i64)]),

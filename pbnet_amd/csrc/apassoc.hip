@@ -250,7 +250,7 @@ extern "C" int pbn_instance_overlap(const int32_t* masks, int n_pred, int n_pts,
     if (n_pred < 0 || n_pts < 0 || n_gt < 1) return PBN_ERR_ARG;
     if (n_pred == 0) return PBN_OK;
     if (!inter) return PBN_ERR_ARG;
-    { const int frc_ = fill_bytes(inter, 0, sizeof(int32_t) * (size_t)n_pred * n_gt, stream); if (frc_ != PBN_OK) return frc_; }
+    PBN_TRY(fill_bytes(inter, 0, sizeof(int32_t) * (size_t)n_pred * n_gt, stream));
     if (n_pts == 0) return PBN_OK;
     if (!masks || !gt_index) return PBN_ERR_ARG;
     const dim3 grid(cdiv(n_pts, OVERLAP_CHUNK), n_pred);

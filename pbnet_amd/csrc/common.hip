@@ -243,7 +243,7 @@ int scan_exclusive_i32_chained(const int* in, int* out, int n, unsigned long lon
 
 int scan_exclusive_i32(const int* in, int* out, int n, int* tmp, int* total, hipStream_t stream) {
     if (n <= 0) {
-        if (total) { const int frc_ = fill_bytes(total, 0, sizeof(int), stream); if (frc_ != PBN_OK) return frc_; }
+        if (total) PBN_TRY(fill_bytes(total, 0, sizeof(int), stream));
         return PBN_OK;
     }
     const int nb = cdiv(n, SCAN_TILE);

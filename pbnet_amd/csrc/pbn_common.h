@@ -1,13 +1,15 @@
 // pbn_common.h -- shared helpers for the gfx950 kernels of libpbnet_hip.so (wave64, CDNA4 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_bf16.h>
+#include <hip/hip_fp16.h>
 #include <stdint.h>
 #include "../../include/pbnet_hip.h"
 
 namespace pbn {
 
 constexpr int WAVE = 64;
-// classes a semantic head may have: bounds the LDS tables of k_sem_argmax_table / k_select_points (stages.hip) and the score
+// classes a semantic head may have: bounds the LDS tables of k_sem_argmax_table / k_select_points (front.hip) and the score
 // registers of k_summary_points (summary.hip)
 constexpr int SEL_MAX_CLASSES = 32;
 
@@ -23,6 +25,33 @@ extern thread_local int g_last_hip_error;
     } while (0)
 
 #define PBN_LAUNCH_CHECK() PBN_HIP_CHECK(hipGetLastError())
+
+// returns the status of a failing call of this library (fill_bytes, scan_exclusive_i32, ...)
+#define PBN_TRY(expr)                                        \
+    do {                                                     \
+        const int _rc = (expr);                              \
+        if (_rc != PBN_OK) return _rc;                       \
+    } while (0)
+
+// calls f with a value of the element type of `dtype` (a generic lambda: `using T = decltype(t)`); false = unknown dtype
+template <typename F>
+static inline bool dispatch_dtype(int dtype, F&& f) {
+    if (dtype == PBN_F32) f(float{});
+    else if (dtype == PBN_BF16) f(__hip_bfloat16{});
+    else if (dtype == PBN_F16) f(__half{});
+    else return false;
+    return true;
+}
+
+template <typename T> __device__ __forceinline__ float to_f32(T v);
+template <> __device__ __forceinline__ float to_f32<float>(float v) { return v; }
+template <> __device__ __forceinline__ float to_f32<__hip_bfloat16>(__hip_bfloat16 v) { return __bfloat162float(v); }
+template <> __device__ __forceinline__ float to_f32<__half>(__half v) { return __half2float(v); }
+// *p = v, rounded once (to nearest even) to T
+template <typename T> __device__ __forceinline__ void st_f32(T* p, float v);
+template <> __device__ __forceinline__ void st_f32<float>(float* p, float v) { *p = v; }
+template <> __device__ __forceinline__ void st_f32<__hip_bfloat16>(__hip_bfloat16* p, float v) { *p = __float2bfloat16(v); }
+template <> __device__ __forceinline__ void st_f32<__half>(__half* p, float v) { *p = __float2half(v); }
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }

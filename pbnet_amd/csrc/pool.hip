@@ -9,11 +9,6 @@
 namespace pbn {
 namespace {
 
-template <typename T> __device__ __forceinline__ float to_f32(T v);
-template <> __device__ __forceinline__ float to_f32<float>(float v) { return v; }
-template <> __device__ __forceinline__ float to_f32<__hip_bfloat16>(__hip_bfloat16 v) { return __bfloat162float(v); }
-template <> __device__ __forceinline__ float to_f32<__half>(__half v) { return __half2float(v); }
-
 template <typename T>
 __global__ __launch_bounds__(256) void k_segment_pool(const T* __restrict__ feats, int ld, int channels,
                                                      const int* __restrict__ seg_start, float* __restrict__ out_max,
@@ -171,16 +166,10 @@ extern "C" int pbn_segment_pool(const void* feats, int ld, int channels, int dty
         float* ps = pm + (size_t)n_seg * split * channels;
         const size_t lds = (size_t)2 * rps * channels * sizeof(float);
         const dim3 grid(n_seg, split);
-        if (dtype == PBN_F32)
-            hipLaunchKernelGGL(k_pool_partial<float>, grid, dim3(256), lds, stream, (const uint4*)feats, ld * esz / 16, vpr,
-                               seg_start, split, pm, ps);
-        else if (dtype == PBN_BF16)
-            hipLaunchKernelGGL(k_pool_partial<__hip_bfloat16>, grid, dim3(256), lds, stream, (const uint4*)feats,
-                               ld * esz / 16, vpr, seg_start, split, pm, ps);
-        else if (dtype == PBN_F16)
-            hipLaunchKernelGGL(k_pool_partial<__half>, grid, dim3(256), lds, stream, (const uint4*)feats, ld * esz / 16,
-                               vpr, seg_start, split, pm, ps);
-        else
+        if (!dispatch_dtype(dtype, [&](auto t) {
+                hipLaunchKernelGGL(k_pool_partial<decltype(t)>, grid, dim3(256), lds, stream, (const uint4*)feats, ld * esz / 16,
+                                   vpr, seg_start, split, pm, ps);
+            }))
             return PBN_ERR_ARG;
         hipLaunchKernelGGL(k_pool_final, dim3(cdiv((long long)n_seg * channels, 256)), dim3(256), 0, stream, pm, ps, seg_start,
                            n_seg, channels, split, out_max, out_avg);
@@ -188,21 +177,12 @@ extern "C" int pbn_segment_pool(const void* feats, int ld, int channels, int dty
         return PBN_OK;
     }
     const dim3 grid(n_seg, cdiv(channels, 32));
-    switch (dtype) {
-        case PBN_F32:
-            hipLaunchKernelGGL(k_segment_pool<float>, grid, dim3(256), 0, stream, (const float*)feats, ld, channels,
-                               seg_start, out_max, out_avg);
-            break;
-        case PBN_BF16:
-            hipLaunchKernelGGL(k_segment_pool<__hip_bfloat16>, grid, dim3(256), 0, stream, (const __hip_bfloat16*)feats,
-                               ld, channels, seg_start, out_max, out_avg);
-            break;
-        case PBN_F16:
-            hipLaunchKernelGGL(k_segment_pool<__half>, grid, dim3(256), 0, stream, (const __half*)feats, ld, channels,
-                               seg_start, out_max, out_avg);
-            break;
-        default: return PBN_ERR_ARG;
-    }
+    if (!dispatch_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(k_segment_pool<T>, grid, dim3(256), 0, stream, (const T*)feats, ld, channels, seg_start, out_max,
+                               out_avg);
+        }))
+        return PBN_ERR_ARG;
     PBN_LAUNCH_CHECK();
     return PBN_OK;
 }

@@ -294,7 +294,7 @@ extern "C" int pbn_proposal_bitmask(const int64_t* proposals_idx, int n_entries,
     if (n_prop == 0) return PBN_OK;
     if (!masks || !counts || (n_entries > 0 && !proposals_idx)) return PBN_ERR_ARG;
     const int words = pbn_post_words(n_fold);
-    { const int frc_ = fill_bytes(masks, 0, sizeof(uint32_t) * (size_t)n_prop * words, stream); if (frc_ != PBN_OK) return frc_; }
+    PBN_TRY(fill_bytes(masks, 0, sizeof(uint32_t) * (size_t)n_prop * words, stream));
     if (n_entries > 0)
         hipLaunchKernelGGL(k_set_bits, dim3(cdiv(n_entries, TPB)), dim3(TPB), 0, stream, (const long long*)proposals_idx,
                            n_entries, n_fold, n_prop, words, masks);
@@ -324,8 +324,8 @@ extern "C" int pbn_superpoint_refine(const uint32_t* masks, const int32_t* pick,
         return PBN_ERR_ARG;
     const int words = pbn_post_words(n_fold);
     const int nb = cdiv(n_fold, TPB);
-    { const int frc_ = fill_bytes(hist, 0, sizeof(int) * (size_t)n_sp * (n_pick + 1), stream); if (frc_ != PBN_OK) return frc_; }
-    if (n_pick > 0) { const int frc_ = fill_bytes(masks_out, 0, sizeof(uint32_t) * (size_t)n_pick * words, stream); if (frc_ != PBN_OK) return frc_; }
+    PBN_TRY(fill_bytes(hist, 0, sizeof(int) * (size_t)n_sp * (n_pick + 1), stream));
+    if (n_pick > 0) PBN_TRY(fill_bytes(masks_out, 0, sizeof(uint32_t) * (size_t)n_pick * words, stream));
     hipLaunchKernelGGL(k_point_labels, dim3(nb), dim3(TPB), 0, stream, masks, pick, n_pick, words, n_fold, (long long*)seg);
     hipLaunchKernelGGL(k_sp_hist, dim3(nb), dim3(TPB), 0, stream, (const long long*)seg, (const long long*)superpoint, n_fold,
                        n_sp, n_pick, hist);

@@ -425,7 +425,7 @@ int post_batch_run(const int64_t* proposals_idx, int n_entries, const void* prop
     const int pitch = pbn_post_words(largest);          // <= pbn_post_words(n_points_total), the pitch the workspace is sized by
     const long long* pidx = (const long long*)proposals_idx;
 
-    { const int frc_ = fill_bytes(masks, 0, sizeof(uint32_t) * (size_t)n_prop * pitch, stream); if (frc_ != PBN_OK) return frc_; }
+    PBN_TRY(fill_bytes(masks, 0, sizeof(uint32_t) * (size_t)n_prop * pitch, stream));
     hipLaunchKernelGGL(k_pb_scene_of, dim3(cdiv(n_prop, TPB)), dim3(TPB), 0, stream, pidx, n_entries, proposals_offset, offset_i64,
                        n_prop, clt_score, score_dtype, scenes, copies, prop_scene, score);
     if (n_entries > 0)

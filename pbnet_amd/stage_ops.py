@@ -1,9 +1,9 @@
-"""Python face of csrc/stages.hip and csrc/plan.hip: the fused glue between the big kernels of PBNet.forward on the inference
-path (/root/reference/network/PBNet.py:113-280), and the ONLY module that marshals those entry points.  Device tensors in,
-device tensors out, no host synchronisation; every function is one launch.  (With autograd enabled PBNet.forward keeps the
-differentiable tensor-op form.)  Every `X` / `X_dev` pair of the C ABI is one function: given a device-side count (`n_dev`: an
-int32 device tensor whose FIRST word is the count, e.g. the one-element view counts[k:k + 1] -- no launch, no allocation, no
-synchronisation, and it captures into a HIP graph) the sizes are CAPACITIES and the `_dev` entry is called."""
+"""Python face of csrc/front.hip, csrc/heads.hip and csrc/plan.hip: the fused glue between the big kernels of PBNet.forward on
+the inference path (/root/reference/network/PBNet.py:113-280), and the ONLY module that marshals those entry points.  Device
+tensors in, device tensors out, no host synchronisation; every function is one launch.  (With autograd enabled PBNet.forward
+keeps the differentiable tensor-op form.)  Given a device-side count (`n_dev`: an int32 device tensor whose FIRST word is the
+count, e.g. the one-element view counts[k:k + 1] -- no launch, no allocation, no synchronisation, and it captures into a HIP
+graph) the sizes are CAPACITIES; without one they are exact."""
 from types import SimpleNamespace
 
 import numpy as np
@@ -64,35 +64,27 @@ def local_scene_rows(packed, n_ent, n_rows, member_idx, ins_ind, xyz, voxel, poi
     coords = torch.empty(n_rows, 4, dtype=torch.int32, device=dev)
     feat = torch.empty(n_rows, ld_out, dtype=point_feat.dtype, device=dev)
     vp = N.c_vp
-    head = ent.pointers() + (int(n_ent), int(n_rows))
-    rest = (N.ptr(member_idx), N.ptr(ins_ind), N.ptr(xyz), reciprocal_f32(voxel),
-            vp(point_feat.data_ptr()), point_feat.stride(0), c, vp(sem_score.data_ptr()), sem_score.stride(0),
-            N.ptr(sem_pred), _DT[point_feat.dtype], N.ptr(point_idx), N.ptr(row_scene), N.ptr(coords),
-            vp(feat.data_ptr()), ld_out, N.current_stream())
-    if n_ent_dev is None:
-        rc = N.lib().pbn_local_scene_rows(*(head + rest))
-    else:
-        rc = N.lib().pbn_local_scene_rows_dev(*(head + (N.ptr(n_ent_dev), N.ptr(n_rows_dev)) + rest))
+    rc = N.lib().pbn_local_scene_rows(*(ent.pointers() + (
+        int(n_ent), int(n_rows), N.ptr(n_ent_dev), N.ptr(n_rows_dev), N.ptr(member_idx), N.ptr(ins_ind), N.ptr(xyz),
+        reciprocal_f32(voxel), vp(point_feat.data_ptr()), point_feat.stride(0), c, vp(sem_score.data_ptr()),
+        sem_score.stride(0), N.ptr(sem_pred), _DT[point_feat.dtype], N.ptr(point_idx), N.ptr(row_scene), N.ptr(coords),
+        vp(feat.data_ptr()), ld_out, N.current_stream())))
     N.check(rc, "pbn_local_scene_rows")
     return point_idx, row_scene, coords, feat
 
 
 def gather_pad_rows(feats, width, idx=None, idx2=None, n=None, n_dev=None):
     """out[i, :] = feats[idx2[idx[i]], :] (either index None = identity) zero-padded to `width` columns, in one launch.  n: output
-    rows (default: those of idx, else of feats); n_dev: their device-side count (the second index exists in this form only)."""
+    rows (default: those of idx, else of feats); n_dev: their device-side count."""
     N.require_cuda(feats, idx, idx2)
     es = feats.element_size()
     if n is None:
         n = int(idx.shape[0]) if idx is not None else int(feats.shape[0])
-    assert feats.stride(1) == 1 and feats.shape[1] <= width and (idx2 is None or n_dev is not None)
+    assert feats.stride(1) == 1 and feats.shape[1] <= width
     out = torch.empty(n, width, dtype=feats.dtype, device=feats.device)
     vp = N.c_vp
-    src = (vp(feats.data_ptr()), feats.stride(0) * es, int(feats.shape[1]) * es, N.ptr(idx))
-    dst = (vp(out.data_ptr()), width * es, N.current_stream())
-    if n_dev is None:
-        rc = N.lib().pbn_gather_pad_rows(*(src + (int(n),) + dst))
-    else:
-        rc = N.lib().pbn_gather_pad_rows_dev(*(src + (N.ptr(idx2), int(n), N.ptr(n_dev)) + dst))
+    rc = N.lib().pbn_gather_pad_rows(vp(feats.data_ptr()), feats.stride(0) * es, int(feats.shape[1]) * es, N.ptr(idx),
+                                     N.ptr(idx2), int(n), N.ptr(n_dev), vp(out.data_ptr()), width * es, N.current_stream())
     N.check(rc, "pbn_gather_pad_rows")
     return out
 
@@ -139,13 +131,14 @@ def mlp_rows(head, feats, idx_a=None, idx_b=None, n=None, n_dev=None, in_rows=No
         n = int(idx_a.shape[0]) if idx_a is not None else int(feats.shape[0])
     out = torch.empty(n, hp.n_out, dtype=feats.dtype, device=feats.device)
     vp = N.c_vp
-    rest = (N.ptr(hp.w1), N.ptr(hp.scale), N.ptr(hp.shift), N.ptr(hp.slope), hp.hidden, N.ptr(hp.w2), N.ptr(hp.b2), hp.n_out,
-            int(hp.sigmoid), vp(out.data_ptr()), hp.n_out, _DT[feats.dtype], N.current_stream())
     if n_dev is None:
-        rc = N.lib().pbn_mlp_rows(vp(feats.data_ptr()), feats.stride(0), hp.channels, N.ptr(idx_a), N.ptr(idx_b), int(n), *rest)
-    else:
-        rc = N.lib().pbn_mlp_rows_dev(vp(feats.data_ptr()), feats.stride(0), int(feats.shape[0] if in_rows is None else in_rows),
-                                      hp.channels, N.ptr(idx_a), N.ptr(idx_b), int(n), N.ptr(n_dev), *rest)
+        in_rows = -1             # exact sizes: the rows are not bounded
+    elif in_rows is None:
+        in_rows = feats.shape[0]
+    rc = N.lib().pbn_mlp_rows(vp(feats.data_ptr()), feats.stride(0), int(in_rows), hp.channels, N.ptr(idx_a), N.ptr(idx_b), int(n),
+                              N.ptr(n_dev), N.ptr(hp.w1), N.ptr(hp.scale), N.ptr(hp.shift), N.ptr(hp.slope), hp.hidden,
+                              N.ptr(hp.w2), N.ptr(hp.b2), hp.n_out, int(hp.sigmoid), vp(out.data_ptr()), hp.n_out,
+                              _DT[feats.dtype], N.current_stream())
     N.check(rc, "pbn_mlp_rows")
     return out
 
@@ -227,9 +220,8 @@ def mask_count(mask_score, thd, row_scene, n_scenes, n_dev=None):
     assert ms.stride(1) == 1 and row_scene.dtype == torch.int64
     per_scene = torch.empty(max(n_scenes, 1), dtype=torch.int32, device=dev)
     block_cnt = torch.empty(max(lib.pbn_select_blocks(n), 1), dtype=torch.int32, device=dev)
-    src = (N.c_vp(ms.data_ptr()), ms.stride(0), float(thd), N.ptr(row_scene), n)
-    rest = (int(n_scenes), _DT[ms.dtype], N.ptr(per_scene), N.ptr(block_cnt), N.current_stream())
-    rc = lib.pbn_mask_count(*(src + rest)) if n_dev is None else lib.pbn_mask_count_dev(*(src + (N.ptr(n_dev),) + rest))
+    rc = lib.pbn_mask_count(N.c_vp(ms.data_ptr()), ms.stride(0), float(thd), N.ptr(row_scene), n, N.ptr(n_dev), int(n_scenes),
+                            _DT[ms.dtype], N.ptr(per_scene), N.ptr(block_cnt), N.current_stream())
     N.check(rc, "pbn_mask_count")
     return per_scene[:n_scenes], block_cnt
 
@@ -268,12 +260,11 @@ def proposal_rows(mask_score, thd, row_scene, point_idx, dense_of, block_cnt, to
     if total == 0:               # no row passed the threshold: nothing to launch (empty tensors have no address)
         return prop_idx, prop_ms, coords, feat
     vp = N.c_vp
-    src = (vp(ms.data_ptr()), ms.stride(0), float(thd), N.ptr(row_scene), N.ptr(point_idx), n)
-    rest = (N.ptr(dense_of), N.ptr(block_cnt), N.ptr(xyz), float(np.float32(scale)), reciprocal_f32(voxel),
-            None if point_feat is None else vp(point_feat.data_ptr()), ld_feat, c, _DT[ms.dtype], N.ptr(prop_idx),
-            vp(prop_ms.data_ptr()), N.ptr(coords), None if feat is None else vp(feat.data_ptr()), N.current_stream())
-    lib = N.lib()
-    rc = lib.pbn_proposal_rows(*(src + rest)) if n_dev is None else lib.pbn_proposal_rows_dev(*(src + (N.ptr(n_dev),) + rest))
+    rc = N.lib().pbn_proposal_rows(
+        vp(ms.data_ptr()), ms.stride(0), float(thd), N.ptr(row_scene), N.ptr(point_idx), n, N.ptr(n_dev), N.ptr(dense_of),
+        N.ptr(block_cnt), N.ptr(xyz), float(np.float32(scale)), reciprocal_f32(voxel),
+        None if point_feat is None else vp(point_feat.data_ptr()), ld_feat, c, _DT[ms.dtype], N.ptr(prop_idx),
+        vp(prop_ms.data_ptr()), N.ptr(coords), None if feat is None else vp(feat.data_ptr()), N.current_stream())
     N.check(rc, "pbn_proposal_rows")
     return prop_idx, prop_ms, coords, feat
 

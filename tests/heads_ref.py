@@ -1,7 +1,7 @@
 """Plain numpy float64 restatements of the ops between the backbone and the losses / the post-processing, each with the
 error bound an honest fp32 kernel must meet:
 
-  mlp_rows      the two-layer heads (csrc/stages.hip k_mlp_rows / k_mlp_rows_mfma)
+  mlp_rows      the two-layer heads (csrc/heads.hip k_mlp_rows / k_mlp_rows_mfma)
   sem_argmax    arg-max class, own-class softmax score, [class, batch] table, per-block class histogram (k_sem_argmax_table)
   segment_pool  per-segment maximum and mean (csrc/pool.hip)
   iou / mask_label   proposal x instance IoU and the mask targets (csrc/iou.hip), bit-exact

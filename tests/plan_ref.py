@@ -1,5 +1,5 @@
 """Plain host references of the device-side control flow of the inference forward (csrc/plan.hip and the `_dev` forms of
-csrc/stages.hip), written from the contracts of include/pbnet_hip.h ("Capacity-planned inference") and the lines of
+csrc/front.hip, csrc/heads.hip), written from the contracts of include/pbnet_hip.h ("Capacity-planned inference") and the lines of
 network/PBNet.py named there.  numpy only, explicit loops, int64 / float64 wherever arithmetic matters; float32 appears only
 where the contract prescribes a float32 operation (the gates' int -> float conversion, d^2, the rounding of the weights, the
 voxel coordinates).  Nothing here is fast and nothing here looks at how the kernels are organised.

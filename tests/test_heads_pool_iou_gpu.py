@@ -1,4 +1,4 @@
-"""GPU tier: the pointwise heads (csrc/stages.hip k_mlp_rows_mfma / k_mlp_rows), the class-score kernel (k_sem_argmax_table), segment
+"""GPU tier: the pointwise heads (csrc/heads.hip k_mlp_rows_mfma / k_mlp_rows), the class-score kernel (k_sem_argmax_table), segment
 pooling (csrc/pool.hip, both kernels) and the IoU targets (csrc/iou.hip) against the float64 references of tests/heads_ref.py, on the
 inputs of tests/heads_cases.py.  Every output element goes through heads_ref.accept (derived bounds; tests/test_heads_ref_cpu.py shows
 what they reject) or is compared bit for bit.  Each test prints the figures it measured before it asserts."""

@@ -1,8 +1,9 @@
 """GPU tier: the device-side control flow of the inference forward, entry point by entry point, against tests/plan_ref.py
 (plain host references, anchored by tests/test_plan_ref_cpu.py):
   csrc/plan.hip     pbn_class_gate, pbn_local_plan, pbn_proposal_offsets, pbn_batch_starts
-  csrc/stages.hip   pbn_local_scene_rows_dev, pbn_gather_pad_rows_dev, pbn_mlp_rows_dev, pbn_mask_count_dev,
-                    pbn_proposal_rows_dev (against their size-exact siblings on the first min(n, cap) rows)
+  csrc/front.hip    pbn_local_scene_rows, pbn_gather_pad_rows, pbn_mask_count, pbn_proposal_rows
+  csrc/heads.hip    pbn_mlp_rows (each with a device count against its size-exact call, NULL count, on the first
+                    min(n, cap) rows)
 No model, no scene generator: every input is built here from a fixed seed, at the sizes where the kernels change path (a
 second chunk of a scan, more clusters than lanes, counts at and beyond a capacity).  Every comparison is exact: integers
 with array_equal, floats bit for bit.  Every output lies inside a larger buffer filled with a byte pattern that must
@@ -597,7 +598,7 @@ def test_local_scene_rows_dev(dtype):
             pi, rsn, co, fe = (Guarded(Rw, torch.int64), Guarded(Rw, torch.int64), Guarded(Rw * 4, torch.int32),
                                Guarded(Rw * ld, dtype))
             cnt = _counts(ENTRIES=n_ent, ROWS=n_rows)
-            rc = N.lib().pbn_local_scene_rows_dev(
+            rc = N.lib().pbn_local_scene_rows(
                 N.ptr(d["rs"]), N.ptr(d["em"]), N.ptr(d["es"]), N.ptr(d["ew"]), E, Rw, VP(cnt.data_ptr() + 4 * R.CNT_ENTRIES),
                 VP(cnt.data_ptr() + 4 * R.CNT_ROWS), N.ptr(d["mi"]), N.ptr(d["ii"]), N.ptr(d["xyz"]),
                 stage_ops.reciprocal_f32(voxel), VP(d["pf"].data_ptr()), d["pf"].stride(0), c, VP(d["sp"].data_ptr()), 1, None,
@@ -620,11 +621,11 @@ def test_gather_pad_rows_dev(two_level):
     idx2 = _dev(rng.permutation(n_in), np.int64) if two_level else None
     idx = _dev(rng.integers(0, n_in, cap), np.int64)
     es = 2
-    # the size-exact sibling has one index level: resolve the second on the host side of the call
+    # the size-exact call (NULL count) with one index level: the second is resolved on the host side of the call
     flat = idx2[idx] if two_level else idx
     exact = torch.empty(cap, width_out, dtype=torch.bfloat16, device=DEV)
-    rc = N.lib().pbn_gather_pad_rows(VP(x.data_ptr()), width * es, width * es, N.ptr(flat), cap, VP(exact.data_ptr()),
-                                     width_out * es, N.current_stream())
+    rc = N.lib().pbn_gather_pad_rows(VP(x.data_ptr()), width * es, width * es, N.ptr(flat), None, cap, None,
+                                     VP(exact.data_ptr()), width_out * es, N.current_stream())
     assert rc == 0
     want = R.gather_pad_rows(x.cpu().view(torch.int16).numpy(), idx.cpu().numpy(), None if idx2 is None else idx2.cpu().numpy(),
                              cap, width_out)
@@ -632,8 +633,8 @@ def test_gather_pad_rows_dev(two_level):
     for n in _ns(cap) + [None]:
         out = Guarded(cap * width_out, torch.bfloat16)
         nd = None if n is None else _dev([n], np.int32)
-        rc = N.lib().pbn_gather_pad_rows_dev(VP(x.data_ptr()), width * es, width * es, N.ptr(idx), N.ptr(idx2), cap, N.ptr(nd),
-                                             out.ptr, width_out * es, N.current_stream())
+        rc = N.lib().pbn_gather_pad_rows(VP(x.data_ptr()), width * es, width * es, N.ptr(idx), N.ptr(idx2), cap, N.ptr(nd),
+                                         out.ptr, width_out * es, N.current_stream())
         assert rc == 0
         torch.cuda.synchronize()
         kk = R.dev_rows(n, cap)
@@ -649,7 +650,7 @@ def _head(rng, hidden, n_out):
 
 def _mlp_exact(h, x, idx_a, idx_b, n, sigmoid, dtype):
     out = torch.empty(max(n, 1), h["n_out"], dtype=dtype, device=DEV)
-    rc = N.lib().pbn_mlp_rows(VP(x.data_ptr()), x.stride(0), 32, N.ptr(idx_a), N.ptr(idx_b), int(n), N.ptr(h["w1"]),
+    rc = N.lib().pbn_mlp_rows(VP(x.data_ptr()), x.stride(0), -1, 32, N.ptr(idx_a), N.ptr(idx_b), int(n), None, N.ptr(h["w1"]),
                               N.ptr(h["scale"]), N.ptr(h["shift"]), N.ptr(h["slope"]), h["hidden"], N.ptr(h["w2"]), N.ptr(h["b2"]),
                               h["n_out"], int(sigmoid), VP(out.data_ptr()), h["n_out"], _DT[dtype], N.current_stream())
     assert rc == 0
@@ -683,10 +684,10 @@ def test_mlp_rows_dev(dtype, n_out, sigmoid, hidden):
     for n in _ns(cap) + [None]:
         out = Guarded(cap * n_out, dtype)
         nd = None if n is None else _dev([n], np.int32)
-        rc = N.lib().pbn_mlp_rows_dev(VP(x.data_ptr()), x.stride(0), in_rows, 32, N.ptr(idx_a), N.ptr(idx_b), cap, N.ptr(nd),
-                                      N.ptr(h["w1"]), N.ptr(h["scale"]), N.ptr(h["shift"]), N.ptr(h["slope"]), hidden,
-                                      N.ptr(h["w2"]), N.ptr(h["b2"]), n_out, int(sigmoid), out.ptr, n_out, _DT[dtype],
-                                      N.current_stream())
+        rc = N.lib().pbn_mlp_rows(VP(x.data_ptr()), x.stride(0), in_rows, 32, N.ptr(idx_a), N.ptr(idx_b), cap, N.ptr(nd),
+                                  N.ptr(h["w1"]), N.ptr(h["scale"]), N.ptr(h["shift"]), N.ptr(h["slope"]), hidden,
+                                  N.ptr(h["w2"]), N.ptr(h["b2"]), n_out, int(sigmoid), out.ptr, n_out, _DT[dtype],
+                                  N.current_stream())
         assert rc == 0
         torch.cuda.synchronize()
         kk = R.dev_rows(n, cap)
@@ -699,7 +700,7 @@ def test_mlp_rows_dev(dtype, n_out, sigmoid, hidden):
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_mask_count_offsets_proposal_rows_dev_chain(dtype):
-    """pbn_mask_count_dev -> pbn_proposal_offsets -> pbn_proposal_rows_dev as the planned forward chains them: one counts block,
+    """pbn_mask_count -> pbn_proposal_offsets -> pbn_proposal_rows with device counts as the planned forward chains them: one counts block,
     the row count read from counts[ROWS], the scene count from counts[SCENES]."""
     rng = np.random.default_rng(54)
     lib = N.lib()
@@ -728,18 +729,18 @@ def test_mask_count_offsets_proposal_rows_dev_chain(dtype):
         counts = _counts(ROWS=n, SCENES=n_scenes, ENTRIES=77)
         cptr = counts.data_ptr()
         per, blk = Guarded(s_cap, torch.int32), Guarded(n_blocks, torch.int32)
-        rc = lib.pbn_mask_count_dev(VP(score.data_ptr()), 1, thd, N.ptr(row_scene), cap, VP(cptr + 4 * R.CNT_ROWS), s_cap,
-                                    _DT[dtype], per.ptr, blk.ptr, N.current_stream())
+        rc = lib.pbn_mask_count(VP(score.data_ptr()), 1, thd, N.ptr(row_scene), cap, VP(cptr + 4 * R.CNT_ROWS), s_cap,
+                                _DT[dtype], per.ptr, blk.ptr, N.current_stream())
         assert rc == 0
         po, al, de = Guarded(s_cap + 1, torch.int64), Guarded(s_cap, torch.int64), Guarded(s_cap, torch.int32)
         rc = lib.pbn_proposal_offsets(per.ptr, s_cap, po.ptr, al.ptr, de.ptr, VP(cptr), N.current_stream())
         assert rc == 0
         pidx, pms, pco, pfe = (Guarded(cap * 2, torch.int64), Guarded(cap, dtype), Guarded(cap * 4, torch.int32),
                                Guarded(cap * c, dtype))
-        rc = lib.pbn_proposal_rows_dev(VP(score.data_ptr()), 1, thd, N.ptr(row_scene), N.ptr(point_idx), cap,
-                                       VP(cptr + 4 * R.CNT_ROWS), de.ptr, blk.ptr, N.ptr(xyz), float(np.float32(scale)),
-                                       stage_ops.reciprocal_f32(voxel), VP(feat.data_ptr()), feat.stride(0), c, _DT[dtype],
-                                       pidx.ptr, pms.ptr, pco.ptr, pfe.ptr, N.current_stream())
+        rc = lib.pbn_proposal_rows(VP(score.data_ptr()), 1, thd, N.ptr(row_scene), N.ptr(point_idx), cap,
+                                   VP(cptr + 4 * R.CNT_ROWS), de.ptr, blk.ptr, N.ptr(xyz), float(np.float32(scale)),
+                                   stage_ops.reciprocal_f32(voxel), VP(feat.data_ptr()), feat.stride(0), c, _DT[dtype],
+                                   pidx.ptr, pms.ptr, pco.ptr, pfe.ptr, N.current_stream())
         assert rc == 0
         torch.cuda.synchronize()
         # ---- the size-exact siblings on the first kk rows ----

@@ -107,7 +107,7 @@ def test_overflow_is_reported_not_written(model):
     with pytest.raises(planned.CapacityOverflow):
         planned.PlannedForward(model, small, dtype=torch.float32)(*_args(b), teacher=t)
     # only level 0 of the score lineage too small: the head behind that U-Net gathers through index tables that name rows
-    # beyond the slab -- pbn_mlp_rows_dev bounds them by the slab's row capacity (zeros, no read past the allocation)
+    # beyond the slab -- pbn_mlp_rows bounds them by the slab's row capacity (zeros, no read past the allocation)
     for lv in ("lv3", "lv2"):
         small = planned.Capacities(**{k: getattr(cap, k) for k in cap.FIELDS})
         setattr(small, lv, [max(1, getattr(cap, lv)[0] // 2)] + list(getattr(cap, lv)[1:]))

@@ -1,4 +1,4 @@
-"""GPU tier: the fused stage-glue launches (csrc/stages.hip) against the tensor-op form they replace
+"""GPU tier: the fused stage-glue launches (csrc/front.hip, csrc/heads.hip) against the tensor-op form they replace
 (/root/reference/network/PBNet.py:182-247 and friends).  Integer outputs bit-exact; feature rows bit-exact (copies)."""
 import numpy as np
 import pytest
@@ -73,10 +73,37 @@ def test_gather_pad_rows():
     x = torch.randn(1000, 34, device=DEV).to(torch.bfloat16)
     idx = torch.randperm(1000, device=DEV)[:777]
     out = torch.empty(777, 40, dtype=torch.bfloat16, device=DEV)
-    rc = N.lib().pbn_gather_pad_rows(ctypes.c_void_p(x.data_ptr()), 68, 68, ctypes.c_void_p(idx.data_ptr()), 777,
+    rc = N.lib().pbn_gather_pad_rows(ctypes.c_void_p(x.data_ptr()), 68, 68, ctypes.c_void_p(idx.data_ptr()), None, 777, None,
                                      ctypes.c_void_p(out.data_ptr()), 80, N.current_stream())
     assert rc == 0
     assert torch.equal(out[:, :34], x[idx]) and (out[:, 34:] == 0).all()
+
+
+@pytest.mark.parametrize("which", ["n_ent_dev", "n_rows_dev"])
+def test_local_scene_rows_wants_both_counts_or_neither(which):
+    """pbn_local_scene_rows with exactly one of its two device counts: PBN_ERR_ARG (-1), decided before any launch -- the outputs
+    keep their pattern."""
+    from pbnet_amd import _native as N
+    n_rows, c = 5, 32
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=DEV)
+    row_start, zero = i32([0, n_rows]), i32([0])
+    weight = torch.ones(1, device=DEV)
+    member_idx = torch.arange(n_rows, dtype=torch.int32, device=DEV)
+    ins_ind = torch.arange(n_rows, dtype=torch.int64, device=DEV)
+    xyz = torch.rand(n_rows, 3, device=DEV)
+    feat, score = torch.randn(n_rows, c, device=DEV), torch.rand(n_rows, 1, device=DEV)
+    point_idx = torch.full((n_rows,), -7, dtype=torch.int64, device=DEV)
+    row_scene, coords = point_idx.clone(), torch.full((n_rows, 4), -7, dtype=torch.int32, device=DEV)
+    out = torch.full((n_rows, c + 2), -7.0, device=DEV)
+    count = i32([n_rows if which == "n_rows_dev" else 1])
+    rc = N.lib().pbn_local_scene_rows(
+        N.ptr(row_start), N.ptr(zero), N.ptr(zero), N.ptr(weight), 1, n_rows, N.ptr(count) if which == "n_ent_dev" else None,
+        N.ptr(count) if which == "n_rows_dev" else None, N.ptr(member_idx), N.ptr(ins_ind), N.ptr(xyz),
+        stage_ops.reciprocal_f32(0.02), N.ptr(feat), c, c, N.ptr(score), 1, None, 0, N.ptr(point_idx), N.ptr(row_scene),
+        N.ptr(coords), N.ptr(out), c + 2, N.current_stream())
+    assert rc == -1
+    torch.cuda.synchronize()
+    assert (point_idx == -7).all() and (row_scene == -7).all() and (coords == -7).all() and (out == -7.0).all()
 
 
 @pytest.mark.parametrize("dtype,tol", [(torch.float32, 1e-5), (torch.bfloat16, 2e-2)])
