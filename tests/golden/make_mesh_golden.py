@@ -6,7 +6,11 @@
   * face_normal / vertex_normal, taken out of datasets/scannetv2/decode_scannet.py with `ast` and exec'd (importing the
     module would start its multiprocessing Pool over the dataset).
 
-    python tests/golden/make_mesh_golden.py [/path/to/reference]      # writes tests/golden/mesh_*.npz
+    python tests/golden/make_mesh_golden.py [/path/to/reference [fixture ...]]      # writes tests/golden/mesh_*.npz
+
+mesh_designed.npz is of another kind: the designed S and W cases of tests/mesh_cases.py whose sup does not depend on the order of
+tied weights (ascending and descending agree, no NaN weight), each with its own k_thresh and seg_min_verts, through the same
+compiled segmentator.  Inputs and sup only, under "<case>.<array>" keys, with the case names under "names".
 
 Nothing compiled and no reference text is written to the repository: only the .npz data.
 
@@ -24,9 +28,11 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 import mesh_ref  # noqa: E402
 
 REF = sys.argv[1] if len(sys.argv) > 1 else "/root/reference"
+ONLY = sys.argv[2:]                      # fixture names to write; none = all
 K_THRESH, MIN_VERTS = 0.01, 20
 
 
@@ -44,15 +50,15 @@ def load_reference():
     return seg, ns["vertex_normal"]
 
 
-def ref_segment_mesh(seg, xyz, faces):
+def ref_segment_mesh(seg, xyz, faces, k_thresh=K_THRESH, min_verts=MIN_VERTS):
     index = seg.segment_mesh(torch.from_numpy(xyz.astype(np.float32)), torch.from_numpy(faces.astype(np.int64)),
-                             K_THRESH, MIN_VERTS)
+                             k_thresh, min_verts)
     return torch.unique(index, return_inverse=True)[1].numpy().astype(np.int64)
 
 
-def ref_segment_point(seg, xyz, normals, edges):
+def ref_segment_point(seg, xyz, normals, edges, k_thresh=K_THRESH, min_verts=MIN_VERTS):
     index = seg.segment_point(torch.from_numpy(xyz.astype(np.float32)), torch.from_numpy(normals.astype(np.float32)),
-                              torch.from_numpy(edges.astype(np.int64)), K_THRESH, MIN_VERTS)
+                              torch.from_numpy(edges.astype(np.int64)), k_thresh, min_verts)
     return torch.unique(index, return_inverse=True)[1].numpy().astype(np.int64)
 
 
@@ -167,10 +173,36 @@ def centred(v, rng):
     return colours, vertices[:, :3] - vertices[:, :3].mean(0), vertices[:, 3:] / 127.5 - 1
 
 
+def designed(seg):
+    """The tie-free S and W cases of tests/mesh_cases.py through the compiled segmentator: inputs and its sup."""
+    import mesh_cases
+    names = [n for n in mesh_cases.SMALL if n[0] in "SW" and mesh_cases.tie_free(n)]
+    arrays = {"names": np.array(names)}
+    for n in names:
+        c = mesh_cases.case(n)
+        k, m = float(np.float32(c["k_thresh"])), int(c["seg_min_verts"])
+        if c["mode"] == "mesh":
+            sup = ref_segment_mesh(seg, c["xyz"], c["faces"], k, m)
+            arrays.update({n + ".xyz": c["xyz"], n + ".faces": c["faces"]})
+        else:
+            sup = ref_segment_point(seg, c["xyz"], c["normals"], c["edges"], k, m)
+            arrays.update({n + ".xyz": c["xyz"], n + ".normals": c["normals"], n + ".edges": c["edges"]})
+        arrays.update({n + ".sup": sup, n + ".k_thresh": np.float32(k), n + ".seg_min_verts": np.int32(m)})
+        print("mesh_designed %-22s V=%d segments=%d %s" % (n, c["xyz"].shape[0], sup.max() + 1, "== mesh_ref" if np.array_equal(
+            sup, mesh_cases.sup_of(c)) else "DIFFERS from mesh_ref: %s" % sup.tolist()))
+    path = os.path.join(HERE, "mesh_designed.npz")
+    np.savez_compressed(path, **arrays)
+    print("mesh_designed: %d cases %d bytes" % (len(names), os.path.getsize(path)))
+
+
 def main():
     seg, vertex_normal = load_reference()
+    if not ONLY or "mesh_designed" in ONLY:
+        designed(seg)
     cases = {"mesh_room": room, "mesh_flat": flat, "mesh_oddities": oddities}
     for name, make in cases.items():
+        if ONLY and name not in ONLY:
+            continue
         for attempt in range(50):
             seed = 1000 * len(name) + attempt
             v, f = make(seed)
@@ -191,6 +223,8 @@ def main():
                             seg_min_verts=np.int32(MIN_VERTS))
         print("%s: V=%d F=%d segments=%d ids_exact=%s seed=%d %d bytes" % (name, xyz.shape[0], f.shape[0], sup.max() + 1,
                                                                          ids_exact, seed, os.path.getsize(path)))
+    if ONLY and "mesh_point" not in ONLY:
+        return
     for attempt in range(50):
         seed = 4242 + attempt
         p, q, e = knn_case(seed)

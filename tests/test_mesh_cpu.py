@@ -2,6 +2,9 @@
 outputs (tests/golden/mesh_*.npz, written by make_mesh_golden.py from decode_scannet.py's numpy normals and the compiled
 segmentator), the PLY reader, and decode_mesh's host arithmetic.
 
+mesh_designed.npz is of another kind: the designed S and W cases of tests/mesh_cases.py whose sup does not depend on the order of
+tied weights, each with the compiled segmentator's sup: the reference's own word on `<=`, `<`, the float32 threshold and dot2 > 0.
+
 sup: the fixtures are committed only when the reference's partition equals mesh_ref's under both tie orders (the
 reference's std::sort leaves tied weights unordered); the ids are compared element by element where the generator
 recorded ids_exact."""
@@ -12,19 +15,23 @@ import numpy as np
 import pytest
 import torch
 
+import mesh_cases
 import mesh_ref
 from pbnet_amd import mesh, scene_io
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-MESHES = sorted(p for p in glob.glob(os.path.join(HERE, "golden", "mesh_*.npz")) if not p.endswith("mesh_point.npz"))
+FIXTURES = sorted(glob.glob(os.path.join(HERE, "golden", "mesh_*.npz")))
+MESHES = [p for p in FIXTURES if not p.endswith(("mesh_point.npz", "mesh_designed.npz"))]
 POINT = os.path.join(HERE, "golden", "mesh_point.npz")
+DESIGNED = os.path.join(HERE, "golden", "mesh_designed.npz")
 
 
 def test_fixture_set():
     names = sorted(os.path.basename(p)[:-4] for p in MESHES)
     assert names == ["mesh_flat", "mesh_oddities", "mesh_room"]
     assert os.path.exists(POINT)
-    for p in MESHES + [POINT]:
+    assert sorted(os.path.basename(p)[:-4] for p in FIXTURES) == ["mesh_designed", "mesh_flat", "mesh_oddities", "mesh_point", "mesh_room"]
+    for p in FIXTURES:
         assert os.path.getsize(p) < 1 << 20
 
 
@@ -49,6 +56,16 @@ def test_restatement_reproduces_point_fixture():
         assert mesh_ref.same_partition(sup, g["sup"]), ties
         if bool(g["ids_exact"]):
             assert np.array_equal(sup, g["sup"]), ties
+
+
+def test_restatement_reproduces_designed_fixture():
+    """Ids, not only partitions: the cases were recorded because both tie orders give one sup."""
+    g = np.load(DESIGNED)
+    assert len(g["names"]) >= 12
+    for name, mode, arrays, k, m, sup in mesh_cases.designed_cases(g):
+        segment = mesh_ref.segment_mesh if mode == "mesh" else mesh_ref.segment_point
+        for ties in ("asc", "desc"):
+            assert np.array_equal(segment(*arrays, k, m, ties=ties), sup), (name, ties)
 
 
 def test_fixtures_cover_the_issue_cases():

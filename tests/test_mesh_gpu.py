@@ -1,7 +1,8 @@
 """GPU tier of the mesh decode (csrc/mesh.hip through pbnet_amd.mesh).
 
 * every fixture of tests/golden/mesh_*.npz (the reference's own outputs): nl bit for bit, the sup partition equal, and
-  sup equal element by element where the generator recorded ids_exact;
+  sup equal element by element where the generator recorded ids_exact; mesh_designed.npz (designed tie-free cases, the compiled
+  segmentator's sup): element by element;
 * a synthetic mesh of the bench scene's size (jitter, flat regions, coincident vertices) against tests/mesh_ref.py with
   the library's tie order: nl bit for bit, sup exactly; a second run bit-identical;
 * error paths: bad indices raise, 0 faces is the identity, degenerate faces give valid ids."""
@@ -12,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import mesh_cases
 import mesh_ref
 from pbnet_amd import mesh
 
@@ -19,8 +21,10 @@ pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
 HERE = os.path.dirname(os.path.abspath(__file__))
-MESHES = sorted(p for p in glob.glob(os.path.join(HERE, "golden", "mesh_*.npz")) if not p.endswith("mesh_point.npz"))
+FIXTURES = sorted(glob.glob(os.path.join(HERE, "golden", "mesh_*.npz")))
+MESHES = [p for p in FIXTURES if not p.endswith(("mesh_point.npz", "mesh_designed.npz"))]
 POINT = os.path.join(HERE, "golden", "mesh_point.npz")
+DESIGNED = [p for p in FIXTURES if p.endswith("mesh_designed.npz")]
 
 
 def _bits(t):
@@ -63,6 +67,19 @@ def test_point_fixture_parity():
         if bool(g["ids_exact"]):
             assert np.array_equal(sup, g["sup"])
         assert np.array_equal(sup, mesh_ref.segment_point(g["points"], g["normals"], g["edges"], ties="asc"))
+
+
+def test_designed_fixture_parity():
+    """mesh_designed.npz: the compiled segmentator's sup on the designed tie-free cases, element by element, both index types."""
+    assert len(DESIGNED) == 1
+    g = np.load(DESIGNED[0])
+    for name, mode, arrays, k, m, sup in mesh_cases.designed_cases(g):
+        for idx in (np.int32, np.int64):
+            if mode == "mesh":
+                got = mesh.segment_mesh(_d(arrays[0]), _d(arrays[1], idx), k, m)
+            else:
+                got = mesh.segment_point(_d(arrays[0]), _d(arrays[1]), _d(arrays[2], idx), k, m)
+            assert np.array_equal(got.cpu().numpy(), sup), (name, idx)
 
 
 def bench_mesh(seed=0, n=402):
