@@ -1054,6 +1054,70 @@ int pbn_cloud_knn_timed(const float* xyz, int n_points, int k, float cell, int32
  * when n . (viewpoint - p_i) < 0, rounded to float32.  |S| < 3 gives the zero vector.  viewpoint: device float[3]. */
 int pbn_cloud_normals(const float* xyz, int n_points, const int32_t* idx, int k, const float* viewpoint, float* nl,
                       pbn_stream_t stream);
+/* The same normals, each turned towards its own point's viewpoint: views f32[n_views,3] and view_of int32[n] (device).
+ * Mean, covariance, Jacobi and rounding are pbn_cloud_normals'; with v = views[view_of[i]] the normal is flipped when
+ * (nx * (double(v.x) - px) + ny * (double(v.y) - py)) + nz * (double(v.z) - pz) < 0, pbn_cloud_normals' expression.  A
+ * view_of[i] outside [0, n_views) leaves the eigenvector's sign as the Jacobi sweeps give it (a NaN view does too: the
+ * comparison is false).  n_views >= 0; views may be NULL only when n_views == 0. */
+int pbn_cloud_normals_views(const float* xyz, int n_points, const int32_t* idx, int k, const float* views, int n_views,
+                            const int32_t* view_of, float* nl, pbn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Posed depth frames (csrc/frames.hip): an RGB-D sequence back-projected into one compacted cloud.
+ * tests/frames_ref.py restates this contract in numpy.  Every expression is one rounded float64 operation per operator,
+ * in the order the brackets give; nothing is fused.
+ *   Inputs   depth [F,H,W] (device), depth_is_f32 = 0: uint16, z = double(d) / depth_scale; 1: float32 metres,
+ *            z = double(d).  colour uint8[F,H,W,3] (device) on the depth grid, or NULL.  pose double[F,16] on the HOST,
+ *            camera to world, row-major 4x4 (r00 r01 r02 t0 | r10 ... | r20 ... | bottom row, which is not read).  intr
+ *            double[F,4] on the HOST: fx, fy, cx, cy.  Both are read before the call returns.
+ *   Limits   checked on the host before any launch, else PBN_ERR_ARG: F, H, W >= 0; F * H * W <= 2^31 - 1; the sampled
+ *            pixels F * ceil(H / stride) * ceil(W / stride) <= 2^28; every fx and fy and depth_scale finite and > 0;
+ *            depth_min <= depth_max (neither NaN); stride >= 1.
+ *   Sampling pixel (u = column, v = row; the pixel centre IS the integer) is considered when u % stride == 0 and
+ *            v % stride == 0.  Its id is (f * H + v) * W + u.
+ *   Valid    (a) the 12 numbers of the top three rows of frame f's pose are finite (a lost frame, ScanNet's -inf pose,
+ *            contributes nothing); (b) z is measured: finite, z > 0 and depth_min <= z <= depth_max (a uint16 0 is no
+ *            measurement); (c) with edge > 0 (a ratio; <= 0 or NaN = off): no pixel (u-1,v), (u+1,v), (u,v-1), (u,v+1) --
+ *            at FULL resolution whatever the stride -- that lies inside the image and whose zn is measured by (b) has
+ *            fabs(zn - z) > edge * z; a neighbour outside the image or without a measurement makes no edge; (d) the three
+ *            float32 world coordinates are finite.
+ *   World    xc = ((double(u) - cx) * z) / fx; yc = ((double(v) - cy) * z) / fy;
+ *            X = ((r00 * xc + r01 * yc) + r02 * z) + t0, Y and Z likewise from rows 1 and 2; each rounded to float32 once,
+ *            on the store.
+ *   Outputs  rows in ascending pixel id: xyz f32[N,3]; rgb f32[N,3] = the colour bytes as 0..255 floats (with colour);
+ *            pixel int32[N].  frame_start int32[F+1]: frame f owns rows frame_start[f] .. frame_start[f+1] - 1, a skipped
+ *            frame none.  result int32[2] (device): [0] status, [1] N -- one read-back gives both.
+ * Two calls around that read-back: pbn_frames_count tests every sampled pixel (a wave64 ballot and popcount, one count per
+ * workgroup), scans the counts (exclusive, into the workspace) and writes frame_start and result; the caller reads result,
+ * allocates exactly N rows, and pbn_frames_write -- same arguments, same workspace, untouched in between -- tests the pixels
+ * again and stores every wave's survivors contiguously at the workgroup's offset + the wave's offset + the lane's rank in
+ * the ballot.  No atomics touch the order: two runs give the same bytes.  A workgroup's pbn_frames_block_pixels() sampled
+ * pixels lie in one frame.  pbn_frames_write writes no row at or beyond n_rows: when its own count says there is one
+ * (depth changed between the calls, or n_rows is not result[1]) it sets bit 1 of result[0], and no output is to be trusted.
+ * Only the _timed entries synchronise.
+ * ------------------------------------------------------------------------------------------------------------ */
+/* bytes of workspace for pbn_frames_count / pbn_frames_write; 0 = sizes out of range (see Limits) */
+size_t pbn_frames_workspace_bytes(int n_frames, int height, int width, int stride);
+int pbn_frames_block_pixels(void);                              /* sampled pixels per workgroup: 1024 */
+int pbn_frames_count(const void* depth, int depth_is_f32, const uint8_t* colour, const double* pose, const double* intr,
+                     int n_frames, int height, int width, double depth_scale, double depth_min, double depth_max, int stride,
+                     double edge, int32_t* frame_start, int32_t* result, void* workspace, size_t workspace_bytes,
+                     pbn_stream_t stream);
+/* n_rows = result[1] as read back; xyz, rgb (NULL exactly when colour is) and pixel hold n_rows rows */
+int pbn_frames_write(const void* depth, int depth_is_f32, const uint8_t* colour, const double* pose, const double* intr,
+                     int n_frames, int height, int width, double depth_scale, double depth_min, double depth_max, int stride,
+                     double edge, int n_rows, float* xyz, float* rgb, int32_t* pixel, int32_t* result, void* workspace,
+                     size_t workspace_bytes, pbn_stream_t stream);
+/* Measurement variants: HIP events around the stages, SYNCHRONISE; times_ms (host): float[2] count, scan + starts for
+ * pbn_frames_count_timed; float[1] write for pbn_frames_write_timed. */
+int pbn_frames_count_timed(const void* depth, int depth_is_f32, const uint8_t* colour, const double* pose, const double* intr,
+                           int n_frames, int height, int width, double depth_scale, double depth_min, double depth_max,
+                           int stride, double edge, int32_t* frame_start, int32_t* result, void* workspace,
+                           size_t workspace_bytes, pbn_stream_t stream, float* times_ms);
+int pbn_frames_write_timed(const void* depth, int depth_is_f32, const uint8_t* colour, const double* pose, const double* intr,
+                           int n_frames, int height, int width, double depth_scale, double depth_min, double depth_max,
+                           int stride, double edge, int n_rows, float* xyz, float* rgb, int32_t* pixel, int32_t* result,
+                           void* workspace, size_t workspace_bytes, pbn_stream_t stream, float* times_ms);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Raw sensor scans (csrc/thin.hip): grid thinning to the network's pitch, statistical outlier removal over the kNN graph's

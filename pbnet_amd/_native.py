@@ -127,6 +127,11 @@ class PostBatchLayout(ctypes.Structure):
                                      "votes", "sp_label", "seg", "seg_refined", "counts2", "renumber", "total_bytes")]
 
 
+# what pbn_frames_count and pbn_frames_write share: depth, depth_is_f32, colour, pose and intr (host double arrays), F, H, W,
+# depth_scale, depth_min, depth_max, stride, edge
+_FRAMES_HEAD = [c_vp, c_int, c_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), c_int, c_int, c_int,
+                ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double]
+
 # name -> (restype, argtypes); must list every symbol of include/pbnet_hip.h (tests/test_abi.py checks this)
 SIGNATURES = {
     "pbn_version": (ctypes.c_char_p, []),
@@ -288,6 +293,14 @@ SIGNATURES = {
     "pbn_cloud_knn_timed": (c_int, [c_f32p, c_int, c_int, c_float, c_i32p, c_f32p, c_i32p, c_vp, c_size, c_vp,
                                     ctypes.POINTER(ctypes.c_float)]),
     "pbn_cloud_normals": (c_int, [c_f32p, c_int, c_i32p, c_int, c_f32p, c_f32p, c_vp]),
+    "pbn_cloud_normals_views": (c_int, [c_f32p, c_int, c_i32p, c_int, c_f32p, c_int, c_i32p, c_f32p, c_vp]),
+    "pbn_frames_workspace_bytes": (c_size, [c_int, c_int, c_int, c_int]),
+    "pbn_frames_block_pixels": (c_int, []),
+    "pbn_frames_count": (c_int, _FRAMES_HEAD + [c_i32p, c_i32p, c_vp, c_size, c_vp]),
+    "pbn_frames_count_timed": (c_int, _FRAMES_HEAD + [c_i32p, c_i32p, c_vp, c_size, c_vp, ctypes.POINTER(ctypes.c_float)]),
+    "pbn_frames_write": (c_int, _FRAMES_HEAD + [c_int, c_f32p, c_f32p, c_i32p, c_i32p, c_vp, c_size, c_vp]),
+    "pbn_frames_write_timed": (c_int, _FRAMES_HEAD + [c_int, c_f32p, c_f32p, c_i32p, c_i32p, c_vp, c_size, c_vp,
+                                                      ctypes.POINTER(ctypes.c_float)]),
     "pbn_thin_workspace_bytes": (c_size, [c_int]),
     "pbn_thin_points": (c_int, [c_f32p, c_f32p, c_int, ctypes.c_double, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, c_i32p, c_vp, c_size,
                                 c_vp]),

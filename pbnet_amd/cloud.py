@@ -99,6 +99,8 @@ _STATUS = {
     **dict.fromkeys(("fit_plane", "upright"), ((_NONFINITE,), "status %(status)d")),
     "thin_points": ((_NONFINITE, (CLOUD_EXTENT, "the cloud spans 2^21 cells or more of pitch %(pitch)r on an axis")), _SORT),
     "orient_normals": ((), "a link chain did not end (status %(status)d)"),
+    "frames_to_points": ((), "the write pass met more valid pixels than the count pass: the frames changed between the two "
+                             "(status %(status)d)"),
     "vote_labels": (((VOTE_SEM_RANGE, "a semantic label is %(n_classes)d or more"),
                      (VOTE_INS_RANGE, "an instance label is %(max_ins)d or more"),
                      (VOTE_ROW_RANGE, "a row lies outside [-1, %(m)d)")), _SORT),
@@ -158,12 +160,28 @@ def knn_graph(xyz, k=16, cell=None, times=None):
     return idx, d2
 
 
-def point_normals(xyz, idx, viewpoint=None):
+def point_normals(xyz, idx, viewpoint=None, views=None, view_of=None):
     """PCA normals over each point and its neighbours `idx` (int32 [N, k], -1 = none): float32 [N, 3] on the device, the
     float64 eigenvector of the smallest covariance eigenvalue, turned towards `viewpoint` (three numbers or a tensor; None
-    = the float64 mean of xyz).  Fewer than three points in a neighbourhood give the zero vector."""
+    = the float64 mean of xyz).  Fewer than three points in a neighbourhood give the zero vector.
+
+    With `views` (f32 [V, 3]) and `view_of` (int32 [N]), both or neither and not together with `viewpoint`, every normal is
+    turned towards its own point's viewpoint views[view_of[i]] -- the sensor position that saw the point -- by the same
+    test; a view_of outside [0, V) leaves the eigenvector's sign as it is."""
     n = _f32("xyz", xyz)
     _i32("idx", idx, n, "k")
+    if (views is None) != (view_of is None):
+        raise ValueError("point_normals: give both views and view_of, or neither")
+    if views is not None:
+        if viewpoint is not None:
+            raise ValueError("point_normals: viewpoint and views are two ways to turn the normals, give one")
+        n_views = _f32("views", views)
+        _i32("view_of", view_of, n)
+        xyz, idx, views, view_of = _device(xyz, idx, views, view_of)
+        nl = torch.empty(n, 3, dtype=torch.float32, device=xyz.device)
+        N.check(N.lib().pbn_cloud_normals_views(N.ptr(xyz), n, N.ptr(idx), int(idx.shape[1]), N.ptr(views), n_views,
+                                                N.ptr(view_of), N.ptr(nl), N.current_stream()), "pbn_cloud_normals_views")
+        return nl
     xyz, idx = _device(xyz, idx)
     k = int(idx.shape[1])
     if viewpoint is None:

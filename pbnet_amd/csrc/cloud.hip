@@ -46,6 +46,8 @@
 // Normals: one lane per point, float64, no atomics.  S = the point, then its valid neighbours in rank order; mean, then
 // the six covariance sums, in that order; the eigenvector of the smallest eigenvalue by a FIXED number of cyclic Jacobi
 // sweeps (no data-dependent loop); flipped towards the viewpoint; rounded to float32.  |S| < 3 gives the zero vector.
+// pbn_cloud_normals_views runs the same kernel with a viewpoint per point (views[view_of[i]], the sensor position that saw
+// it; an index outside the views flips nothing); pbn_cloud_normals is the case of one view and no view_of.
 //
 // Fixed radius (pbn_cloud_radius_count / pbn_cloud_radius_raw_index): the same grid front (cloud_front below, which
 // pbn_cloud_knn runs too) with a cell a hair above the radius, and shell_walk with a radius in place of a k-th neighbour.
@@ -380,37 +382,51 @@ __global__ __launch_bounds__(TPB) void k_radius_gather(const int* __restrict__ i
 }
 
 // ---- normals -----------------------------------------------------------------------------------------------------------
-// float64 throughout: 4 waves per SIMD leave the 128 VGPRs the rotations want (no scratch)
+// The unit eigenvector of point i's neighbourhood covariance, before any flip; false (nothing written) with |S| < 3.
+__device__ __forceinline__ bool cloud_pca(const float* __restrict__ xyz, int n, const int* __restrict__ idx, int k, int i,
+                                          double& px, double& py, double& pz, double& nx, double& ny, double& nz) {
+    px = (double)xyz[3 * (size_t)i]; py = (double)xyz[3 * (size_t)i + 1]; pz = (double)xyz[3 * (size_t)i + 2];
+    double sx = px, sy = py, sz = pz;
+    int m = 1;
+    for (int r = 0; r < k; ++r) {
+        const int j = idx[(size_t)i * k + r];
+        if ((unsigned)j >= (unsigned)n) continue;                            // -1 (or anything out of range) is no neighbour
+        sx = sx + (double)xyz[3 * (size_t)j]; sy = sy + (double)xyz[3 * (size_t)j + 1]; sz = sz + (double)xyz[3 * (size_t)j + 2];
+        ++m;
+    }
+    if (m < 3) return false;
+    const double mx = sx / (double)m, my = sy / (double)m, mz = sz / (double)m;
+    double dx = px - mx, dy = py - my, dz = pz - mz;
+    double a00 = dx * dx, a01 = dx * dy, a02 = dx * dz, a11 = dy * dy, a12 = dy * dz, a22 = dz * dz;
+    for (int r = 0; r < k; ++r) {
+        const int j = idx[(size_t)i * k + r];
+        if ((unsigned)j >= (unsigned)n) continue;
+        dx = (double)xyz[3 * (size_t)j] - mx; dy = (double)xyz[3 * (size_t)j + 1] - my; dz = (double)xyz[3 * (size_t)j + 2] - mz;
+        a00 = a00 + dx * dx; a01 = a01 + dx * dy; a02 = a02 + dx * dz;
+        a11 = a11 + dy * dy; a12 = a12 + dy * dz; a22 = a22 + dz * dz;
+    }
+    jacobi_smallest(a00, a01, a02, a11, a12, a22, nx, ny, nz);         // scan_dev.h
+    return true;
+}
+
+// float64 throughout: 4 waves per SIMD leave the 128 VGPRs the rotations want (no scratch).  With view_of (non-null) point
+// i looks at views[view_of[i]], and at nothing (no flip) when that index lies outside [0, n_views); without it every point
+// looks at views[0].
 __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_cloud_normals(const float* __restrict__ xyz, int n, const int* __restrict__ idx,
-                                                       int k, const float* __restrict__ viewpoint, float* __restrict__ nl) {
+                                                       int k, const float* __restrict__ views, int n_views,
+                                                       const int* __restrict__ view_of, float* __restrict__ nl) {
     for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) {
-        const double px = (double)xyz[3 * (size_t)i], py = (double)xyz[3 * (size_t)i + 1], pz = (double)xyz[3 * (size_t)i + 2];
-        double sx = px, sy = py, sz = pz;
-        int m = 1;
-        for (int r = 0; r < k; ++r) {
-            const int j = idx[(size_t)i * k + r];
-            if ((unsigned)j >= (unsigned)n) continue;                        // -1 (or anything out of range) is no neighbour
-            sx = sx + (double)xyz[3 * (size_t)j]; sy = sy + (double)xyz[3 * (size_t)j + 1]; sz = sz + (double)xyz[3 * (size_t)j + 2];
-            ++m;
-        }
-        if (m < 3) {
+        double px, py, pz, nx, ny, nz;
+        if (!cloud_pca(xyz, n, idx, k, i, px, py, pz, nx, ny, nz)) {
             nl[3 * (size_t)i] = 0.0f; nl[3 * (size_t)i + 1] = 0.0f; nl[3 * (size_t)i + 2] = 0.0f;
             continue;
         }
-        const double mx = sx / (double)m, my = sy / (double)m, mz = sz / (double)m;
-        double dx = px - mx, dy = py - my, dz = pz - mz;
-        double a00 = dx * dx, a01 = dx * dy, a02 = dx * dz, a11 = dy * dy, a12 = dy * dz, a22 = dz * dz;
-        for (int r = 0; r < k; ++r) {
-            const int j = idx[(size_t)i * k + r];
-            if ((unsigned)j >= (unsigned)n) continue;
-            dx = (double)xyz[3 * (size_t)j] - mx; dy = (double)xyz[3 * (size_t)j + 1] - my; dz = (double)xyz[3 * (size_t)j + 2] - mz;
-            a00 = a00 + dx * dx; a01 = a01 + dx * dy; a02 = a02 + dx * dz;
-            a11 = a11 + dy * dy; a12 = a12 + dy * dz; a22 = a22 + dz * dz;
+        const int w = view_of ? view_of[i] : 0;
+        if ((unsigned)w < (unsigned)n_views) {
+            const float* __restrict__ vp = views + 3 * (size_t)w;
+            const double dot = (nx * ((double)vp[0] - px) + ny * ((double)vp[1] - py)) + nz * ((double)vp[2] - pz);
+            if (dot < 0.0) { nx = -nx; ny = -ny; nz = -nz; }
         }
-        double nx, ny, nz;
-        jacobi_smallest(a00, a01, a02, a11, a12, a22, nx, ny, nz);     // scan_dev.h
-        const double dot = (nx * ((double)viewpoint[0] - px) + ny * ((double)viewpoint[1] - py)) + nz * ((double)viewpoint[2] - pz);
-        if (dot < 0.0) { nx = -nx; ny = -ny; nz = -nz; }
         nl[3 * (size_t)i] = (float)nx; nl[3 * (size_t)i + 1] = (float)ny; nl[3 * (size_t)i + 2] = (float)nz;
     }
 }
@@ -600,7 +616,18 @@ extern "C" int pbn_cloud_normals(const float* xyz, int n_points, const int32_t* 
     if ((n_points && (!xyz || !idx || !nl)) || !viewpoint) return PBN_ERR_ARG;
     if (n_points == 0) return PBN_OK;
     hipLaunchKernelGGL(k_cloud_normals, dim3(grid_for(n_points)), dim3(TPB), 0, (hipStream_t)stream, xyz, n_points, idx, k,
-                       viewpoint, nl);
+                       viewpoint, 1, (const int*)nullptr, nl);
+    PBN_LAUNCH_CHECK();
+    return PBN_OK;
+}
+
+extern "C" int pbn_cloud_normals_views(const float* xyz, int n_points, const int32_t* idx, int k, const float* views, int n_views,
+                                       const int32_t* view_of, float* nl, pbn_stream_t stream) {
+    if (bad_sizes(n_points, k) || n_views < 0) return PBN_ERR_ARG;
+    if ((n_points && (!xyz || !idx || !nl || !view_of)) || (n_views && !views)) return PBN_ERR_ARG;
+    if (n_points == 0) return PBN_OK;
+    hipLaunchKernelGGL(k_cloud_normals, dim3(grid_for(n_points)), dim3(TPB), 0, (hipStream_t)stream, xyz, n_points, idx, k,
+                       views, n_views, view_of, nl);
     PBN_LAUNCH_CHECK();
     return PBN_OK;
 }

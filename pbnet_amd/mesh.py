@@ -6,17 +6,22 @@ segment_mesh     lib/segmentator segment_mesh + main.py's torch.unique relabel (
 segment_point    lib/segmentator segment_point (caller-given normals and E x 2 edges)
 decode_mesh      f_test without the file writes: mean-centred xyz, rgb / 127.5 - 1, nl, face (int32), sup
 decode_points    decode_mesh without faces: xyz, rgb, nl, sup
+decode_frames    decode_points for posed depth frames: frames_to_points, then the same chain, normals towards each sensor
 save_decoded     the reference's `<scene>_{xyz,rgb,nl,face,sup}.npy` (+ labels when given) through scene_io
 
 The rest lives in two other modules and is reachable here as before.
 read_ply, read_ply_points, write_ply   ply.py, numpy only: ScanNet's binary_little_endian meshes and vertex-only scans
 cloud.py, scans without a mesh (csrc/cloud.hip): segment_point's normals and edges from the points alone.
 knn_graph        the exact k nearest neighbours over a uniform grid, bit for bit a float32 brute force
-point_normals    float64 PCA normals over each point and its neighbours, turned towards a viewpoint
+point_normals    float64 PCA normals over each point and its neighbours, turned towards a viewpoint, or each towards its
+                 own point's sensor position (views, view_of)
 knn_edges        the graph as segment_point's E x 2 edges
 orient_normals   point_normals' signs made consistent over the graph (csrc/orient.hip), bit for bit tests/orient_ref.py
 fit_plane        the floor plane of a scan (csrc/upright.hip): RANSAC on the device, float64 refit, bit for bit tests/upright_ref.py
 upright          fit_plane and the scan rotated so that the plane's normal is +z
+frames.py, posed depth frames (csrc/frames.hip): what a depth camera hands over, before it is a cloud.
+frames_to_points depth images, poses and intrinsics back-projected into one compacted raw cloud in pixel order, every point
+                 with its pixel (hence its frame) and every frame with its sensor centre; bit for bit tests/frames_ref.py
 cloud.py, raw sensor scans (csrc/thin.hip): to the network's pitch and back.
 thin_points      one float64 centroid per occupied cell of a grid, bit for bit tests/thin_ref.py
 outlier_mask     statistical outlier removal over knn_graph's d2, sums of a fixed shape
@@ -48,12 +53,14 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import frames as _frames
 from . import scene_io
 from .cloud import (CLOUD_EXTENT, CLOUD_MAX_K, CLOUD_NONFINITE, CLOUD_SORT_SPIN, CLOUD_STAGES, CLOUD_WALK_CAP, ORIENT_STAGES,  # noqa: F401
                     RADIUS_MAX_CAP, RADIUS_STAGES, THIN_STAGES, UPRIGHT_KEYS, UPRIGHT_MAX_HYP, UPRIGHT_STAGES, VOTE_INS_RANGE,
                     VOTE_MAX_CLASSES, VOTE_MAX_INS, VOTE_ROW_RANGE, VOTE_SEM_RANGE, VOTE_STAGES, _device, _f32, _got, _scan_workspace, _upright,
                     _upright_args, carry_labels, fit_plane, knn_edges, knn_graph, orient_normals, outlier_mask, point_normals,
                     radius_count, radius_outlier_mask, radius_raw_index, raw_index, thin_points, upright, vote_labels)
+from .frames import FRAMES_STAGES, frames_to_points  # noqa: F401
 from .ply import _PLY_SCALARS, _read_ply_header, _vertex_arrays, _vertex_dtype, read_ply, read_ply_points, write_ply  # noqa: F401
 
 MESH_NORMALS, MESH_SEGMENT, MESH_SEGMENT_POINT = 0, 1, 2
@@ -200,33 +207,37 @@ def _raw_labels(name, labels, n):
     return np.ascontiguousarray(a.astype(np.int32))
 
 
-def _kept_points(xyz, colours, dev, k, pitch, outlier_ratio, outlier_radius, outlier_min_pts, upright_kw):
-    """decode_points' front for a raw scan: upload, thin_points (pitch), then knn_graph -> outlier_mask -> raw_index
+def _kept_points(xyz, colours, dev, k, pitch, outlier_ratio, outlier_radius, outlier_min_pts, upright_kw, want_first=False):
+    """decode_points' front for a raw scan: upload (host arrays; device tensors are taken as they are), thin_points (pitch), then knn_graph -> outlier_mask -> raw_index
     (outlier_ratio) or radius_outlier_mask -> radius_raw_index (outlier_radius, outlier_min_pts: no graph over the
     unfiltered points), and the compaction.  The kept points come back as host arrays -- centre_and_scale is a host numpy
     expression, so the kept M x 6 floats make one extra round trip -- with raw_index and count on the device (None when the
     points were neither thinned nor filtered) and `up`, upright's result or None.  With `upright_kw` (fit_plane's keyword arguments) the
     kept points are turned upright while they are still on the device: the returned xyz is in the upright frame, and the
-    result's "kept_xyz" holds the kept points in the sensor's frame."""
-    xyz_d = torch.from_numpy(np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)).to(dev)
-    col_d = torch.from_numpy(np.ascontiguousarray(colours, np.float32).reshape(-1, 3)).to(dev)
+    result's "kept_xyz" holds the kept points in the sensor's frame.  `first` (with want_first) is the lowest raw member of
+    every kept row -- thin_points' first, compacted by the filter's keep -- or None when nothing was thinned or filtered."""
+    xyz_d, col_d = (t if torch.is_tensor(t) and t.is_cuda else
+                    torch.from_numpy(np.ascontiguousarray(t, np.float32).reshape(-1, 3)).to(dev) for t in (xyz, colours))
     n_raw = int(xyz_d.shape[0])
-    inverse = count = None
+    inverse = count = first = None
     if pitch is not None:
         th = thin_points(xyz_d, col_d, pitch)
-        xyz_d, col_d, count, inverse = th["xyz"], th["rgb"], th["count"], th["inverse"]
+        xyz_d, col_d, count, inverse, first = th["xyz"], th["rgb"], th["count"], th["inverse"], th["first"]
     elif outlier_ratio is not None or outlier_radius is not None:
         count = torch.ones(n_raw, dtype=torch.int32, device=dev)
         inverse = torch.arange(n_raw, dtype=torch.int32, device=dev)
+        first = inverse
+    keep = None
     if outlier_ratio is not None:
         idx, d2 = knn_graph(xyz_d, k=k)
         keep, _ = outlier_mask(d2, outlier_ratio)
         inverse = raw_index(inverse, keep, idx)
-        xyz_d, col_d, count = xyz_d[keep], col_d[keep], count[keep]
     elif outlier_radius is not None:
         keep = radius_outlier_mask(xyz_d, outlier_radius, outlier_min_pts)
         inverse = radius_raw_index(inverse, keep, xyz_d, outlier_radius)
+    if keep is not None:
         xyz_d, col_d, count = xyz_d[keep], col_d[keep], count[keep]
+        first = first[keep] if want_first else None
     up = None
     if upright_kw is not None:
         up = upright(xyz_d, **upright_kw)
@@ -235,7 +246,8 @@ def _kept_points(xyz, colours, dev, k, pitch, outlier_ratio, outlier_radius, out
                              "check threshold, up_hint and below_frac" % (int(xyz_d.shape[0]), upright_kw["hypotheses"],
                                                                           int(up["info"][6])))
         up["kept_xyz"], xyz_d = xyz_d, up["xyz"]
-    return types.SimpleNamespace(xyz=xyz_d.cpu().numpy(), colours=col_d.cpu().numpy(), raw_index=inverse, count=count, up=up)
+    return types.SimpleNamespace(xyz=xyz_d.cpu().numpy(), colours=col_d.cpu().numpy(), raw_index=inverse, count=count, up=up,
+                                 first=first)
 
 
 def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpoint=None, return_graph=False, pitch=None,
@@ -283,60 +295,173 @@ def decode_points(src, device="cuda", k=16, kThresh=0.01, segMinVerts=20, viewpo
         xyz, colours = read_ply_points(src)
     else:
         xyz, colours = (t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t) for t in src)
-    if orient is not None and orient != "graph":
-        raise ValueError("decode_points: orient must be None or \"graph\", got %r" % (orient,))
-    if (sem_label is None) != (ins_label is None):
-        raise ValueError("decode_points: give both sem_label and ins_label, or neither")
-    if (outlier_radius is None) != (outlier_min_pts is None):
-        raise ValueError("decode_points: give both outlier_radius and outlier_min_pts, or neither")
-    if outlier_radius is not None and outlier_ratio is not None:
-        raise ValueError("decode_points: outlier_radius / outlier_min_pts and outlier_ratio are two filters, give one")
-    upright_kw = _upright_option(upright, pitch)
+    opts = _decode_options("decode_points", k, kThresh, segMinVerts, viewpoint, return_graph, pitch, outlier_ratio, return_kept,
+                           sem_label, ins_label, n_classes, outlier_radius, outlier_min_pts, orient, upright)
     dev = torch.device(device)
     labels = None
     if sem_label is not None:
         n_raw = int(np.asarray(xyz).reshape(-1, 3).shape[0])
         labels = [_raw_labels(name, v, n_raw) for name, v in (("sem_label", sem_label), ("ins_label", ins_label))]
         labels = [torch.from_numpy(a).to(dev) for a in labels]
+    return _decode_cloud(xyz, colours, dev, labels, opts)
+
+
+def _decode_options(what, k, kThresh, segMinVerts, viewpoint, return_graph, pitch, outlier_ratio, return_kept, sem_label, ins_label,
+                    n_classes, outlier_radius, outlier_min_pts, orient, upright):
+    """decode_points' options, checked before anything is uploaded: what _decode_cloud reads."""
+    if orient is not None and orient != "graph":
+        raise ValueError("%s: orient must be None or \"graph\", got %r" % (what, orient))
+    if (sem_label is None) != (ins_label is None):
+        raise ValueError("%s: give both sem_label and ins_label, or neither" % what)
+    if (outlier_radius is None) != (outlier_min_pts is None):
+        raise ValueError("%s: give both outlier_radius and outlier_min_pts, or neither" % what)
+    if outlier_radius is not None and outlier_ratio is not None:
+        raise ValueError("%s: outlier_radius / outlier_min_pts and outlier_ratio are two filters, give one" % what)
+    upright_kw = _upright_option(upright, pitch)
     front = pitch is not None or outlier_ratio is not None or outlier_radius is not None
     if return_kept and not front:
-        raise ValueError("decode_points: return_kept needs pitch, outlier_ratio or outlier_radius")
+        raise ValueError("%s: return_kept needs pitch, outlier_ratio or outlier_radius" % what)
+    return types.SimpleNamespace(k=k, kThresh=kThresh, segMinVerts=segMinVerts, viewpoint=viewpoint, return_graph=return_graph,
+                                 pitch=pitch, outlier_ratio=outlier_ratio, return_kept=return_kept, n_classes=n_classes,
+                                 outlier_radius=outlier_radius, outlier_min_pts=outlier_min_pts, orient=orient,
+                                 upright_kw=upright_kw, front=front)
+
+
+def _centred_mean(xyz):
+    """The float32 mean centre_and_scale subtracts, by its own expression on its own layout."""
+    vertices = np.zeros(shape=[xyz.shape[0], 6], dtype=np.float32)
+    vertices[:, 0:3] = xyz
+    return vertices[:, :3].mean(0)
+
+
+def _sensor_views(kept, sensor, n_kept, dev):
+    """decode_frames(normals="sensor"): views f32 [F, 3], the sensor centres in the final frame, and view_of int32 [M], the
+    frame of every kept row's lowest raw member.  On the host in float64: R . c when the scan was turned upright, minus the
+    float32 mean centre_and_scale subtracted, rounded once."""
+    c = sensor.centres.astype(np.float64)
+    if kept.up is not None:
+        R = kept.up["R"].cpu().numpy()
+        c = np.stack([(R[r, 0] * c[:, 0] + R[r, 1] * c[:, 1]) + R[r, 2] * c[:, 2] for r in range(3)], axis=1)
+    with np.errstate(invalid="ignore"):
+        views = (c - _centred_mean(kept.xyz).astype(np.float64)[None, :]).astype(np.float32)
+    first = getattr(kept, "first", None)
+    frame = sensor.frame if first is None else sensor.frame[first.long()]
+    assert int(frame.shape[0]) == n_kept
+    return torch.from_numpy(np.ascontiguousarray(views)).to(dev), frame.contiguous()
+
+
+def _decode_cloud(xyz, colours, dev, labels, o, sensor=None):
+    """What decode_points does with a raw cloud -- host arrays, or the device tensors they would be uploaded to -- and its
+    checked options `o` (_decode_options); `labels` are the raw points' int32 labels on the device or None.  `sensor`
+    (decode_frames: frame int32 [N] on the device, centres f32 [F, 3] on the host; `turn` says whether the normals look at
+    them) adds `frame`, the frame of every kept row."""
     kept = types.SimpleNamespace(xyz=xyz, colours=colours, up=None)     # the decode of before: nothing goes through the front
-    if front or upright_kw is not None:
-        kept = _kept_points(xyz, colours, dev, k, pitch, outlier_ratio, outlier_radius, outlier_min_pts, upright_kw)
+    if o.front or o.upright_kw is not None:
+        kept = _kept_points(xyz, colours, dev, o.k, o.pitch, o.outlier_ratio, o.outlier_radius, o.outlier_min_pts, o.upright_kw,
+                            want_first=sensor is not None)
+    elif torch.is_tensor(xyz):
+        kept = types.SimpleNamespace(xyz=xyz.cpu().numpy(), colours=colours.cpu().numpy(), up=None)
     xyz_c, rgb = centre_and_scale(kept.xyz, kept.colours)
     xyz_d = torch.from_numpy(np.ascontiguousarray(xyz_c, np.float32)).to(dev)
-    idx, d2 = knn_graph(xyz_d, k=k)
-    nl = point_normals(xyz_d, idx, viewpoint)
-    oriented = orient_normals(nl, idx) if orient is not None else None
+    idx, d2 = knn_graph(xyz_d, k=o.k)
+    frame = None
+    if sensor is not None:
+        views, frame = _sensor_views(kept, sensor, int(xyz_d.shape[0]), dev)
+    if sensor is not None and sensor.turn:
+        nl = point_normals(xyz_d, idx, views=views, view_of=frame)
+    else:
+        nl = point_normals(xyz_d, idx, o.viewpoint)
+    oriented = orient_normals(nl, idx) if o.orient is not None else None
     if oriented is not None:
         nl = oriented["nl"]
-    sup = segment_point(xyz_d, nl, knn_edges(idx), kThresh, segMinVerts)
+    sup = segment_point(xyz_d, nl, knn_edges(idx), o.kThresh, o.segMinVerts)
     out = {"xyz": xyz_d, "rgb": torch.from_numpy(np.ascontiguousarray(rgb, np.float32)).to(dev), "nl": nl, "sup": sup}
     if oriented is not None:
         out.update(flipped=oriented["flipped"], tree=oriented["tree"])
     up = kept.up
     if up is not None:
         out.update(R=up["R"], plane=up["plane"], floor=up["floor"], height=up["height"])
-    if return_graph:
+    if o.return_graph:
         out.update(idx=idx, d2=d2)
-    if front:
+    if o.front:
         out.update(raw_index=kept.raw_index, count=kept.count)
-    if return_kept:
+    if o.return_kept:
         out.update(kept_xyz=up["kept_xyz"] if up is not None else torch.from_numpy(kept.xyz).to(dev),
                    kept_rgb=torch.from_numpy(kept.colours).to(dev))
     if labels is not None:
         m = int(xyz_d.shape[0])
-        rows = kept.raw_index if front else torch.arange(m, dtype=torch.int32, device=dev)
-        v = vote_labels(rows, labels[0], labels[1], m=m, n_classes=n_classes)
+        rows = kept.raw_index if o.front else torch.arange(m, dtype=torch.int32, device=dev)
+        v = vote_labels(rows, labels[0], labels[1], m=m, n_classes=o.n_classes)
         out.update(sem_label=v["sem_label"], ins_label=v["ins_label"], ins_old_id=v["old_id"])
-        if front:
+        if o.front:
             out.update(votes=v["votes"], members=v["members"])
+    if frame is not None:
+        out.update(frame=frame)
+    return out
+
+
+def _label_image(name, labels, shape):
+    """decode_frames' label image, checked on the host: an integer tensor [F, H, W], wherever it lives."""
+    t = labels if torch.is_tensor(labels) else torch.from_numpy(np.ascontiguousarray(labels))
+    if t.dtype.is_floating_point or t.dtype == torch.bool or t.is_complex():
+        raise TypeError("decode_frames: %s must be an integer image, got %s" % (name, t.dtype))
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("decode_frames: %s must have shape %s, got %s" % (name, list(shape), list(t.shape)))
+    return t
+
+
+def decode_frames(depth, poses, intrinsics, colour=None, device="cuda", depth_scale=1000.0, depth_min=0.0, depth_max=float("inf"),
+                  stride=1, edge=None, normals="sensor", sem_label=None, ins_label=None, k=16, kThresh=0.01, segMinVerts=20,
+                  viewpoint=None, return_graph=False, pitch=None, outlier_ratio=None, return_kept=False, n_classes=20,
+                  outlier_radius=None, outlier_min_pts=None, orient=None, upright=None):
+    """decode_points for what a depth camera hands over: frames_to_points (pbnet_amd/frames.py: `depth` [F, H, W] uint16 or
+    float32, `colour` uint8 [F, H, W, 3] or None -- arrays or tensors, brought to `device` --, host `poses` [F, 4, 4] and
+    `intrinsics`, and depth_scale, depth_min, depth_max, stride, edge), then decode_points' chain on the raw cloud with
+    decode_points' options.  Without `colour` every point is black (0, 0, 0).  With `pitch` the N raw points never visit
+    the host: the kept M points make the one round trip through centre_and_scale that decode_points documents.
+
+    `normals="sensor"` turns every normal towards the sensor position that saw its point instead of one viewpoint for the
+    whole cloud: a kept row's frame is that of its lowest raw member (thin_points' first, compacted by the outlier filter's
+    keep; the point itself without a front), and the F sensor centres (frames_to_points' centres) are brought into the
+    final frame on the host in float64 -- R . c when `upright` is set, minus the float32 mean centre_and_scale subtracted,
+    rounded once -- and handed to point_normals(views=, view_of=).  It excludes `viewpoint`.  `orient="graph"` may still
+    follow.  `normals=None` is decode_points on frames_to_points' cloud, byte for byte.
+
+    `sem_label` and `ins_label` (both or neither) are integer images [F, H, W]: the raw points' labels are gathered through
+    `pixel` and voted down as decode_points does.
+
+    The result is decode_points' plus pixel (int32 [N], of the raw points: raw_index speaks of the same rows), frame (int32
+    [M], of the kept points), centres (f32 [F, 3], in the frames' world), frame_start (int32 [F + 1], rows of the raw
+    cloud) and skipped (bool [F])."""
+    if normals is not None and normals != "sensor":
+        raise ValueError("decode_frames: normals must be None or \"sensor\", got %r" % (normals,))
+    if normals == "sensor" and viewpoint is not None:
+        raise ValueError("decode_frames: normals=\"sensor\" and viewpoint are two ways to turn the normals, give one")
+    opts = _decode_options("decode_frames", k, kThresh, segMinVerts, viewpoint, return_graph, pitch, outlier_ratio, return_kept,
+                           sem_label, ins_label, n_classes, outlier_radius, outlier_min_pts, orient, upright)
+    dev = torch.device(device)
+    depth, colour = (t if t is None or torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t)) for t in (depth, colour))
+    shape, pose, _, _ = _frames._frames_args("decode_frames", depth, poses, intrinsics, colour, depth_scale, depth_min, depth_max,
+                                             stride, edge)
+    labels = None
+    if sem_label is not None:
+        labels = [_label_image(name, v, shape) for name, v in (("sem_label", sem_label), ("ins_label", ins_label))]
+    cloud = _frames.frames_to_points(depth.to(dev), pose.reshape(-1, 4, 4), intrinsics, None if colour is None else colour.to(dev),
+                                     depth_scale, depth_min, depth_max, stride, edge)
+    pixel = cloud["pixel"]
+    if labels is not None:
+        labels = [t.to(dev).reshape(-1)[pixel.long()].to(torch.int32) for t in labels]
+    n = int(pixel.shape[0])
+    rgb = cloud["rgb"] if colour is not None else torch.zeros(n, 3, dtype=torch.float32, device=dev)
+    sensor = types.SimpleNamespace(frame=torch.div(pixel, max(shape[1] * shape[2], 1), rounding_mode="floor").to(torch.int32),
+                                   centres=_frames.host_centres(pose)[0], turn=normals == "sensor")
+    out = _decode_cloud(cloud["xyz"], rgb, dev, labels, opts, sensor)
+    out.update(pixel=pixel, centres=cloud["centres"], frame_start=cloud["frame_start"], skipped=cloud["skipped"])
     return out
 
 
 SCENE_BOOKKEEPING = ("votes", "members", "ins_old_id", "raw_index", "count", "flipped", "tree",
-                     "R", "plane", "floor", "height")        # of a decode, not of a scene on disk
+                     "R", "plane", "floor", "height", "pixel", "frame", "centres", "frame_start", "skipped")   # of a decode, not of a scene on disk
 
 
 def save_decoded(npy_dir, scene, decoded, sem_label=None, ins_label=None):
