@@ -1120,6 +1120,95 @@ int pbn_frames_write_timed(const void* depth, int depth_is_f32, const uint8_t* c
                            void* workspace, size_t workspace_bytes, pbn_stream_t stream, float* times_ms);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Depth-frame fusion (csrc/tsdf.hip): the frames of "Posed depth frames" fused into a truncated signed distance volume over
+ * blocks of 8 x 8 x 8 voxels, and the volume's zero crossings as points with colours and normals.
+ * tests/fuse_ref.py restates this contract in numpy.  Every expression is one rounded float64 operation per operator, in
+ * the order the brackets give; nothing is fused; a result is rounded to float32 once, on the store.
+ *   Inputs   depth, depth_is_f32, colour, pose, intr, F, H, W, depth_scale, depth_min, depth_max, edge as in "Posed depth
+ *            frames" (no stride), with its Limits.  voxel finite and > 0; trunc finite with 0 < trunc <= 8 * voxel;
+ *            min_weight >= 1; else PBN_ERR_ARG.  A skipped frame (a non-finite number in its pose's top three rows)
+ *            contributes nothing anywhere.
+ *   Blocks   pbn_fuse_blocks takes the raw cloud xyz f32[n,3] (pbn_frames_write's, stride 1, same filters).  B = 8 * voxel;
+ *            origin g[a] = double(min32[a]) - B with min32 the float32 minimum of axis a; a point's block is
+ *            b[a] = max(floor((double(p[a]) - g[a]) / B), 1): the quotient is 1 or more up to its rounding, and a point on the minimum
+ *            that comes out a last bit below 1 lies in block 1 all the same.  A block is allocated when it or one of its 26
+ *            neighbours holds a point.  key = bz << 42 | by << 21 | bx; blocks are ranked in ascending key.
+ *            result int32[8] (device): [0] status -- bit 1 a coordinate is not finite, bit 2 an axis spans 2^21 - 1 blocks or
+ *            more, neighbours included (block coordinates are 0 .. 2^21 - 2: a neighbour's key is the key +- 1, 2^21 or 2^42,
+ *            and coordinate 2^21 - 1 is where the borrow of coordinate 0's lower neighbour lands, so it is never a block), bit 8 a sort gave up, bit 4 more than pbn_fuse_max_blocks() = 2^21 blocks (the
+ *            voxel is too small for the scene); with a status no key is written --, [1] M_b, [2..4] the bits of min32: one
+ *            read-back gives all.  n = 0 gives M_b = 0.  pbn_fuse_block_keys -- same n_points, same workspace, untouched in
+ *            between -- writes block_key int64[M_b]; n_blocks other than result[1] sets bit 32 and writes nothing.
+ *   Volume   pbn_fuse_integrate.  World to camera per frame, on the host: Rt = R transposed,
+ *            tc[r] = -((Rt[r,0]*t0 + Rt[r,1]*t1) + Rt[r,2]*t2) (a rigid inverse; a pose that is not rigid is the caller's
+ *            error and is not detected).  The voxel (ix, iy, iz) of block (bx, by, bz) has the centre
+ *            p[a] = g[a] + (double(8 * b[a] + i[a]) + 0.5) * voxel, origin = g as double[3] on the HOST.  For every frame
+ *            that is not skipped, in ascending frame order:
+ *              1. pc[r] = ((Rt[r,0]*p0 + Rt[r,1]*p1) + Rt[r,2]*p2) + tc[r]; zc = pc[2]; skip unless zc > 0;
+ *              2. uf = (fx * pc[0]) / zc + cx, vf = (fy * pc[1]) / zc + cy, ur = rint(uf), vr = rint(vf) (ties to even); skip
+ *                 unless 0 <= ur <= W - 1 and 0 <= vr <= H - 1, compared in float64 (false for NaN);
+ *              3. z = the depth at (vr, ur), valid by rules (b) and (c) of "Posed depth frames" (rule (d) is not asked: no
+ *                 world point is formed);
+ *              4. s = z - zc; skip when s < -trunc;
+ *              5. d = min(1.0, s / trunc);
+ *              6. S += d, Wt += 1, and with colour C[c] += double(byte c).
+ *            tsdf = float32(S / double(Wt)), weight = Wt, rgb[c] = float32(C[c] / double(Wt)); a voxel with Wt = 0 stores
+ *            0 everywhere.  tsdf f32[M_b,512], weight int32[M_b,512], rgb f32[M_b,512,3] (NULL exactly when colour is),
+ *            in-block index (iz * 8 + iy) * 8 + ix.  One workgroup per block keeps every voxel's sums in registers through
+ *            all frames; frames whose frustum cannot meet the block's bounding sphere are passed over, which never changes
+ *            a result.  The call waits once for its upload of the cameras; the volume is never read.
+ *   Surface  a voxel is observed when weight >= min_weight.  For every observed voxel q in ascending (block rank, in-block
+ *            index) and a = 0, 1, 2: n = q + e_a (in another block through the sorted keys; a block that is not allocated
+ *            is unobserved) must be observed and (D(q) < 0) != (D(n) < 0) on the stored float32 values as float64.  Then
+ *            r = D(q) / (D(q) - D(n)); the point is p(q) with coordinate a replaced by p(q)[a] + r * voxel;
+ *            rgb = rgb(q) + r * (rgb(n) - rgb(q)); G(x)[b] = D'(x + e_b) - D'(x - e_b) where an unobserved voxel reads as
+ *            D(x) itself; gv[b] = G(q)[b] + r * (G(n)[b] - G(q)[b]); len = sqrt((gv0*gv0 + gv1*gv1) + gv2*gv2); nl = gv / len,
+ *            the zero vector when len is 0 or not finite: it points from the surface into free space, towards the sensors.
+ *            Rows in that order: xyz, rgb, nl f32[N,3], weight int32[N] = min(weight(q), weight(n)), voxel_id int64[N] =
+ *            (block rank * 512 + in-block index) * 3 + a.  pbn_fuse_extract_count writes result int32[2] = (status, N);
+ *            the caller reads it and pbn_fuse_extract_write -- same volume, same workspace, untouched in between -- writes
+ *            the rows; a row at or beyond n_rows is not written and sets bit 32; the rows below n_rows are written all the same.  n_blocks <= 1398101 (N fits an int32).
+ * No atomic touches an order or a float: two runs give the same bytes.  Only the _timed entries (and pbn_fuse_integrate's
+ * one wait) synchronise.
+ * ------------------------------------------------------------------------------------------------------------ */
+int pbn_fuse_max_blocks(void);                                  /* 2^21 */
+/* bytes of workspace for pbn_fuse_blocks / pbn_fuse_block_keys; 0 = n_points out of range (< 0 or above 2^28) */
+size_t pbn_fuse_blocks_workspace_bytes(int n_points);
+int pbn_fuse_blocks(const float* xyz, int n_points, double voxel, int32_t* result, void* workspace, size_t workspace_bytes,
+                    pbn_stream_t stream);
+/* Measurement variant: SYNCHRONISES; times_ms (host float[3]): box + keys, the points' blocks, dilation + the allocated blocks. */
+int pbn_fuse_blocks_timed(const float* xyz, int n_points, double voxel, int32_t* result, void* workspace, size_t workspace_bytes,
+                          pbn_stream_t stream, float* times_ms);
+int pbn_fuse_block_keys(int n_points, int n_blocks, int64_t* block_key, int32_t* result, void* workspace, size_t workspace_bytes,
+                        pbn_stream_t stream);
+size_t pbn_fuse_integrate_workspace_bytes(int n_frames);        /* 0 = n_frames < 0 */
+int pbn_fuse_integrate(const void* depth, int depth_is_f32, const uint8_t* colour, const double* pose, const double* intr,
+                       int n_frames, int height, int width, double depth_scale, double depth_min, double depth_max, double edge,
+                       double voxel, double trunc, const double* origin, const int64_t* block_key, int n_blocks, float* tsdf,
+                       int32_t* weight, float* rgb, void* workspace, size_t workspace_bytes, pbn_stream_t stream);
+/* Measurement variant: SYNCHRONISES; times_ms (host float[1]): the integration; stats (host uint64[2], or NULL): [0] the
+ * block-frame pairs left by the cull (each stands for 512 voxel-frame pairs), [1] the depth samples gathered in step 3. */
+int pbn_fuse_integrate_timed(const void* depth, int depth_is_f32, const uint8_t* colour, const double* pose, const double* intr,
+                             int n_frames, int height, int width, double depth_scale, double depth_min, double depth_max,
+                             double edge, double voxel, double trunc, const double* origin, const int64_t* block_key, int n_blocks,
+                             float* tsdf, int32_t* weight, float* rgb, void* workspace, size_t workspace_bytes, pbn_stream_t stream,
+                             float* times_ms, uint64_t* stats);
+size_t pbn_fuse_extract_workspace_bytes(int n_blocks);          /* 0 = n_blocks out of range */
+int pbn_fuse_extract_count(const float* tsdf, const int32_t* weight, const int64_t* block_key, int n_blocks, int min_weight,
+                           int32_t* result, void* workspace, size_t workspace_bytes, pbn_stream_t stream);
+int pbn_fuse_extract_write(const float* tsdf, const int32_t* weight, const float* vol_rgb, const int64_t* block_key, int n_blocks,
+                           int min_weight, double voxel, const double* origin, int n_rows, float* xyz, float* rgb, float* nl,
+                           int32_t* out_weight, int64_t* voxel_id, int32_t* result, void* workspace, size_t workspace_bytes,
+                           pbn_stream_t stream);
+/* Measurement variants: SYNCHRONISE; times_ms (host float[1]): count + scan; the write. */
+int pbn_fuse_extract_count_timed(const float* tsdf, const int32_t* weight, const int64_t* block_key, int n_blocks, int min_weight,
+                                 int32_t* result, void* workspace, size_t workspace_bytes, pbn_stream_t stream, float* times_ms);
+int pbn_fuse_extract_write_timed(const float* tsdf, const int32_t* weight, const float* vol_rgb, const int64_t* block_key,
+                                 int n_blocks, int min_weight, double voxel, const double* origin, int n_rows, float* xyz, float* rgb,
+                                 float* nl, int32_t* out_weight, int64_t* voxel_id, int32_t* result, void* workspace,
+                                 size_t workspace_bytes, pbn_stream_t stream, float* times_ms);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Raw sensor scans (csrc/thin.hip): grid thinning to the network's pitch, statistical outlier removal over the kNN graph's
  * d2, and the way back from the kept points to the raw ones.  Argument checks run on the host before any launch; only the
  * _timed entry synchronises.  Every output is a pure function of the input (no float atomics): two runs give the same

@@ -127,6 +127,15 @@ class PostBatchLayout(ctypes.Structure):
                                      "votes", "sp_label", "seg", "seg_refined", "counts2", "renumber", "total_bytes")]
 
 
+# pbn_fuse_integrate: depth, depth_is_f32, colour, pose, intr (host), F, H, W, depth_scale, depth_min, depth_max, edge, voxel,
+# trunc, origin (host double[3]), block_key, n_blocks, tsdf, weight, rgb
+_FUSE_HEAD = [c_vp, c_int, c_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), c_int, c_int, c_int,
+              ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+              ctypes.POINTER(ctypes.c_double), c_vp, c_int, c_f32p, c_i32p, c_f32p]
+# pbn_fuse_extract_write: tsdf, weight, vol_rgb, block_key, n_blocks, min_weight, voxel, origin (host), n_rows, xyz, rgb, nl,
+# out_weight, voxel_id, result
+_FUSE_ROWS = [c_f32p, c_i32p, c_f32p, c_vp, c_int, c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_double), c_int, c_f32p, c_f32p,
+              c_f32p, c_i32p, c_vp, c_i32p]
 # what pbn_frames_count and pbn_frames_write share: depth, depth_is_f32, colour, pose and intr (host double arrays), F, H, W,
 # depth_scale, depth_min, depth_max, stride, edge
 _FRAMES_HEAD = [c_vp, c_int, c_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), c_int, c_int, c_int,
@@ -301,6 +310,21 @@ SIGNATURES = {
     "pbn_frames_write": (c_int, _FRAMES_HEAD + [c_int, c_f32p, c_f32p, c_i32p, c_i32p, c_vp, c_size, c_vp]),
     "pbn_frames_write_timed": (c_int, _FRAMES_HEAD + [c_int, c_f32p, c_f32p, c_i32p, c_i32p, c_vp, c_size, c_vp,
                                                       ctypes.POINTER(ctypes.c_float)]),
+    "pbn_fuse_max_blocks": (c_int, []),
+    "pbn_fuse_blocks_workspace_bytes": (c_size, [c_int]),
+    "pbn_fuse_blocks": (c_int, [c_f32p, c_int, ctypes.c_double, c_i32p, c_vp, c_size, c_vp]),
+    "pbn_fuse_blocks_timed": (c_int, [c_f32p, c_int, ctypes.c_double, c_i32p, c_vp, c_size, c_vp, ctypes.POINTER(ctypes.c_float)]),
+    "pbn_fuse_block_keys": (c_int, [c_int, c_int, c_vp, c_i32p, c_vp, c_size, c_vp]),
+    "pbn_fuse_integrate_workspace_bytes": (c_size, [c_int]),
+    "pbn_fuse_integrate": (c_int, _FUSE_HEAD + [c_vp, c_size, c_vp]),
+    "pbn_fuse_integrate_timed": (c_int, _FUSE_HEAD + [c_vp, c_size, c_vp, ctypes.POINTER(ctypes.c_float),
+                                                      ctypes.POINTER(ctypes.c_uint64)]),
+    "pbn_fuse_extract_workspace_bytes": (c_size, [c_int]),
+    "pbn_fuse_extract_count": (c_int, [c_f32p, c_i32p, c_vp, c_int, c_int, c_i32p, c_vp, c_size, c_vp]),
+    "pbn_fuse_extract_count_timed": (c_int, [c_f32p, c_i32p, c_vp, c_int, c_int, c_i32p, c_vp, c_size, c_vp,
+                                             ctypes.POINTER(ctypes.c_float)]),
+    "pbn_fuse_extract_write": (c_int, _FUSE_ROWS + [c_vp, c_size, c_vp]),
+    "pbn_fuse_extract_write_timed": (c_int, _FUSE_ROWS + [c_vp, c_size, c_vp, ctypes.POINTER(ctypes.c_float)]),
     "pbn_thin_workspace_bytes": (c_size, [c_int]),
     "pbn_thin_points": (c_int, [c_f32p, c_f32p, c_int, ctypes.c_double, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, c_i32p, c_vp, c_size,
                                 c_vp]),

@@ -24,6 +24,7 @@
 // Arithmetic contract (-ffp-contract=off): float64, one rounded operation per written operation; float32 on the store.
 #include <cmath>
 
+#include "frames_dev.h"
 #include "scan_dev.h"
 
 namespace pbn {
@@ -49,14 +50,6 @@ struct FramesShape {
     double scale, z_min, z_max, edge;
 };
 
-__device__ __forceinline__ double frames_z(unsigned short d, double scale) { return (double)d / scale; }
-__device__ __forceinline__ double frames_z(float d, double) { return (double)d; }
-
-// rule (b); a uint16 0 gives z = 0 and fails z > 0
-__device__ __forceinline__ bool frames_measured(double z, double z_min, double z_max) {
-    return __builtin_isfinite(z) && z > 0.0 && z >= z_min && z <= z_max;
-}
-
 // One sampled pixel s of frame f (pose_ok = rule (a)): rules (b), (c), (d); the pixel id and the float32 world point.
 template <typename D>
 __device__ __forceinline__ bool frames_point(const D* __restrict__ depth, const FramesShape& a, const double* __restrict__ P,
@@ -64,45 +57,16 @@ __device__ __forceinline__ bool frames_point(const D* __restrict__ depth, const 
                                              float& Y, float& Z) {
     if (!pose_ok || s >= a.per_frame) return false;
     const int v = (s / a.ws) * a.stride, u = (s % a.ws) * a.stride;
-    const size_t row = (size_t)f * a.height + v;
     const D* __restrict__ img = depth + (size_t)f * a.height * a.width;
-    id = (int)(row * a.width + u);                           // F * H * W <= 2^31 - 1
-    const double z = frames_z(depth[row * a.width + u], a.scale);
-    if (!frames_measured(z, a.z_min, a.z_max)) return false;
-    if (a.edge > 0.0) {
-        const double lim = a.edge * z;
-        bool is_edge = false;
-        if (u > 0) {
-            const double zn = frames_z(img[(size_t)v * a.width + (u - 1)], a.scale);
-            is_edge |= frames_measured(zn, a.z_min, a.z_max) && fabs(zn - z) > lim;
-        }
-        if (u + 1 < a.width) {
-            const double zn = frames_z(img[(size_t)v * a.width + (u + 1)], a.scale);
-            is_edge |= frames_measured(zn, a.z_min, a.z_max) && fabs(zn - z) > lim;
-        }
-        if (v > 0) {
-            const double zn = frames_z(img[(size_t)(v - 1) * a.width + u], a.scale);
-            is_edge |= frames_measured(zn, a.z_min, a.z_max) && fabs(zn - z) > lim;
-        }
-        if (v + 1 < a.height) {
-            const double zn = frames_z(img[(size_t)(v + 1) * a.width + u], a.scale);
-            is_edge |= frames_measured(zn, a.z_min, a.z_max) && fabs(zn - z) > lim;
-        }
-        if (is_edge) return false;
-    }
+    id = (int)(((size_t)f * a.height + v) * a.width + u);    // F * H * W <= 2^31 - 1
+    double z;
+    if (!frames_depth_ok(img, a.height, a.width, u, v, a.scale, a.z_min, a.z_max, a.edge, z)) return false;   // rules (b), (c)
     const double xc = (((double)u - K[2]) * z) / K[0];
     const double yc = (((double)v - K[3]) * z) / K[1];
     X = (float)(((P[0] * xc + P[1] * yc) + P[2] * z) + P[3]);
     Y = (float)(((P[4] * xc + P[5] * yc) + P[6] * z) + P[7]);
     Z = (float)(((P[8] * xc + P[9] * yc) + P[10] * z) + P[11]);
     return __builtin_isfinite(X) && __builtin_isfinite(Y) && __builtin_isfinite(Z);
-}
-
-__device__ __forceinline__ bool frames_pose_ok(const double* __restrict__ P) {
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) ok = ok && __builtin_isfinite(P[i]);
-    return ok;
 }
 
 // WRITE = false: counts[workgroup] = its valid pixels.  WRITE = true: the rows, at offs[workgroup] + ...

@@ -16,6 +16,8 @@ from . import _native as N
 from .cloud import _device, _got, _int_in, _real, _scan_status, _scan_workspace
 
 FRAMES_STAGES = ("count", "scan + starts", "write")
+FUSE_STAGES = ("box + keys", "point blocks", "dilation + blocks", "integrate", "extract count", "extract write")
+FUSE_TOO_MANY, FUSE_ROWS, FUSE_MAX_BLOCKS, FUSE_MAX_EXTRACT_BLOCKS = 4, 32, 1 << 21, 1398101     # csrc/tsdf.hip
 FRAMES_MAX_PIXELS, FRAMES_MAX_SAMPLED = (1 << 31) - 1, 1 << 28      # F * H * W; csrc/scan_dev.h's SCAN_MAX_POINTS
 _DOUBLE_P = ctypes.POINTER(ctypes.c_double)
 
@@ -126,4 +128,125 @@ def frames_to_points(depth, poses, intrinsics, colour=None, depth_scale=1000.0, 
            "skipped": torch.from_numpy(skipped).to(dev), "shape": (f, h, w)}
     if rgb is not None:
         out["rgb"] = rgb
+    return out
+
+
+def _fuse_args(what, voxel, trunc, min_weight):
+    """fuse_frames' own scalars, checked on the host: (voxel, trunc, min_weight) as the library takes them."""
+    voxel = float(_real(what, "voxel", voxel))
+    if not (voxel > 0.0 and math.isfinite(voxel) and math.isfinite(8.0 * voxel)):
+        raise ValueError("%s: voxel must be positive and finite, got %r" % (what, voxel))
+    trunc = 4.0 * voxel if trunc is None else float(_real(what, "trunc", trunc, "a number or None"))
+    if not (math.isfinite(trunc) and 0.0 < trunc <= 8.0 * voxel):
+        raise ValueError("%s: trunc must be finite with 0 < trunc <= 8 * voxel = %r, got %r" % (what, 8.0 * voxel, trunc))
+    min_weight = _int_in(what, "min_weight", min_weight, 1, (1 << 31) - 1, "1..2^31 - 1")
+    return voxel, trunc, min_weight
+
+
+def _fuse_status(what, status, voxel):
+    """A fusion stage's status word: the chain's bits, then the stage's own."""
+    if status & FUSE_TOO_MANY:
+        raise ValueError("%s: more than 2^21 blocks of 8 voxels of %r: the voxel is too small for the scene" % (what, voxel))
+    if status & 2:
+        raise ValueError("%s: the cloud spans 2^21 blocks or more of 8 voxels of %r on an axis" % (what, voxel))
+    if status & 1:
+        raise ValueError("%s: a coordinate is NaN or infinite" % what)
+    if status & FUSE_ROWS:
+        raise RuntimeError("%s: a pass met more rows than its count pass: the inputs changed between the two (status %d)"
+                           % (what, status))
+    if status:
+        raise RuntimeError("%s: the device sort gave up (status %d)" % (what, status))
+
+
+def fuse_frames(depth, poses, intrinsics, colour=None, voxel=0.02, trunc=None, depth_scale=1000.0, depth_min=0.0,
+                depth_max=math.inf, edge=None, min_weight=1, return_volume=False, times=None):
+    """An RGB-D sequence fused into a truncated signed distance volume and its surface points (csrc/tsdf.hip; the contract
+    is include/pbnet_hip.h's "Depth-frame fusion", tests/fuse_ref.py restates it).  The arguments are frames_to_points'
+    without `stride`, plus `voxel` (metres), `trunc` (the truncation distance, None = 4 * voxel, at most 8 * voxel) and
+    `min_weight` (a voxel counts as observed when that many frames saw it).
+
+    Blocks of 8^3 voxels are allocated around the raw cloud (frames_to_points at stride 1, never read back); every voxel
+    of every block then meets every frame in ascending order -- projective distance, truncated, averaged with weight 1 --
+    with its sums in one lane's registers; the zero crossings between observed neighbours along x, y and z come back as
+    points with interpolated colour and the normalised gradient of the distance field, which points towards the sensors.
+
+    Returns a dict on the device: xyz, nl f32 [N, 3], rgb f32 [N, 3] (with `colour`), weight int32 [N] (the lesser
+    of the crossing's two voxels), voxel_id int64 [N] = (block rank * 512 + in-block index) * 3 + axis, ascending; origin
+    (f64 [3], host: the corner of block (0, 0, 0)), n_blocks, centres, skipped and shape as frames_to_points gives them; with
+    return_volume also block_key int64 [M_b], tsdf f32 [M_b, 512], vol_weight int32 [M_b, 512] and vol_rgb f32
+    [M_b, 512, 3].  More than 1 398 101 blocks raise ValueError (the allocation takes 2^21, the extraction's int32 row
+    count does not).  Three read-backs, each a status and a count: the raw points, the blocks, the surface rows.  `times` (a
+    dict) takes the stage times of the measurement entries, which synchronise, and "stats": the block-frame pairs the cull
+    left and the depth samples gathered."""
+    what = "fuse_frames"
+    (f, h, w), pose, intr, (scale, z_min, z_max, _, edge) = _frames_args(what, depth, poses, intrinsics, colour, depth_scale,
+                                                                         depth_min, depth_max, 1, edge)
+    voxel, trunc, min_weight = _fuse_args(what, voxel, trunc, min_weight)
+    depth, colour = _device(depth, colour)
+    dev, lib = depth.device, N.lib()
+    cloud = frames_to_points(depth, pose.reshape(f, 4, 4), intr, None, scale, z_min, z_max, 1, edge, times=times)
+    xyz, n = cloud["xyz"], int(cloud["xyz"].shape[0])
+    stream = N.current_stream()
+    t = None if times is None else [(ctypes.c_float * k)() for k in (3, 1, 1, 1)]
+    stats = (ctypes.c_uint64 * 2)()
+
+    def call(entry, args, slot):
+        if t is None:
+            N.check(getattr(lib, entry)(*args), entry)
+        else:
+            extra = (t[slot], stats) if entry == "pbn_fuse_integrate" else (t[slot],)
+            N.check(getattr(lib, entry + "_timed")(*args, *extra), entry + "_timed")
+
+    ws = _scan_workspace(lib.pbn_fuse_blocks_workspace_bytes(n), dev, "%d raw points" % n)
+    result = torch.empty(8, dtype=torch.int32, device=dev)
+    call("pbn_fuse_blocks", (N.ptr(xyz), n, voxel, N.ptr(result), N.ptr(ws), ws.numel(), stream), 0)
+    head = result.tolist()                                   # the second read-back: status, M_b and the minimum's bits
+    _fuse_status(what, head[0], voxel)
+    m_b = head[1]
+    origin = np.array(head[2:5], np.int32).view(np.float32).astype(np.float64) - 8.0 * voxel if n else np.zeros(3)
+    origin = np.ascontiguousarray(origin, np.float64)
+    block_key = torch.empty(m_b, dtype=torch.int64, device=dev)
+    if m_b:
+        N.check(lib.pbn_fuse_block_keys(n, m_b, N.ptr(block_key), N.ptr(result), N.ptr(ws), ws.numel(), stream), "pbn_fuse_block_keys")
+    del ws, xyz, cloud["xyz"]
+    if m_b > FUSE_MAX_EXTRACT_BLOCKS:
+        raise ValueError("%s: %d blocks exceed the %d whose surface rows fit an int32: the voxel is too small for the scene"
+                         % (what, m_b, FUSE_MAX_EXTRACT_BLOCKS))
+    tsdf = torch.empty(m_b, 512, dtype=torch.float32, device=dev)
+    vol_weight = torch.empty(m_b, 512, dtype=torch.int32, device=dev)
+    vol_rgb = torch.empty(m_b, 512, 3, dtype=torch.float32, device=dev) if colour is not None else None
+    n_rows = 0
+    if m_b:                                                  # an empty cloud: every later stage returns empty without a launch
+        ws = torch.empty(lib.pbn_fuse_integrate_workspace_bytes(f), dtype=torch.uint8, device=dev)
+        call("pbn_fuse_integrate", (N.ptr(depth), int(depth.dtype == torch.float32), N.ptr(colour), pose.ctypes.data_as(_DOUBLE_P),
+                                    intr.ctypes.data_as(_DOUBLE_P), f, h, w, scale, z_min, z_max, edge, voxel, trunc,
+                                    origin.ctypes.data_as(_DOUBLE_P), N.ptr(block_key), m_b, N.ptr(tsdf), N.ptr(vol_weight),
+                                    N.ptr(vol_rgb), N.ptr(ws), ws.numel(), stream), 1)
+        ws = torch.empty(lib.pbn_fuse_extract_workspace_bytes(m_b), dtype=torch.uint8, device=dev)
+        res2 = torch.empty(2, dtype=torch.int32, device=dev)
+        call("pbn_fuse_extract_count", (N.ptr(tsdf), N.ptr(vol_weight), N.ptr(block_key), m_b, min_weight, N.ptr(res2), N.ptr(ws),
+                                        ws.numel(), stream), 2)
+        st, n_rows = res2.tolist()                           # the third read-back
+        _fuse_status(what, st, voxel)
+    out_xyz = torch.empty(n_rows, 3, dtype=torch.float32, device=dev)
+    out_nl = torch.empty(n_rows, 3, dtype=torch.float32, device=dev)
+    out_rgb = torch.empty(n_rows, 3, dtype=torch.float32, device=dev) if colour is not None else None
+    out_weight = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    voxel_id = torch.empty(n_rows, dtype=torch.int64, device=dev)
+    if m_b:
+        call("pbn_fuse_extract_write", (N.ptr(tsdf), N.ptr(vol_weight), N.ptr(vol_rgb), N.ptr(block_key), m_b, min_weight, voxel,
+                                        origin.ctypes.data_as(_DOUBLE_P), n_rows, N.ptr(out_xyz), N.ptr(out_rgb), N.ptr(out_nl),
+                                        N.ptr(out_weight), N.ptr(voxel_id), N.ptr(res2), N.ptr(ws), ws.numel(), stream), 3)
+        if t is not None:
+            _fuse_status(what, int(res2[0].item()), voxel)   # the measurement entry has synchronised already
+    if t is not None:
+        flat = [float(v) for a in t for v in a] if m_b else [float(v) for v in t[0]] + [0.0, 0.0, 0.0]
+        times.update(zip(FUSE_STAGES, flat))
+        times["stats"] = {"block_frame_pairs": int(stats[0]), "depth_samples": int(stats[1])}
+    out = {"xyz": out_xyz, "nl": out_nl, "weight": out_weight, "voxel_id": voxel_id, "origin": origin, "n_blocks": m_b,
+           "centres": cloud["centres"], "skipped": cloud["skipped"], "shape": (f, h, w)}
+    if out_rgb is not None:
+        out["rgb"] = out_rgb
+    if return_volume:
+        out.update(block_key=block_key, tsdf=tsdf, vol_weight=vol_weight, vol_rgb=vol_rgb)
     return out

@@ -350,15 +350,25 @@ def _sensor_views(kept, sensor, n_kept, dev):
     return torch.from_numpy(np.ascontiguousarray(views)).to(dev), frame.contiguous()
 
 
-def _decode_cloud(xyz, colours, dev, labels, o, sensor=None):
+def _fused_normals(nl, up):
+    """decode_frames(fuse=, normals="tsdf"): the fused surface's normals in the final frame -- as they are, or with `upright`
+    R . n in float64, (R[r,0]*n0 + R[r,1]*n1) + R[r,2]*n2, rounded once."""
+    if up is None:
+        return nl.contiguous()
+    R, n = up["R"].to(nl.device, torch.float64), nl.double()
+    return torch.stack([(R[r, 0] * n[:, 0] + R[r, 1] * n[:, 1]) + R[r, 2] * n[:, 2] for r in range(3)], dim=1).float().contiguous()
+
+
+def _decode_cloud(xyz, colours, dev, labels, o, sensor=None, fused=None):
     """What decode_points does with a raw cloud -- host arrays, or the device tensors they would be uploaded to -- and its
     checked options `o` (_decode_options); `labels` are the raw points' int32 labels on the device or None.  `sensor`
     (decode_frames: frame int32 [N] on the device, centres f32 [F, 3] on the host; `turn` says whether the normals look at
-    them) adds `frame`, the frame of every kept row."""
+    them) adds `frame`, the frame of every kept row.  `fused` (decode_frames with fuse: nl f32 [N, 3] and weight int32 [N] of
+    the fused surface on the device; `turn` says whether nl replaces point_normals' output) adds `fuse_weight`."""
     kept = types.SimpleNamespace(xyz=xyz, colours=colours, up=None)     # the decode of before: nothing goes through the front
     if o.front or o.upright_kw is not None:
         kept = _kept_points(xyz, colours, dev, o.k, o.pitch, o.outlier_ratio, o.outlier_radius, o.outlier_min_pts, o.upright_kw,
-                            want_first=sensor is not None)
+                            want_first=sensor is not None or fused is not None)
     elif torch.is_tensor(xyz):
         kept = types.SimpleNamespace(xyz=xyz.cpu().numpy(), colours=colours.cpu().numpy(), up=None)
     xyz_c, rgb = centre_and_scale(kept.xyz, kept.colours)
@@ -367,7 +377,15 @@ def _decode_cloud(xyz, colours, dev, labels, o, sensor=None):
     frame = None
     if sensor is not None:
         views, frame = _sensor_views(kept, sensor, int(xyz_d.shape[0]), dev)
-    if sensor is not None and sensor.turn:
+    fuse_weight = None
+    if fused is not None:                                     # a kept row speaks with its lowest raw member, as `frame` does
+        first = getattr(kept, "first", None)
+        rows = slice(None) if first is None else first.long()
+        fuse_weight = fused.weight[rows].contiguous()
+        assert int(fuse_weight.shape[0]) == int(xyz_d.shape[0])
+    if fused is not None and fused.turn:
+        nl = _fused_normals(fused.nl[rows], kept.up)
+    elif sensor is not None and sensor.turn:
         nl = point_normals(xyz_d, idx, views=views, view_of=frame)
     else:
         nl = point_normals(xyz_d, idx, o.viewpoint)
@@ -397,7 +415,30 @@ def _decode_cloud(xyz, colours, dev, labels, o, sensor=None):
             out.update(votes=v["votes"], members=v["members"])
     if frame is not None:
         out.update(frame=frame)
+    if fuse_weight is not None:
+        out.update(fuse_weight=fuse_weight)
     return out
+
+
+_NORMALS_DEFAULT = "default"                                 # decode_frames: "sensor", or "tsdf" with fuse
+FUSE_KEYS = ("voxel", "trunc", "min_weight")
+
+
+def _fuse_option(fuse):
+    """decode_frames' `fuse` as fuse_frames' keyword arguments, or None; checked before anything is uploaded."""
+    if fuse is None or fuse is False:
+        return None
+    if fuse is True:
+        fuse = {}
+    if not isinstance(fuse, dict):
+        raise TypeError("decode_frames: fuse must be None, True or a dict of voxel, trunc and min_weight, got %r" % (fuse,))
+    unknown = sorted(set(fuse) - set(FUSE_KEYS))
+    if unknown:
+        raise TypeError("decode_frames: fuse has no argument %s (it takes %s)" % (", ".join(map(repr, unknown)), ", ".join(FUSE_KEYS)))
+    kw = dict(voxel=0.02, trunc=None, min_weight=1)
+    kw.update(fuse)
+    _frames._fuse_args("decode_frames: fuse", kw["voxel"], kw["trunc"], kw["min_weight"])
+    return kw
 
 
 def _label_image(name, labels, shape):
@@ -411,9 +452,9 @@ def _label_image(name, labels, shape):
 
 
 def decode_frames(depth, poses, intrinsics, colour=None, device="cuda", depth_scale=1000.0, depth_min=0.0, depth_max=float("inf"),
-                  stride=1, edge=None, normals="sensor", sem_label=None, ins_label=None, k=16, kThresh=0.01, segMinVerts=20,
+                  stride=1, edge=None, normals=_NORMALS_DEFAULT, sem_label=None, ins_label=None, k=16, kThresh=0.01, segMinVerts=20,
                   viewpoint=None, return_graph=False, pitch=None, outlier_ratio=None, return_kept=False, n_classes=20,
-                  outlier_radius=None, outlier_min_pts=None, orient=None, upright=None):
+                  outlier_radius=None, outlier_min_pts=None, orient=None, upright=None, fuse=None):
     """decode_points for what a depth camera hands over: frames_to_points (pbnet_amd/frames.py: `depth` [F, H, W] uint16 or
     float32, `colour` uint8 [F, H, W, 3] or None -- arrays or tensors, brought to `device` --, host `poses` [F, 4, 4] and
     `intrinsics`, and depth_scale, depth_min, depth_max, stride, edge), then decode_points' chain on the raw cloud with
@@ -432,7 +473,25 @@ def decode_frames(depth, poses, intrinsics, colour=None, device="cuda", depth_sc
 
     The result is decode_points' plus pixel (int32 [N], of the raw points: raw_index speaks of the same rows), frame (int32
     [M], of the kept points), centres (f32 [F, 3], in the frames' world), frame_start (int32 [F + 1], rows of the raw
-    cloud) and skipped (bool [F])."""
+    cloud) and skipped (bool [F]).
+
+    `fuse` (True, or a dict of voxel, trunc and min_weight) puts volumetric fusion between the frames and the chain:
+    fuse_frames' surface points (xyz, rgb; black without `colour`) are the raw cloud, and pitch, the outlier filters,
+    upright and orient work on it as before.  `normals` is then "tsdf" (the default with fuse: a kept row takes the fused
+    normal of its lowest raw member -- thin_points' first, compacted by the filter's keep --, turned by R when `upright` is
+    set, in float64, rounded once; it replaces point_normals' output) or None (PCA normals, the chain as it is); "sensor"
+    raises ValueError, because a fused point has no single frame.  Label images and a stride other than 1 raise ValueError
+    with fuse: label fusion per voxel is not built.  The result gains fuse_weight (int32 [M], of the kept rows' lowest
+    members) and n_blocks, and has no pixel, frame or frame_start.  fuse=None is the decode of before, byte for byte."""
+    fuse_kw = _fuse_option(fuse)
+    if fuse_kw is not None:
+        return _decode_fused(depth, poses, intrinsics, colour, device, depth_scale, depth_min, depth_max, stride, edge, normals,
+                             sem_label, ins_label, fuse_kw,
+                             dict(k=k, kThresh=kThresh, segMinVerts=segMinVerts, viewpoint=viewpoint, return_graph=return_graph,
+                                  pitch=pitch, outlier_ratio=outlier_ratio, return_kept=return_kept, n_classes=n_classes,
+                                  outlier_radius=outlier_radius, outlier_min_pts=outlier_min_pts, orient=orient, upright=upright))
+    if normals == _NORMALS_DEFAULT:
+        normals = "sensor"
     if normals is not None and normals != "sensor":
         raise ValueError("decode_frames: normals must be None or \"sensor\", got %r" % (normals,))
     if normals == "sensor" and viewpoint is not None:
@@ -460,8 +519,39 @@ def decode_frames(depth, poses, intrinsics, colour=None, device="cuda", depth_sc
     return out
 
 
+def _decode_fused(depth, poses, intrinsics, colour, device, depth_scale, depth_min, depth_max, stride, edge, normals, sem_label,
+                  ins_label, fuse_kw, chain):
+    """decode_frames with `fuse`: every exclusion on the host first, then fuse_frames, then decode_points' chain."""
+    if normals == _NORMALS_DEFAULT:
+        normals = "tsdf"
+    if normals == "sensor":
+        raise ValueError("decode_frames: normals=\"sensor\" needs one frame per point, which a fused point does not have; "
+                         "give \"tsdf\" or None with fuse")
+    if normals is not None and normals != "tsdf":
+        raise ValueError("decode_frames: normals must be None or \"tsdf\" with fuse, got %r" % (normals,))
+    if sem_label is not None or ins_label is not None:
+        raise ValueError("decode_frames: sem_label / ins_label cannot be given with fuse: labels are not fused per voxel")
+    if isinstance(stride, bool) or stride != 1:
+        raise ValueError("decode_frames: stride must be 1 with fuse (every depth sample is integrated), got %r" % (stride,))
+    opts = _decode_options("decode_frames", chain["k"], chain["kThresh"], chain["segMinVerts"], chain["viewpoint"],
+                           chain["return_graph"], chain["pitch"], chain["outlier_ratio"], chain["return_kept"], None, None,
+                           chain["n_classes"], chain["outlier_radius"], chain["outlier_min_pts"], chain["orient"], chain["upright"])
+    dev = torch.device(device)
+    depth, colour = (t if t is None or torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t)) for t in (depth, colour))
+    _, pose, _, _ = _frames._frames_args("decode_frames", depth, poses, intrinsics, colour, depth_scale, depth_min, depth_max, 1, edge)
+    surface = _frames.fuse_frames(depth.to(dev), pose.reshape(-1, 4, 4), intrinsics, None if colour is None else colour.to(dev),
+                                  depth_scale=depth_scale, depth_min=depth_min, depth_max=depth_max, edge=edge, **fuse_kw)
+    n = int(surface["xyz"].shape[0])
+    rgb = surface["rgb"] if colour is not None else torch.zeros(n, 3, dtype=torch.float32, device=dev)
+    fused = types.SimpleNamespace(nl=surface["nl"], weight=surface["weight"], turn=normals == "tsdf")
+    out = _decode_cloud(surface["xyz"], rgb, dev, None, opts, fused=fused)
+    out.update(n_blocks=surface["n_blocks"], centres=surface["centres"], skipped=surface["skipped"])
+    return out
+
+
 SCENE_BOOKKEEPING = ("votes", "members", "ins_old_id", "raw_index", "count", "flipped", "tree",
-                     "R", "plane", "floor", "height", "pixel", "frame", "centres", "frame_start", "skipped")   # of a decode, not of a scene on disk
+                     "R", "plane", "floor", "height", "pixel", "frame", "centres", "frame_start", "skipped",
+                     "fuse_weight", "n_blocks")   # of a decode, not of a scene on disk
 
 
 def save_decoded(npy_dir, scene, decoded, sem_label=None, ins_label=None):
