@@ -297,7 +297,10 @@ int pbn_bn_act_train_backward(const void* x, int ld_x, const void* dy, int ld_dy
  *                              and totals int32[K] (pairs per offset) -- the caller reads the totals back, gives every
  *                              offset ceil(total/seg) segments of `seg` pairs and passes their first-segment indices
  *   pbn_rulebook_pair_fill   : in_idx / out_idx int32[n_segments * seg] (-1 = padding; int64 until round 3), seg_offset int64[n_segments]
- * Pairs of an offset keep ascending output-row order; positions are prefix counts (no atomics): deterministic. */
+ *                              the caller passes n_segments >= the segments the map needs; a surplus segment reads -1 / offset 0
+ * nbr[o, k] >= 0 is a pair; EVERY negative value (not only -1) is "no pair".  Pairs of an offset keep ascending output-row
+ * order; positions are prefix counts (no atomics): deterministic.  More than 512 offsets: the counts succeed, the fill answers
+ * PBN_ERR_UNSUPPORTED.  A refused fill has written nothing. */
 int pbn_rulebook_pair_blocks(int n);
 int pbn_rulebook_pair_counts(const int32_t* nbr, int n, int n_offsets, int32_t* table, int32_t* totals, pbn_stream_t stream);
 int pbn_rulebook_pair_fill(const int32_t* nbr, int n, int n_offsets, const int32_t* table, const int32_t* seg_start, int seg,
@@ -307,15 +310,18 @@ int pbn_rulebook_pair_fill(const int32_t* nbr, int n, int n_offsets, const int32
  * pbn_rulebook_pair_counts and the fill: a training step builds ~40 maps): seg_begin int32[n_offsets + 1] is computed on the
  * device from `totals`, in_idx / out_idx / seg_offset must hold the worst case of n * n_offsets / segment + n_offsets
  * segments, only the segments below seg_begin[n_offsets] are written and may be read.  The tail of an offset's last segment
- * is NOT padded: the consumer bounds every offset by its pair count (pbn_spconv_wgrad: pair_counts = `totals`).  One launch
- * (every block derives seg_begin from the totals itself); n_offsets <= 512. */
+ * is NOT padded -- the slots behind an offset's pair count are not written at all --: the consumer bounds every offset by its
+ * pair count (pbn_spconv_wgrad: pair_counts = `totals`).  One launch (every block derives seg_begin from the totals itself);
+ * n_offsets <= 512, beyond that PBN_ERR_UNSUPPORTED with nothing written. */
 int pbn_rulebook_pair_fill_dev(const int32_t* nbr, int n, int n_offsets, const int32_t* table, const int32_t* totals,
                                int segment, int32_t* seg_begin, int32_t* in_idx, int32_t* out_idx, int64_t* seg_offset,
                                pbn_stream_t stream);
 
 /* pbn_rulebook_pairs_multi -- counts + device-side fill (the two calls above) of up to 16 maps in THREE launches: the
  * training executor needs the lists of all 14 maps of a lineage, most of them small (a launch costs more than their work).
- * Per job the buffers of pbn_rulebook_pair_counts / _fill_dev (table int32[max(pbn_rulebook_pair_blocks(n), 1) * n_offsets]). */
+ * Per job the buffers of pbn_rulebook_pair_counts / _fill_dev (table int32[max(pbn_rulebook_pair_blocks(n), 1) * n_offsets]; an
+ * empty map keeps one block, which zeroes its table row and publishes its seg_begin).  n_jobs outside 1..16, segment < 1 or a NULL
+ * among a job's buffers: PBN_ERR_ARG; a job of more than 512 offsets: PBN_ERR_UNSUPPORTED; either way nothing is launched. */
 typedef struct {
     const int32_t* nbr;
     int32_t n, n_offsets;
@@ -428,7 +434,9 @@ int pbn_mlp_rows(const void* in, int ld_in, int in_rows, int channels, const int
  * pbn_select_points -- network/PBNet.py:151-170: the points of the kept classes in class-major order, ascending point
  * index inside a class (what a stable sort by class yields), written straight to the grouping inputs:
  *   position(i) = class_base[c] + #(j < i with class c);   class_base[c] < 0 drops the class.
- *   ins_ind[pos] = i, ins_orig[pos] = xyz[i], ins_off[pos] = xyz[i] + float(offset[i]) (fp32 add), ins_sem[pos] = c. */
+ *   ins_ind[pos] = i, ins_orig[pos] = xyz[i], ins_off[pos] = xyz[i] + float(offset[i]) (fp32 add), ins_sem[pos] = c.
+ * A negative sem_pred belongs to no class (not selected, no position); labels >= n_cls are not allowed.  class_base need not
+ * ascend with the class: the kept classes' ranges must be disjoint, in any order.  Positions no point is sent to are not written. */
 int pbn_select_blocks(int n);
 int pbn_sem_argmax_table(const void* score, int ld, int n_cls, const int32_t* batch, int nb, int n, int dtype,
                          int64_t* sem_pred, void* sem_prob, int32_t* table, int32_t* block_hist, pbn_stream_t stream);

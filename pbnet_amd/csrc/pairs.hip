@@ -205,15 +205,15 @@ extern "C" int pbn_rulebook_pair_fill(const int32_t* nbr, int n, int n_offsets, 
                                       pbn_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (n_segments < 0) return PBN_ERR_ARG;
-    PBN_TRY(pair_map_check(n, n_offsets, seg, false, {}));
+    PBN_TRY(pair_map_check(n, n_offsets, seg, true, {}));
     if (n_segments == 0) return PBN_OK;
-    PBN_TRY(pair_map_check(n, n_offsets, seg, false, {in_idx, out_idx, seg_offset}));
+    PBN_TRY(pair_map_check(n, n_offsets, seg, true, {in_idx, out_idx, seg_offset}));
+    if (n > 0) PBN_TRY(pair_map_check(n, n_offsets, seg, true, {nbr, table, seg_start}));    // every refusal before the first write
     // padding slots (and surplus segments) read as -1 / offset 0
     PBN_TRY(fill_bytes(in_idx, 0xff, sizeof(int32_t) * (size_t)n_segments * seg, stream));
     PBN_TRY(fill_bytes(out_idx, 0xff, sizeof(int32_t) * (size_t)n_segments * seg, stream));
     PBN_TRY(fill_bytes(seg_offset, 0, sizeof(int64_t) * (size_t)n_segments, stream));
     if (n == 0) return PBN_OK;
-    PBN_TRY(pair_map_check(n, n_offsets, seg, true, {nbr, table, seg_start}));
     hipLaunchKernelGGL(k_pair_fill, dim3(pbn_rulebook_pair_blocks(n)), dim3(TPB), 0, stream, nbr, n, n_offsets, table, seg_start,
                        (const int*)nullptr, (int*)nullptr, seg, in_idx, out_idx, (long long*)seg_offset);
     PBN_LAUNCH_CHECK();
@@ -242,9 +242,8 @@ extern "C" int pbn_rulebook_pairs_multi(const pbn_pair_job* jobs, int n_jobs, in
     int blocks = 0, cols = 0;
     for (int j = 0; j < n_jobs; ++j) {
         const pbn_pair_job& q = jobs[j];
-        if (pair_map_check(q.n, q.n_offsets, segment, true,
-                           {q.totals, q.seg_begin, q.nbr, q.table, q.in_idx, q.out_idx, q.seg_offset}) != PBN_OK)
-            return PBN_ERR_ARG;
+        PBN_TRY(pair_map_check(q.n, q.n_offsets, segment, true,
+                               {q.totals, q.seg_begin, q.nbr, q.table, q.in_idx, q.out_idx, q.seg_offset}));
         J.nbr[j] = q.nbr; J.table[j] = q.table; J.totals[j] = q.totals; J.seg_begin[j] = q.seg_begin;
         J.in_idx[j] = q.in_idx; J.out_idx[j] = q.out_idx; J.seg_offset[j] = (long long*)q.seg_offset;
         J.n[j] = q.n; J.K[j] = q.n_offsets;
